@@ -8,11 +8,18 @@ six partial products accumulated in fp32, csrc/mlp_rw.hip). `--dtype f16x2` sele
 = one mpc_step, i.e. one mpcd_mpc_step call: context upload, Philox x_T + the denoising loop (2 net evaluations
 per step) + clip flag + fp64 rollout/cost + argmin + winner row (+ RCCL cost all-gather and winner exchange for
 N > 1) + the applied trajectory to the host. Strong scaling: the workload's B candidates are split
-over the ranks; a multi-rank run also times the weak form (B per rank) and reports it beside the value as
-"weak_scaling".
+over the ranks.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg1..cfg5|panda] [--dtype ...]
+                  [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (roofline included: it is arithmetic
+on the timed steps' own HIP events and a stored PMC file). `--dump-outputs DIR` then writes what the last timed
+step returned (the MPCResult's arrays; the Panda chain) as DIR/<name>.npy: same arguments, same inputs, so two
+builds compare output for output. `--full` adds the measurements that take runs of their own: the CPU baseline,
+the strong-scaling shard probes, on several ranks the other scaling form ("weak_scaling" beside a strong value)
+and, for the Panda workload, the B = 64 throughput leg.
 
 `--gpus N` without torchrun starts the N rank processes itself (launch_ranks); under torchrun --gpus must
 equal WORLD_SIZE. `--exchange gloo` rehearses the multi-rank bench with every rank on cuda:0.
@@ -179,6 +186,26 @@ def cpu_baseline(cfg, budget_s=12.0):
                       f"process's share); per-candidate cost is linear in B, so cand/s at B={cfg['B']} is the same"}
 
 
+DUMP_CAP = 24 << 20  # bytes per dumped array; a larger one is a fixed seeded sample of its rows
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, float32 or float64 (integers exactly, as float64). An
+    array over DUMP_CAP is cut to a seeded sample of its leading-axis rows (sorted, the same from run to run)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        if a.dtype != np.float32:
+            a = a.astype(np.float64)
+        if a.nbytes > DUMP_CAP:
+            keep = max(1, DUMP_CAP // (a.nbytes // a.shape[0]))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 PANDA_CKPT = os.path.join(ROOT, "tests", "golden", "panda_test6_117600_ema.safetensors")
 PANDA_REF_S = 0.3615  # BASELINE.md / SURVEY §6: the reference's median Panda control step (unspecified CUDA GPU)
 
@@ -191,7 +218,8 @@ def panda(args):
     panda_test6_117600 EMA net (ConditionedTemporalUnet d=7, C=20, N=25, the checkpoint's schedule buffers),
     timed host-side around the call and a stream synchronisation, as the reference's time.time() pair around
     diffusion_sampling (its TimerCUDA synchronises). States ~ U[-1, 1]^20 with limits [-1, 1] (the training
-    data behind the reference's limits is not shipped). Also: the same step at B = 64 candidates (throughput)."""
+    data behind the reference's limits is not shipped). --full: also the same step at B = 64 candidates
+    (throughput)."""
     from safetensors.torch import load_file
 
     from mpc_via_diffusion_model_amd import DiffusionMPC, NetSpec
@@ -217,7 +245,7 @@ def panda(args):
            "(tests/golden), synthetic states ~ U[-1,1]^20", "vs_baseline": None,
            "reference_published_s": {"median": PANDA_REF_S, "note": "BASELINE.md / SURVEY §6, unspecified CUDA GPU "
                                      "(eager PyTorch); context only, different hardware"}}
-    for B in (1, 64):
+    for B in (1, 64) if args.full else (1,):
         xs = rng.uniform(-1, 1, (warmup + steps, 20))
         for i in range(warmup):
             control_step(xs[i], B, i)
@@ -234,6 +262,8 @@ def panda(args):
                "candidates_per_s": B / float(np.median(lat))}
         if B == 1:
             out.update(value=rec["p50_s"], ms_per_step=1e3 * rec["p50_s"], latency_b1=rec)
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, {"chain": chain})
         else:
             out["throughput_b64"] = rec
     form = plan.unet_form("ddpm_cfg")
@@ -305,12 +335,18 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="timed control steps (default 50; U-Net configs 5)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed control steps (default 20: the shader clock settles over the first dozen launches; U-Net configs 2, the first one runs the tiling autotune)")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
-                    help="strong (default, SURVEY §8d): the workload's B_total candidates split over the ranks (a "
-                         "multi-rank run also times the weak form beside it); weak: every GPU runs B candidates and "
-                         "the units all ranks process add up")
+                    help="strong (default, SURVEY §8d): the workload's B_total candidates split over the ranks (with "
+                         "--full a multi-rank run also times the weak form beside it); weak: every GPU runs B "
+                         "candidates and the units all ranks process add up")
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS) + ["panda"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-shard-probe", action="store_true", help="skip the strong-scaling shard probes (kernel traces)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline, the strong-scaling shard "
+                         "probes, on several ranks the other scaling form, for panda the B = 64 throughput leg")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-shard-probe", action="store_true",
+                    help="with --full: skip the strong-scaling shard probes (kernel traces)")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--candidates", type=int, default=None,
                     help="override the workload's B (profiling a shard size; the line then names the changed config)")
@@ -403,10 +439,14 @@ def main():
         return el, kms, res
 
     elapsed, kms, r = timed(b_local)
-    # a multi-rank run also times the other form in the same job: weak beside a strong value (B per rank, the
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"u0": r.u0, "u_best": r.u_best, "best_cost": [r.best_cost],
+                                         "best_index": [r.best_index], "flags": [r.flags], "costs": r.costs,
+                                         "u_norm": r.u_norm})
+    # --full, several ranks: the other form timed in the same job: weak beside a strong value (B per rank, the
     # units of all ranks added), strong beside a weak one (the workload's B over the ranks)
     other = None
-    if world > 1:
+    if world > 1 and args.full:
         b_o = cfg["B"] if scaling == "strong" else cfg["B"] // world
         el_o, kms_o, r_o = timed(b_o)
         other = {"candidates_total": b_o * world, "candidates_per_gpu": b_o, "steps": steps,
@@ -416,7 +456,7 @@ def main():
     # strong scaling: the shard each of P = 2, 4, 8 GPUs gets (B_total / P candidates), measured here on one GPU;
     # (ms_per_step at B_total) / (ms_per_step at B_total / P) is the compute-only P-GPU speedup bound
     shard_probe = []
-    if world == 1 and not args.no_shard_probe:
+    if world == 1 and args.full and not args.no_shard_probe:
         ms_full = 1e3 * elapsed / steps
         for div in (2, 4, 8):
             if cfg["B"] % div:
@@ -553,7 +593,7 @@ def main():
                         "(before the per-step exchange); speedup_bound = ms_per_step(B_total) / ms_per_step(shard) "
                         "is the compute-only P-GPU bound",
                 "shards": shard_probe}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_budget)
         else:
             out["cpu_baseline"] = None

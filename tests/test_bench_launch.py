@@ -49,11 +49,32 @@ def _line(r):
 
 
 @pytest.mark.gpu
+@pytest.mark.timeout(120)
+def test_plain_run_times_the_asked_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run (no --full) carries the headline figures only - no CPU baseline, no shard probes - and
+    --dump-outputs writes the last timed step's MPCResult as float32 / float64 .npy files that agree with the line."""
+    import numpy as np
+    out = _line(_run(["--gpus", "1", "--workload", "cfg1", "--steps", "2", "--warmup", "1", "--dump-outputs",
+                      str(tmp_path)], timeout=100))
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["value"] > 0
+    assert out["ms_per_step"] == pytest.approx(1e3 * 64 / out["value"])  # cfg1: 64 candidates per timed step
+    assert out["cpu_baseline"] is None and "strong_shard_probe" not in out
+    got = {f[:-4]: np.load(tmp_path / f) for f in sorted(os.listdir(tmp_path))}
+    assert sorted(got) == ["best_cost", "best_index", "costs", "flags", "u0", "u_best", "u_norm"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["u_norm"].shape == (64, 16, 2) and got["costs"].shape == (64,) and got["u_best"].shape == (16, 2)
+    assert got["best_cost"][0] == out["best_cost_last_step"] == got["costs"].min()
+    assert got["costs"][int(got["best_index"][0])] == got["best_cost"][0]
+    np.testing.assert_array_equal(got["u0"], got["u_best"][0])
+
+
+@pytest.mark.gpu
 @pytest.mark.timeout(400)
 def test_bench_two_ranks_on_one_gpu_default_is_strong():
     """The default multi-rank line is SURVEY §8d's strong scaling: cfg2's 4,096 candidates split over the ranks,
     value = 4,096 x steps / time; the weak form (4,096 per rank) is reported beside it."""
-    out = _line(_run(["--gpus", "2", "--exchange", "gloo", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]))
+    out = _line(_run(["--gpus", "2", "--exchange", "gloo", "--steps", "3", "--warmup", "1", "--full",
+                      "--no-cpu-baseline"]))
     assert out["n_gpus"] == 2 and out["scaling"] == "strong"
     assert out["config"]["candidates_total"] == 4096 and out["config"]["candidates_per_gpu"] == 2048
     assert out["config"]["parallelism"] == "dp2" and "gloo" in out["config"]["exchange"]
@@ -67,7 +88,7 @@ def test_bench_two_ranks_on_one_gpu_default_is_strong():
 @pytest.mark.timeout(400)
 def test_bench_two_ranks_on_one_gpu_weak_reports_the_strong_split():
     out = _line(_run(["--gpus", "2", "--exchange", "gloo", "--scaling", "weak", "--steps", "3", "--warmup", "1",
-                      "--no-cpu-baseline"]))
+                      "--full", "--no-cpu-baseline"]))
     assert out["n_gpus"] == 2 and out["scaling"] == "weak"
     assert out["config"]["candidates_total"] == 8192 and out["config"]["candidates_per_gpu"] == 4096
     st = out["strong_scaling"]

@@ -8,9 +8,8 @@ import torch
 from oracle import nets, sampler, schedule
 from oracle import systems as osys
 
-REF = "/root/reference"
-CKPT = os.path.join(REF, "trained_models", "cart_pole_84000_test1", "final", "checkpoints",
-                    "ema_model_current_state_dict.pth")
+# the reference's cart_pole_84000_test1 EMA state dict, every tensor as stored (tests/golden/make_kat3.py)
+CKPT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cart_pole_84000_test1_ema.safetensors")
 
 
 def test_kat1_exponential_schedule_values():
@@ -46,9 +45,9 @@ def test_kat2_parameter_counts():
     assert nets.param_count(nets.ConditionedMLPNet(state_dim=2, horizon=16, context_dim=4)) == 119072
 
 
-@pytest.mark.skipif(not os.path.exists(CKPT), reason="reference checkpoint not present")
 def test_kat2_kat3_trained_checkpoint_trace():
-    sd = torch.load(CKPT, map_location="cpu", weights_only=True)
+    from safetensors.torch import load_file
+    sd = load_file(CKPT)
     n_model = sum(v.numel() for k, v in sd.items() if k.startswith("model."))
     assert n_model == 1000929 and sum(v.numel() for v in sd.values()) == 1001229
     net = nets.ConditionedTemporalUnet(state_dim=1, context_dim=5).eval()

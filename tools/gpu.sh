@@ -44,6 +44,8 @@ run_job() {
     smoke)
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 ;;
     bench)
+      # the whole line: CPU baseline, shard probes and the other legs that bench.py keeps behind --full
+      local BENCH_ARGS="--full $BENCH_ARGS"
       local w=${arg:-cfg2}
       timeout -k 10 600 python -u bench.py --workload "$w" $BENCH_ARGS > "gpurun_out/bench_$w.log" 2>&1 ;;
     trace)
@@ -60,7 +62,9 @@ run_job() {
           > "gpurun_out/prof/pmc_${w}_$c.log" 2>&1 || return $?
       done ;;
     mlpab)
-      # cfg2 bench line of an experiment build (python -m mpc_via_diffusion_model_amd.build <variant> DEF=..)
+      # cfg2 bench line of an experiment build (python -m mpc_via_diffusion_model_amd.build <variant> DEF=..),
+      # with the strong-scaling shard probes (--full)
+      local BENCH_ARGS="--full $BENCH_ARGS"
       MPCD_LIB=$PWD/mpc_via_diffusion_model_amd/libmpcd_$arg.so timeout -k 10 300 python -u bench.py --workload cfg2 \
         --no-cpu-baseline $BENCH_ARGS > "gpurun_out/mlpab_$arg.log" 2>&1 ;;
     l2pmc)
