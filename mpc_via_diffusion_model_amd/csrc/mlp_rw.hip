@@ -15,6 +15,15 @@
 // first, k-chunks in order, accumulators initialised from the bias / cond tables), Mish, split and
 // denoise update as mlp_x3_kernel, so its results are bit-identical to the streaming kernel's
 // (tests/test_gpu_mlp.py checks it).
+//
+// The 8-wave form (layout rw32x8, W = 8: two waves per SIMD, 32 rows) splits each layer's n-tiles over twice the
+// waves, keeps Linear 5, 6 and half of Linear 7 resident (120 AGPRs of a wave's 256 registers), streams the rest
+// one layer ahead, and has waves 4-7, idle in the 32-wide layers, draw the noise. Bit-identical to the 4-wave form
+// (tests/test_gpu_mlp_rw8.py). Measured against rw32, alternating on one box (profiles/rw8_ab.txt): kernel 1.069 vs
+// 1.084 ms at cfg2 (0.986x), 4.246 vs 4.313 ms at 16,384 candidates (0.984x) - a small gain, far from the 0.90x hoped
+// for: the two waves of a SIMD run each layer in lock step between the same workgroup barriers (MFMA busy 0.34 of
+// the shader cycles per SIMD, as before), so the matrix pipe's idle time is mostly shared, not filled. It is the
+// default wherever rw32 was.
 #include <hip/hip_runtime.h>
 
 #include "mlp_x3.h"
@@ -30,6 +39,10 @@ constexpr int RES_NL = 3;
 constexpr int RES_G = RES_NL * 2 * 4;  // groups (layer, n-tile j, k-chunk) of 3 plane fragments per wave: 24
 constexpr int RES_AG = 21;             // groups 0..20 resident in AGPRs (63 fragments, 252 registers); the
                                        // last three (layer 7, n-tile w + 4, k-chunks 1-3) stream each step
+// The 8-wave form (rw32x8: two waves per SIMD, 256 registers each, at most 128 of them AGPRs): wave w owns n-tile
+// w of the 128-wide layers, 12 groups; Linear 5, 6 and k-chunks 0-1 of Linear 7 are resident (30 fragments, 120
+// AGPRs), k-chunks 2-3 of Linear 7 stream each step. Waves w and w + 4 share a SIMD.
+constexpr int RES_AG8 = 10;
 
 // Six partial products of one 32-k chunk with the weight planes in AGPRs (the A operand of an MFMA may be
 // an AGPR on gfx950; hipcc does not allocate builtin operands there, so the chain is written out). One
@@ -155,11 +168,43 @@ MPCD_DEV f32x4 mfma_agpr1(const u32x4 &w, const u32x4 &x, f32x4 acc)
 #error "wrong-result timing switches build only as an experiment variant (build.py variant: -DMPCD_VARIANT)"
 #endif
 
-template <int D0, int SMODE, bool CTX, int R>
+// The 8-wave form's own tuning switches (same results either way; profiles/rw8_ab.txt):
+// MPCD_RW8_PF: operand k-chunks read ahead (1: the partner wave of the SIMD covers LDS latency too; 2 measured 0.7 %
+// slower at 16,384 candidates and the same at 4,096)
+#ifndef MPCD_RW8_PF
+#define MPCD_RW8_PF 1
+#endif
+// MPCD_RW8_FLIP = 1: waves 4-7 run the two column tiles of a 128-wide layer in the opposite order to waves 0-3
+// (a phase offset between the two waves of a SIMD, which otherwise reach MFMAs, epilogue and barrier together)
+#ifndef MPCD_RW8_FLIP
+#define MPCD_RW8_FLIP 1
+#endif
+// MPCD_RW8_PRIO = 1: one static s_setprio 1 for waves 4-7 before the step loop
+#ifndef MPCD_RW8_PRIO
+#define MPCD_RW8_PRIO 0
+#endif
+
+// W = 4: one wave per SIMD (rw32 / rw16). W = 8: two per SIMD, 32 rows (rw32x8), the same sums in the same
+// order; only which wave computes a pass, and when, differs.
+template <int D0, int SMODE, bool CTX, int R, int W = RW_W>
 struct MlpRw {
     static constexpr int NB = (SMODE == MODE_DDIM || SMODE == MODE_EPS1) ? 1 : 2;
     static constexpr bool IS_DDPM = SMODE == MODE_DDPM_CFG || SMODE == MODE_DDPM_XN;
     static_assert(R == 32 || R == 16, "32 or 16 rows per workgroup");
+    static_assert(W == 4 || (W == 8 && R == 32), "4 waves, or 8 waves at 32 rows");
+    // the 8-wave form implements the default arms of the MPCD_RW_* switches only
+    static_assert(W == 4 || (MPCD_RW_ILV && MPCD_RW_EPI_STEPS && MPCD_RW_PKTAIL && MPCD_RW_XREG && MPCD_RW_TABLE_EARLY &&
+                             MPCD_RW_TABLE_SIDE && !MPCD_RW_EXP_NOLASTEPI && !MPCD_RW_EXP_BAR2 && !MPCD_RW_EXP_NOVM),
+                  "rw32x8 builds with the default MPCD_RW_* arms");
+    static constexpr int NTH = 64 * W;      // threads
+    // W = 8 at H*d = 128 (Linear 0's 12 fragments, two update quads per lane): operands one k-chunk ahead and the next
+    // step's Linear 0 fragments issued after the update, or the kernel spills
+    static constexpr int PF8 = D0 == 128 ? 1 : MPCD_RW8_PF;
+    static constexpr bool W0_LATE = D0 == 128;
+    static constexpr int TPL = 8 / W;       // n-tiles of a 128-wide layer per wave
+    static constexpr int NRG = RES_NL * TPL * 4;          // groups (layer, n-tile j, k-chunk) per wave
+    static constexpr int NAG = W == 8 ? RES_AG8 : RES_AG;  // of them resident in AGPRs
+    static_assert(W == 8 || NRG == RES_G);
     static constexpr int NCT = R / 16;  // 16-row column tiles
     using A = Arch<D0>;
     using L = Lds3<D0, NB, R>;
@@ -183,11 +228,29 @@ struct MlpRw {
     // Layer l's work per wave. N = 32 at 32 rows (SPL): wave w -> n-tile w & 1, column tile w >> 1. Otherwise
     // wave w -> n-tiles w + 4j (j < T) for every column tile; a wave with no tile (N = 32 at 16 rows) loads
     // a clamped copy and computes nothing.
-    template <int l> static constexpr bool SPL = A::N[l] == 32 && NCT == 2;
-    template <int l> static constexpr int TL = SPL<l> ? 1 : (A::N[l] / 16 + 3) / 4;
+    //
+    // W = 8, hidden layers (one pass or two per wave, T = 1): N = 128: wave w -> n-tile w, both column tiles (waves
+    // 4-7 in the opposite order, MPCD_RW8_FLIP); N = 64: n-tile w & 3, column tile w >> 2; N = 32: waves 0-3 as
+    // at W = 4, waves 4-7 idle. The final layer (l = 13) keeps the 4-wave mapping on waves 0-3 (n-tiles w + 4j,
+    // a candidate's two CFG rows in one lane); waves 4-7 load clamped copies and skip it.
+    template <int l> static constexpr bool HID = l != NLAYER - 1;
+    template <int l> static constexpr bool SPL = W == 8 ? (HID<l> && A::N[l] <= 64) : (A::N[l] == 32 && NCT == 2);
+    template <int l> static constexpr int TL = (SPL<l> || (W == 8 && HID<l>)) ? 1 : (A::N[l] / 16 + 3) / 4;
     template <int l> static constexpr int CL = SPL<l> ? 1 : NCT;
-    template <int l> static MPCD_DEV int nt_of(int wave, int j) { return SPL<l> ? (wave & 1) : wave + 4 * j; }
-    template <int l> static MPCD_DEV int ct_of(int wave, int c) { return SPL<l> ? (wave >> 1) : c; }
+    template <int l> static MPCD_DEV int nt_of(int wave, int j)
+    {
+        if constexpr (W == 8) return !HID<l> ? (wave & 3) + 4 * j : A::N[l] == 128 ? wave : A::N[l] == 64 ? (wave & 3) : (wave & 1);
+        return SPL<l> ? (wave & 1) : wave + 4 * j;
+    }
+    template <int l> static MPCD_DEV int ct_of(int wave, int c)
+    {
+        if constexpr (W == 8) return !SPL<l> ? (MPCD_RW8_FLIP && HID<l> ? c ^ (wave >> 2) : c) : A::N[l] == 64 ? (wave >> 2) : ((wave >> 1) & 1);
+        return SPL<l> ? (wave >> 1) : c;
+    }
+    // a wave with no tile in hidden layer l (it still runs the layer's side work, loads and barriers)
+    template <int l> static MPCD_DEV bool idle_of(int wave) { return W == 8 && HID<l> && A::N[l] == 32 && wave >= 4; }
+    // waves that run the final layer and the update, and hold x_t / the noise
+    static MPCD_DEV bool upd_wave(int wave) { return W == 4 || wave < 4; }
 
     // ONE buffer descriptor over the whole weight pack for every streamed layer (the layer offset goes into the
     // soffset): per-layer descriptors, kept live across the step loop, cost 4 SGPRs each and pushed ~50 SGPRs into
@@ -242,28 +305,28 @@ struct MlpRw {
     // Resident fragments: group g = ((li * 2 + j) * 4 + kc), planes 0..2 (AGPRs); Tail: groups RES_AG.. of
     // layer 7, streamed like the other layers (VGPRs)
     struct Res {
-        u32x4 a[RES_AG][3];
+        u32x4 a[NAG][3];
     };
     struct Tail {
-        u32x4 v[RES_G - RES_AG][3];
+        u32x4 v[NRG - NAG][3];
     };
     static MPCD_DEV void load_tail1(Tail &t, const float *__restrict__ wp, int wave, int lane16, int f)
     {
         const __amdgpu_buffer_rsrc_t rs = pack_rsrc(wp);
-        const int g = RES_AG + f / 3, pl = f % 3, j = (g / 4) & 1, kc = g & 3, nt = wave + 4 * j;
+        const int g = NAG + f / 3, pl = f % 3, j = (g / 4) % TPL, kc = g & 3, nt = wave + 4 * j;
         const int soff = __builtin_amdgcn_readfirstlane(woffx<D0>(RES_L0 + RES_NL - 1) * 4 + ((nt * 4 + kc) * 3 + pl) * 1024);
-        t.v[g - RES_AG][pl] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, soff, 0));
+        t.v[g - NAG][pl] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, soff, 0));
     }
     static MPCD_DEV void load_tail(Tail &t, const float *__restrict__ wp, int wave, int lane16)
     {
         const __amdgpu_buffer_rsrc_t rs = pack_rsrc(wp);
 #pragma unroll
-        for (int g = RES_AG; g < RES_G; ++g) {
-            const int j = (g / 4) & 1, kc = g & 3, nt = wave + 4 * j;
+        for (int g = NAG; g < NRG; ++g) {
+            const int j = (g / 4) % TPL, kc = g & 3, nt = wave + 4 * j;
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) {
                 const int soff = __builtin_amdgcn_readfirstlane(woffx<D0>(RES_L0 + RES_NL - 1) * 4 + ((nt * 4 + kc) * 3 + pl) * 1024);
-                t.v[g - RES_AG][pl] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, soff, 0));
+                t.v[g - NAG][pl] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, soff, 0));
             }
         }
     }
@@ -271,8 +334,8 @@ struct MlpRw {
     static MPCD_DEV void load_res(Res &r, const float *__restrict__ wp, int wave, int lane)
     {
 #pragma unroll
-        for (int g = 0; g < RES_AG; ++g) {
-            const int li = g / 8, j = (g / 4) & 1, kc = g & 3;
+        for (int g = 0; g < NAG; ++g) {
+            const int li = g / (4 * TPL), j = (g / 4) % TPL, kc = g & 3;
             const int nt = wave + 4 * j;
             const float *base = wp + woffx<D0>(RES_L0 + li) + (size_t)((nt * 4 + kc) * 3) * 256 + lane * 4;
 #pragma unroll
@@ -378,6 +441,12 @@ struct MlpRw {
                 for (int k = 0; k < NS; ++k) side(k);
                 return;
             }
+        if constexpr (W == 8 && N == 32)
+            if (idle_of<l>(wave)) {  // waves 4-7: no tile; the side work, then the layer's barrier
+#pragma unroll
+                for (int k = 0; k < NS; ++k) side(k);
+                return;
+            }
         auto jp = [](int p) { return p / NC; };
         auto cp = [](int p) { return p % NC; };
         auto init_of = [&](int p) {
@@ -408,7 +477,7 @@ struct MlpRw {
             *reinterpret_cast<u32x2 *>(o + 2 * L::out_pl(l)) = p2;
         };
         // operand fragments read PF k-chunks ahead (a ring of PF + 1)
-        constexpr int PF = MPCD_RW_PF;
+        constexpr int PF = W == 8 ? PF8 : MPCD_RW_PF;
         u32x4 xb[PF + 1][3];
 #pragma unroll
         for (int i = 0; i < PF; ++i)
@@ -562,12 +631,12 @@ struct MlpRw {
 #if MPCD_RW_ILV
         hidden_ilv<RES_L0 + li, NS>(
             [&](int j, int kc, int m, const u32x4 (&x)[3], f32x4 acc) {
-                const int g = (li * 2 + j) * 4 + kc;
-                if (g >= RES_AG) return mfma_bf(t.v[g - RES_AG][wpl(m)], x[xpl(m)], acc);
+                const int g = (li * TPL + j) * 4 + kc;
+                if (g >= NAG) return mfma_bf(t.v[g - NAG][wpl(m)], x[xpl(m)], acc);
                 const bool first = kc == 0 && m == 0;
                 // LAST: the pass's last product, or the one before the VGPR-tail groups (a builtin MFMA then
                 // reads the result: srcC forwarding needs no wait, but the compiler may copy it between)
-                const bool last = (kc == 3 || g + 1 == RES_AG) && m == 5;
+                const bool last = (kc == 3 || g + 1 == NAG) && m == 5;
                 if (first && last) return mfma_agpr1<true, true>(r.a[g][wpl(m)], x[xpl(m)], acc);
                 if (first) return mfma_agpr1<true, false>(r.a[g][wpl(m)], x[xpl(m)], acc);
                 if (last) return mfma_agpr1<false, true>(r.a[g][wpl(m)], x[xpl(m)], acc);
@@ -577,9 +646,9 @@ struct MlpRw {
 #else
         hidden<RES_L0 + li>(
             [&](int j, int kc, const u32x4 (&x)[3], f32x4 acc) {
-                const int g = (li * 2 + j) * 4 + kc;
-                if (g < RES_AG) return mfma_x3_agpr(r.a[g][0], r.a[g][1], r.a[g][2], x, acc);
-                return mfma_x3(t.v[g - RES_AG], x, acc);
+                const int g = (li * TPL + j) * 4 + kc;
+                if (g < NAG) return mfma_x3_agpr(r.a[g][0], r.a[g][1], r.a[g][2], x, acc);
+                return mfma_x3(t.v[g - NAG], x, acc);
             },
             lds, wave, lane);
 #pragma unroll
@@ -636,9 +705,12 @@ struct MlpRw {
 #endif
     // x_t of the update's (n-tile j, column group g) quads, when MPCD_RW_XREG keeps it in registers
     static constexpr int XG = NB == 2 ? 1 : NCT;
+    // x_t in registers (MPCD_RW_XREG); the 8-wave form only where that is one quad per lane, else the fp32 copy in
+    // LDS (the same values: 256 registers per wave do not hold 2-4 quads beside the final layer's operands)
+    static constexpr bool XREG = MPCD_RW_XREG && (W == 4 || (D0 / 16 + 3) / 4 * XG == 1);
     static MPCD_DEV bool x_lane(int j, int wave, int col)
     {
-        return (D0 / 16 % 4 == 0 || wave + 4 * j < D0 / 16) && !(R == 16 && NB == 2 && col >= 8);
+        return upd_wave(wave) && (D0 / 16 % 4 == 0 || wave + 4 * j < D0 / 16) && !(R == 16 && NB == 2 && col >= 8);
     }
     static MPCD_DEV void load_xr(f32x4 (&xr)[NZT][XG], const char *lds, int wave, int lane)
     {
@@ -660,6 +732,7 @@ struct MlpRw {
 #ifdef MPCD_PROF_LAYERS
         uint64_t tmark = __builtin_readcyclecounter();
 #endif
+        if (!upd_wave(wave)) return;  // W = 8: waves 0-3 run the final layer (no barrier, no global load inside)
         constexpr int T = NZT, NT = D0 / 16;
         const int col = lane & 15, q = lane >> 4;
         const float *bias = reinterpret_cast<const float *>(lds + L::BI + A::boff(13) * 4);
@@ -673,9 +746,9 @@ struct MlpRw {
         u32x4 xf[NCT][3];
 #pragma unroll
         for (int c = 0; c < NCT; ++c) load_x3(xf[c], lds + L::T1 + (c * 16 + col) * L::RS + 16 * (q ^ swz(col)), L::PL);
-        // MPCD_RW_XREG, DDPM: the x-only products of the update under the operand reads' latency (each through a
+        // XREG, DDPM: the x-only products of the update under the operand reads' latency (each through a
         // fence, the same values as in the update's order: a x, c2 x, std z are separate roundings there too)
-        constexpr bool PRE = MPCD_RW_XREG && IS_DDPM;
+        constexpr bool PRE = XREG && IS_DDPM;
         f32x4 pax[T][XG], pcx[T][XG], psz[T][XG];
         if constexpr (PRE) {
             auto fn = [](float &v) { asm volatile("" : "+v"(v)); };
@@ -738,7 +811,7 @@ struct MlpRw {
                     }
                     continue;
                 }
-                const f32x4 x = MPCD_RW_XREG ? xr[j][g] : *reinterpret_cast<const f32x4 *>(lds + L::XB + (cl * L::SX + n) * 4);
+                const f32x4 x = XREG ? xr[j][g] : *reinterpret_cast<const f32x4 *>(lds + L::XB + (cl * L::SX + n) * 4);
                 f32x4 xn;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -785,8 +858,8 @@ struct MlpRw {
                     xn[r] = o;
                     am[g] = max(am[g], max(abs_bits(xv), abs_bits(o)));
                 }
-                store_x<!MPCD_RW_XREG>(lds, cl, n, xn);
-                if (MPCD_RW_XREG) xr[j][g] = xn;
+                store_x<!XREG>(lds, cl, n, xn);
+                if (XREG) xr[j][g] = xn;
                 if (gc < p.batch) {
                     if (p.chain) *reinterpret_cast<f32x4 *>(p.chain + ((size_t)(s + 1) * p.batch + gc) * D0 + n) = xn;
                     if (last) *reinterpret_cast<f32x4 *>(p.x_out + (size_t)gc * D0 + n) = xn;
@@ -913,25 +986,25 @@ struct MlpRw {
 
 #if MPCD_RW_EXP_NOLASTEPI
         // the timing experiment leaves output tiles unwritten: start from a zeroed LDS so they read finite values
-        for (int i = threadIdx.x; i < L::total / 16; i += RW_T) reinterpret_cast<u32x4 *>(lds)[i] = u32x4{0u, 0u, 0u, 0u};
+        for (int i = threadIdx.x; i < L::total / 16; i += NTH) reinterpret_cast<u32x4 *>(lds)[i] = u32x4{0u, 0u, 0u, 0u};
         lds_barrier();
 #endif
         Res res;
         load_res(res, wp, wave, lane);
         for (int l = 0; l < NLAYER; ++l)
-            for (int i = threadIdx.x; i < A::N[l]; i += RW_T) bi[A::boff(l) + i] = wp[woffx<D0>(l) + wfl<D0>(l) + i];
+            for (int i = threadIdx.x; i < A::N[l]; i += NTH) bi[A::boff(l) + i] = wp[woffx<D0>(l) + wfl<D0>(l) + i];
         for (int j = 0; j < 6; ++j)
-            for (int i = threadIdx.x; i < A::N[2 * j + 1]; i += RW_T)
+            for (int i = threadIdx.x; i < A::N[2 * j + 1]; i += NTH)
                 bic[cond_off(j) + i] = wp[woffx<D0>(2 * j + 1) + wfl<D0>(2 * j + 1) + i];
         // mpcd_mpc_step (ctx_fused): the shared context row's projection computed here, as ctx_prologue_row_kernel
         // would (the same function: the same bits), so the control step has no prologue launch
-        for (int i = threadIdx.x; i < COND_TOTAL; i += RW_T)
+        for (int i = threadIdx.x; i < COND_TOTAL; i += NTH)
             cps[i] = !CTX ? 0.f
                           : p.ctx_fused ? ctx_proj_col(p.ctx_row, p.ctx_dim, p.cond_layers, p.n_cond, p.cond_dim, i)
                                         : p.cproj[i];
         if (threadIdx.x < CPW) reinterpret_cast<uint32_t *>(lds + L::AMX)[threadIdx.x] = 0u;
         uint32_t am[2] = {0u, 0u};
-        for (int i = threadIdx.x; i < CPW * QUADS; i += RW_T) {  // x_T (fp32 + planes)
+        for (int i = threadIdx.x; i < CPW * QUADS; i += NTH) {  // x_T (fp32 + planes)
             const int c = i / QUADS, qd = i - c * QUADS;
             const int64_t gc = cand0 + c;
             f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -943,7 +1016,7 @@ struct MlpRw {
             store_x(lds, c, qd * 4, z);
         }
         f32x4 xr[NZT][XG];
-        if constexpr (MPCD_RW_XREG) {
+        if constexpr (XREG) {
             lds_barrier();
             load_xr(xr, lds, wave, lane);
         }
@@ -953,7 +1026,7 @@ struct MlpRw {
         load_ws<0>(w0, wp, wave, lane16);
         f32x4 nz[NZT][NB];
         StepPlan sp = load_plan(p.plan, 0);
-        fetch_noise(nz, p, sp, 0, cand0, wave, lane);
+        if constexpr (W == 4) fetch_noise(nz, p, sp, 0, cand0, wave, lane);
         const int tpi = threadIdx.x < COND_TOTAL / 4 ? (int)threadIdx.x : threadIdx.x < COND_TOTAL / 2 ? (int)threadIdx.x - COND_TOTAL / 4 : 0;
         f32x4 tpre = reinterpret_cast<const f32x4 *>(p.tproj)[tpi];
 #ifdef MPCD_PROF_LAYERS
@@ -980,10 +1053,17 @@ struct MlpRw {
 #endif
 #endif
 
+        if constexpr (W == 8 && MPCD_RW8_PRIO)
+            if (wave >= 4) __builtin_amdgcn_s_setprio(1);
+        int lane_l = lane;
         for (int s = 0; s < p.n_steps; ++s) {
             // launder the weight base: stops LICM hoisting the streamed layers' loads out of the loop
             asm volatile("" : "+s"(wofs), "+v"(lane16));
             const float *ws = wp + wofs;
+            // W = 8: the lane index laundered too. Hoisted out of the step loop, every layer's LDS addresses stand
+            // in registers for the whole launch, which 256 registers per wave do not hold (they spilled to scratch)
+            if constexpr (W == 8) asm volatile("" : "+v"(lane_l));
+            const int lane = lane_l;
             auto none = [](int) {};
             // Each layer's fragments are issued one at a time in the free MFMA slots of an earlier layer
             // (hidden_ilv side work): the vector-memory issue rides under MFMAs instead of stalling a layer, and
@@ -1008,10 +1088,15 @@ struct MlpRw {
                 table();
                 tpre = reinterpret_cast<const f32x4 *>(p.tproj + (size_t)(s + 1 < p.n_steps ? s + 1 : s) * COND_TOTAL)[tpi];
             }
+            // W = 8 (256 registers per wave, 120 of them resident weights): every streamed layer's fragments are
+            // issued one layer later than at W = 4, so that at most two layers' stand in registers at a time
             WS<3> w3;
-            layer<0, NFRAG<3>>(w0, [&](int k) { load_ws1<3>(w3, ws, wave, lane16, k); }, lds, wave, lane);
-            bar();
             WS<4> w4;
+            auto side3 = [&](int k) { load_ws1<3>(w3, ws, wave, lane16, k); };
+            auto side4 = [&](int k) { load_ws1<4>(w4, ws, wave, lane16, k); };
+            if constexpr (W == 8) layer<0>(w0, none, lds, wave, lane);
+            else layer<0, NFRAG<3>>(w0, side3, lds, wave, lane);
+            bar();
             WS<8> w8;
             Tail tail;
             WS<9> w9;
@@ -1045,38 +1130,89 @@ struct MlpRw {
 #endif
                 }
             };
-            layer<1, NFRAG<4>>(w1, [&](int k) { load_ws1<4>(w4, ws, wave, lane16, k); }, lds, wave, lane);
+            if constexpr (W == 8) layer<1, NFRAG<3>>(w1, side3, lds, wave, lane);
+            else layer<1, NFRAG<4>>(w1, side4, lds, wave, lane);
             bar();
-            layer<2>(w2, none, lds, wave, lane);
+            if constexpr (W == 8) layer<2, NFRAG<4>>(w2, side4, lds, wave, lane);
+            else layer<2>(w2, none, lds, wave, lane);
             bar();
             layer<3>(w3, none, lds, wave, lane);
             bar();
             layer<4>(w4, none, lds, wave, lane);
             bar();
-            constexpr int W8A = MPCD_RW_W8_SPLIT ? NFRAG<8> / 2 : 0;  // Linear 8 fragments issued during Linear 5
-            layer_res<0, W8A>(res, tail, [&](int k) { load_ws1<8>(w8, ws, wave, lane16, k); }, lds, wave, lane);
-            bar();
-            layer_res<1, NFRAG<8> - W8A>(res, tail, [&](int k) { load_ws1<8>(w8, ws, wave, lane16, W8A + k); }, lds, wave,
-                                         lane);
-            load_tail(tail, ws, wave, lane16);
-            bar();
-            layer_res<2>(res, tail, none, lds, wave, lane);
-            load_ws<9>(w9, ws, wave, lane16);
-            bar();
-            if (s + 1 < p.n_steps) sp = load_plan(p.plan, s + 1);
-            if constexpr (STAGED_NOISE) {
-                ph_init(ph, p, s + 2, cand0, wave, lane);  // step s + 1's noise is Philox slice s + 2 (fetch_noise)
-                layer<8, NPH>(w8, [&](int k) { ph_step(ph, k); }, lds, wave, lane);
+            if constexpr (W == 8) {
+                // 256 registers per wave, 120 of them resident weights: Linear 8's 24 fragments (96 registers) never
+                // stand whole. Its first W8P k-chunks are issued behind Linear 7's MFMAs (the Tail's registers die
+                // there as they are used), k-chunk c >= W8P in the MFMA slots of k-chunk c - W8P + 1 of Linear 8
+                // itself (into registers its first chunks have left), Linear 9's in the slots of k-chunk 6.
+                constexpr int W8P = 4, KC8 = A::K[8] / 32, S9 = 6 * 6;
+                static_assert(NFRAG<8> == KC8 * 3 && NFRAG<9> == 6 && W8P >= 2);
+                layer_res<0>(res, tail, none, lds, wave, lane);
+                bar();
+                layer_res<1>(res, tail, none, lds, wave, lane);
+                load_tail(tail, ws, wave, lane16);
+                bar();
+                layer_res<2>(res, tail, none, lds, wave, lane);
+#pragma unroll
+                for (int f = 0; f < W8P * 3; ++f) load_ws1<8>(w8, ws, wave, lane16, f);
+                bar();
+                if (s + 1 < p.n_steps) sp = load_plan(p.plan, s + 1);
+                auto stream8 = [&](int k) {
+                    const int kc = k / 6, m = k % 6;
+                    if (kc >= 1 && kc + W8P - 1 < KC8 && m < 3) load_ws1<8>(w8, ws, wave, lane16, (kc + W8P - 1) * 3 + m);
+                    if (k >= S9 && k < S9 + NFRAG<9>) load_ws1<9>(w9, ws, wave, lane16, k - S9);
+                };
+                layer<8, KC8 * 6>(w8, stream8, lds, wave, lane);
+                load_ws<10>(w10, ws, wave, lane16);
+                bar();
             } else {
-                layer<8>(w8, none, lds, wave, lane);
+                constexpr int W8A = MPCD_RW_W8_SPLIT ? NFRAG<8> / 2 : 0;  // Linear 8 fragments issued during Linear 5
+                layer_res<0, W8A>(res, tail, [&](int k) { load_ws1<8>(w8, ws, wave, lane16, k); }, lds, wave, lane);
+                bar();
+                layer_res<1, NFRAG<8> - W8A>(res, tail, [&](int k) { load_ws1<8>(w8, ws, wave, lane16, W8A + k); }, lds, wave,
+                                             lane);
+                load_tail(tail, ws, wave, lane16);
+                bar();
+                layer_res<2>(res, tail, none, lds, wave, lane);
+                load_ws<9>(w9, ws, wave, lane16);
+                bar();
+                if (s + 1 < p.n_steps) sp = load_plan(p.plan, s + 1);
+                if constexpr (STAGED_NOISE) {
+                    ph_init(ph, p, s + 2, cand0, wave, lane);  // step s + 1's noise is Philox slice s + 2 (fetch_noise)
+                    layer<8, NPH>(w8, [&](int k) { ph_step(ph, k); }, lds, wave, lane);
+                } else {
+                    layer<8>(w8, none, lds, wave, lane);
+                }
+                load_ws<10>(w10, ws, wave, lane16);  // after L8: w8's 96 registers are free again
+                bar();
             }
-            load_ws<10>(w10, ws, wave, lane16);  // after L8: w8's 96 registers are free again
-            bar();
-            layer<9, NFRAG<11> + NFRAG<12> + NFRAG<13>>(w9, side9, lds, wave, lane);
-            bar();
-            layer<10>(w10, none, lds, wave, lane);
-            noise_next();
-            load_ws<0>(w0, ws, wave, lane16);  // next step's layer 0 (unconditional: path-independent load count)
+            constexpr int NS9 = NFRAG<11> + NFRAG<12> + NFRAG<13>;
+            if constexpr (W == 8) {
+                // Linear 11-13's fragments behind the second half of Linear 10's MFMAs, where half of its own 12
+                // fragments are spent
+                constexpr int S10 = (A::K[10] / 32) * 6 / 2;
+                layer<9>(w9, none, lds, wave, lane);
+                bar();
+                // This step's noise, drawn (or fetched) by waves 4-7, which have no tile in Linear 10-12 and the final
+                // layer: lane for lane what wave - 4 would draw (fetch_noise: the same bits), handed over in the C0
+                // buffer, which is dead from Linear 8's barrier to the next step's Linear 5; the final layer reads it
+                // two barriers later. Waves 0-3 then carry no Philox state and no noise registers through the step.
+                if constexpr (IS_DDPM)
+                    if (wave >= 4) {
+                        f32x4 nzh[NZT][NB];
+                        fetch_noise(nzh, p, cur, s, cand0, wave - 4, lane);
+#pragma unroll
+                        for (int j = 0; j < NZT; ++j)
+                            *reinterpret_cast<f32x4 *>(lds + L::C0 + ((j * 4 + wave - 4) * 64 + lane) * 16) = nzh[j][0];
+                    }
+                layer<10, S10 + NS9>(w10, [&](int k) { if (k >= S10) side9(k - S10); }, lds, wave, lane);
+            } else {
+                layer<9, NS9>(w9, side9, lds, wave, lane);
+                bar();
+                layer<10>(w10, none, lds, wave, lane);
+                noise_next();
+                load_ws<0>(w0, ws, wave, lane16);  // next step's layer 0 (unconditional: path-independent load count)
+            }
             bar();
             layer<11>(w11, none, lds, wave, lane);
             bar();
@@ -1105,19 +1241,29 @@ struct MlpRw {
                 }
                 layer<12>(w12, none, lds, wave, lane);
             }
+            if constexpr (W == 8 && !W0_LATE) load_ws<0>(w0, ws, wave, lane16);  // next step's layer 0, behind the final layer
             bar();
+            if constexpr (W == 8) {
+#pragma unroll
+                for (int j = 0; j < NZT; ++j) {
+#pragma unroll
+                    for (int g = 0; g < NB; ++g) nzc[j][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (IS_DDPM && wave < 4) nzc[j][0] = *reinterpret_cast<const f32x4 *>(lds + L::C0 + ((j * 4 + wave) * 64 + lane) * 16);
+                }
+            }
 #ifdef MPCD_PROF_LAYERS
             final_and_update(w13, lds, p, cur, s, cand0, nzc, am, xr, wave, lane, tacc);  // "-" row: MFMAs / update
 #else
             final_and_update(w13, lds, p, cur, s, cand0, nzc, am, xr, wave, lane);
 #endif
+            if constexpr (W == 8 && W0_LATE) load_ws<0>(w0, ws, wave, lane16);  // H*d = 128: after the update's registers
         }
 #ifdef MPCD_PROF_LAYERS
         {
             const uint64_t t = __builtin_readcyclecounter();
             tacc[2 * 15] += t - tprev;
-            if (p.dbg && blockIdx.x < 32 / RW_W && lane == 0)  // 32 wave slots
-                for (int i = 0; i < 32; ++i) p.dbg[(blockIdx.x * RW_W + (threadIdx.x >> 6)) * 32 + i] = (float)tacc[i];
+            if (p.dbg && blockIdx.x < 32 / W && lane == 0)  // 32 wave slots
+                for (int i = 0; i < 32; ++i) p.dbg[(blockIdx.x * W + (threadIdx.x >> 6)) * 32 + i] = (float)tacc[i];
             if (p.dbg && threadIdx.x == 0) {  // per-block loop start / end (memrealtime, low 32 bits)
                 p.dbg[4096 + blockIdx.x * 2] = __builtin_bit_cast(float, (uint32_t)rt0);
                 p.dbg[4096 + blockIdx.x * 2 + 1] = __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_s_memrealtime());
@@ -1130,60 +1276,68 @@ struct MlpRw {
 #endif
         if (SMODE != MODE_EPS && SMODE != MODE_EPS1 && p.chain_absmax) {
             const int col = lane & 15;
-            store_chain_absmax<CPW, RW_T>(reinterpret_cast<uint32_t *>(lds + L::AMX), am, col,
+            store_chain_absmax<CPW, NTH>(reinterpret_cast<uint32_t *>(lds + L::AMX), am, col,
                                           (NB == 2 || R == 16) ? -1 : 16 + col, NB == 1 || R == 32 || col < 8,
                                           p.chain_absmax, cand0, p.batch);
         }
     }
 };
 
-template <int D0, int SMODE, bool CTX, int R>
-__global__ __launch_bounds__(RW_T, 1) void mlp_rw_kernel(const MlpSampleArgs p)
+template <int D0, int SMODE, bool CTX, int R, int W>
+__global__ __launch_bounds__(64 * W, 1) void mlp_rw_kernel(const MlpSampleArgs p)
 {
-    MlpRw<D0, SMODE, CTX, R>::run(p);
+    MlpRw<D0, SMODE, CTX, R, W>::run(p);
 }
 
-template <int D0, int SMODE, bool CTX, int R>
+template <int D0, int SMODE, bool CTX, int R, int W>
 hipError_t launch_rw_r(const MlpSampleArgs &a, hipStream_t stream)
 {
-    using L = Lds3<D0, MlpRw<D0, SMODE, CTX, R>::NB, R>;
+    using L = Lds3<D0, MlpRw<D0, SMODE, CTX, R, W>::NB, R>;
     static_assert(L::total <= 160 * 1024, "LDS budget (160 KiB per CU)");
-    if (hipError_t e = allow_max_lds<&mlp_rw_kernel<D0, SMODE, CTX, R>>(); e != hipSuccess) return e;
+    if (hipError_t e = allow_max_lds<&mlp_rw_kernel<D0, SMODE, CTX, R, W>>(); e != hipSuccess) return e;
     const int64_t blocks = (a.batch + L::CPW - 1) / L::CPW;
-    return launch_sampler_kernel(mlp_rw_kernel<D0, SMODE, CTX, R>, dim3((unsigned)blocks), dim3(RW_T), (size_t)L::total, stream, a);
+    return launch_sampler_kernel(mlp_rw_kernel<D0, SMODE, CTX, R, W>, dim3((unsigned)blocks), dim3(64 * W), (size_t)L::total, stream, a);
 }
 
+// the 8-wave form exists for the default arms of the MPCD_RW_* switches (an experiment build of another arm has none)
+constexpr bool RW8_BUILT = MPCD_RW_ILV && MPCD_RW_EPI_STEPS && MPCD_RW_PKTAIL && MPCD_RW_XREG && MPCD_RW_TABLE_EARLY &&
+                           MPCD_RW_TABLE_SIDE && !MPCD_RW_EXP_NOLASTEPI && !MPCD_RW_EXP_BAR2 && !MPCD_RW_EXP_NOVM;
+
 template <int D0, int SMODE, bool CTX>
-hipError_t launch_rw(const MlpSampleArgs &a, int rows, hipStream_t stream)
+hipError_t launch_rw(const MlpSampleArgs &a, int rows, int waves, hipStream_t stream)
 {
-    return rows == 16 ? launch_rw_r<D0, SMODE, CTX, 16>(a, stream) : launch_rw_r<D0, SMODE, CTX, 32>(a, stream);
+    if (waves == 8) {
+        if constexpr (RW8_BUILT) return rows == 32 ? launch_rw_r<D0, SMODE, CTX, 32, 8>(a, stream) : hipErrorInvalidValue;
+        else return hipErrorInvalidValue;
+    }
+    return rows == 16 ? launch_rw_r<D0, SMODE, CTX, 16, 4>(a, stream) : launch_rw_r<D0, SMODE, CTX, 32, 4>(a, stream);
 }
 
 template <int D0>
-hipError_t launch_rw_d0(const MlpSampleArgs &a, int rows, hipStream_t stream)
+hipError_t launch_rw_d0(const MlpSampleArgs &a, int rows, int waves, hipStream_t stream)
 {
     const bool ctx = a.cproj != nullptr;
     switch (a.mode) {
     case MODE_DDPM_CFG:
-        if (a.noise) return ctx ? launch_rw<D0, MODE_DDPM_XN, true>(a, rows, stream) : launch_rw<D0, MODE_DDPM_XN, false>(a, rows, stream);
-        return ctx ? launch_rw<D0, MODE_DDPM_CFG, true>(a, rows, stream) : launch_rw<D0, MODE_DDPM_CFG, false>(a, rows, stream);
-    case MODE_DDIM_CFG: return ctx ? launch_rw<D0, MODE_DDIM_CFG, true>(a, rows, stream) : launch_rw<D0, MODE_DDIM_CFG, false>(a, rows, stream);
-    case MODE_DDIM: return ctx ? launch_rw<D0, MODE_DDIM, true>(a, rows, stream) : launch_rw<D0, MODE_DDIM, false>(a, rows, stream);
-    case MODE_EPS: return ctx ? launch_rw<D0, MODE_EPS, true>(a, rows, stream) : launch_rw<D0, MODE_EPS, false>(a, rows, stream);
-    case MODE_EPS1: return ctx ? launch_rw<D0, MODE_EPS1, true>(a, rows, stream) : launch_rw<D0, MODE_EPS1, false>(a, rows, stream);
+        if (a.noise) return ctx ? launch_rw<D0, MODE_DDPM_XN, true>(a, rows, waves, stream) : launch_rw<D0, MODE_DDPM_XN, false>(a, rows, waves, stream);
+        return ctx ? launch_rw<D0, MODE_DDPM_CFG, true>(a, rows, waves, stream) : launch_rw<D0, MODE_DDPM_CFG, false>(a, rows, waves, stream);
+    case MODE_DDIM_CFG: return ctx ? launch_rw<D0, MODE_DDIM_CFG, true>(a, rows, waves, stream) : launch_rw<D0, MODE_DDIM_CFG, false>(a, rows, waves, stream);
+    case MODE_DDIM: return ctx ? launch_rw<D0, MODE_DDIM, true>(a, rows, waves, stream) : launch_rw<D0, MODE_DDIM, false>(a, rows, waves, stream);
+    case MODE_EPS: return ctx ? launch_rw<D0, MODE_EPS, true>(a, rows, waves, stream) : launch_rw<D0, MODE_EPS, false>(a, rows, waves, stream);
+    case MODE_EPS1: return ctx ? launch_rw<D0, MODE_EPS1, true>(a, rows, waves, stream) : launch_rw<D0, MODE_EPS1, false>(a, rows, waves, stream);
     }
     return hipErrorInvalidValue;
 }
 
 }  // namespace
 
-// rows: 32 or 16 per workgroup (mlp_x3.hip picks, as for its own layouts)
-hipError_t launch_mlp_rw(int d0, int rows, const MlpSampleArgs &a, hipStream_t stream)
+// rows: 32 or 16 per workgroup, waves: 4, or 8 at 32 rows (mlp_x3.hip picks, as for its own layouts)
+hipError_t launch_mlp_rw(int d0, int rows, int waves, const MlpSampleArgs &a, hipStream_t stream)
 {
     switch (d0) {
-    case 32: return launch_rw_d0<32>(a, rows, stream);
-    case 64: return launch_rw_d0<64>(a, rows, stream);
-    case 128: return launch_rw_d0<128>(a, rows, stream);
+    case 32: return launch_rw_d0<32>(a, rows, waves, stream);
+    case 64: return launch_rw_d0<64>(a, rows, waves, stream);
+    case 128: return launch_rw_d0<128>(a, rows, waves, stream);
     }
     return hipErrorInvalidValue;
 }

@@ -594,7 +594,8 @@ hipError_t launch_x3_r(const MlpSampleArgs &a, hipStream_t stream)
 // (fewer than one per CU), 16x4 = two independent 4-wave workgroups per CU, whose barriers and
 // latency chains interleave on each SIMD instead of coinciding. MPCD_MLP_LAYOUT=32x8|16x8|16x4 forces.
 // rw32 / rw16: mlp_rw.hip (4 waves, the 128-wide layers' weights resident in registers), 32 or 16 rows.
-enum { LAYOUT_32x8 = 0, LAYOUT_16x8 = 1, LAYOUT_16x4 = 2, LAYOUT_RW32 = 3, LAYOUT_RW16 = 4 };
+// rw32x8: mlp_rw.hip's 8-wave form (two waves per SIMD, 32 rows, Linear 5, 6 and half of 7 resident).
+enum { LAYOUT_32x8 = 0, LAYOUT_16x8 = 1, LAYOUT_16x4 = 2, LAYOUT_RW32 = 3, LAYOUT_RW16 = 4, LAYOUT_RW32X8 = 5 };
 std::atomic<int> g_force_layout{-1};  // mpcd_mlp_force_layout (tests: every layout against the oracle)
 int mlp_x3_layout(int64_t batch, int nb)
 {
@@ -603,14 +604,18 @@ int mlp_x3_layout(int64_t batch, int nb)
         const char *e = getenv("MPCD_MLP_LAYOUT");
         if (!e || !e[0]) return -1;
         return !strcmp(e, "32x8") ? (int)LAYOUT_32x8 : !strcmp(e, "16x8") ? (int)LAYOUT_16x8 : !strcmp(e, "16x4") ? (int)LAYOUT_16x4
-             : !strcmp(e, "rw32") ? (int)LAYOUT_RW32 : !strcmp(e, "rw16") ? (int)LAYOUT_RW16 : -1;
+             : !strcmp(e, "rw32") ? (int)LAYOUT_RW32 : !strcmp(e, "rw16") ? (int)LAYOUT_RW16
+             : !strcmp(e, "rw32x8") ? (int)LAYOUT_RW32X8 : -1;
     }();
     if (forced >= 0) return forced;
     // the resident-weight kernel (mlp_rw.hip) at every batch: 32-row workgroups (cfg2: 1.187 vs 1.252 ms kernel for
     // the streaming 32x8), 16-row ones below one 32-row workgroup per CU (the 512-candidate strong-scaling shard:
-    // 0.87 vs 1.04 ms per control step for 16x8; cfg1 0.41 vs 0.49 ms kernel) - profiles/r4_mlp_layouts.txt
+    // 0.87 vs 1.04 ms per control step for 16x8; cfg1 0.41 vs 0.49 ms kernel) - profiles/r4_mlp_layouts.txt.
+    // The 32-row form on 8 waves (rw32x8) since it beat rw32 beyond the run-to-run spread in alternating runs on
+    // one box: kernel 1.069 vs 1.084 ms at 4,096 candidates, 2.128 vs 2.164 at 8,192, 4.246 vs 4.313 at 16,384
+    // (profiles/rw8_ab.txt)
     const int n_cu = device_cu_count();
-    return (batch * nb + 31) / 32 < n_cu ? LAYOUT_RW16 : LAYOUT_RW32;
+    return (batch * nb + 31) / 32 < n_cu ? LAYOUT_RW16 : LAYOUT_RW32X8;
 }
 
 template <int D0, int SMODE, bool CTX>
@@ -714,7 +719,8 @@ hipError_t launch_mlp_x3(int d0, int nb, const MlpSampleArgs &a, hipStream_t str
     if ((nb == 1) != (a.mode == MODE_DDIM || a.mode == MODE_EPS1)) return hipErrorInvalidValue;
     if (a.cproj && a.cproj_stride != 0) return hipErrorInvalidValue;  // shared context only
     const int lay = mlp_x3_layout(a.batch, nb);  // decided once per call
-    if (lay == LAYOUT_RW32 || lay == LAYOUT_RW16) return launch_mlp_rw(d0, lay == LAYOUT_RW32 ? 32 : 16, a, stream);
+    if (lay == LAYOUT_RW32X8) return launch_mlp_rw(d0, 32, 8, a, stream);
+    if (lay == LAYOUT_RW32 || lay == LAYOUT_RW16) return launch_mlp_rw(d0, lay == LAYOUT_RW32 ? 32 : 16, 4, a, stream);
     switch (d0) {
     case 32: return launch_x3_d0<32>(a, lay, stream);
     case 64: return launch_x3_d0<64>(a, lay, stream);

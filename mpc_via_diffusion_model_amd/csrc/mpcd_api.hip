@@ -916,8 +916,8 @@ int mpcd_mlp_layout(int64_t batch, int32_t cfg_masked, int32_t *layout_out)
 
 int mpcd_mlp_force_layout(int32_t layout)
 {
-    if (layout < -1 || layout > 4)
-        return fail(MPCD_EINVAL, "layout -1 (auto), 0 (32x8), 1 (16x8), 2 (16x4), 3 (rw32) or 4 (rw16)");
+    if (layout < -1 || layout > 5)
+        return fail(MPCD_EINVAL, "layout -1 (auto), 0 (32x8), 1 (16x8), 2 (16x4), 3 (rw32), 4 (rw16) or 5 (rw32x8)");
     mlp_x3_force_layout(layout);
     return MPCD_OK;
 }

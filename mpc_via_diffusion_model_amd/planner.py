@@ -59,12 +59,13 @@ def force_unet_path(path="auto"):
     N.check(N.lib().mpcd_unet_force_path(UNET_PATHS[path]), "mpcd_unet_force_path")
 
 
-MLP_LAYOUTS = {"auto": -1, "32x8": 0, "16x8": 1, "16x4": 2, "rw32": 3, "rw16": 4}
+MLP_LAYOUTS = {"auto": -1, "32x8": 0, "16x8": 1, "16x4": 2, "rw32": 3, "rw16": 4, "rw32x8": 5}
 
 
 def force_mlp_layout(layout="auto"):
     """Process-wide MLP sampler workgroup layout (mpcd_mlp_force_layout): "auto" (by batch size), "32x8",
-    "16x8" or "16x4" (rows x waves per workgroup), "rw32" / "rw16" (4 waves, resident 128-wide weights)."""
+    "16x8" or "16x4" (rows x waves per workgroup), "rw32" / "rw16" (4 waves, resident 128-wide weights), "rw32x8"
+    (the resident-weight kernel on 8 waves, 32 rows)."""
     N.check(N.lib().mpcd_mlp_force_layout(MLP_LAYOUTS[layout]), "mpcd_mlp_force_layout")
 
 
@@ -359,7 +360,7 @@ class DiffusionMPC:
                 "waves_per_workgroup": int(out[3])}
 
     def mlp_layout(self, n_samples):
-        """The MLP sampler layout ("32x8", "16x8", "16x4", "rw32", "rw16") a sample call of n_samples runs."""
+        """The MLP sampler layout ("32x8", "16x8", "16x4", "rw32", "rw16", "rw32x8") a sample call of n_samples runs."""
         out = ctypes.c_int32()
         with torch.cuda.device(self.device):  # the library decides on the current device's CU count
             N.check(self._lib.mpcd_mlp_layout(int(n_samples), int(self.spec.cfg), ctypes.byref(out)), "mpcd_mlp_layout")
