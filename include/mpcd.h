@@ -54,8 +54,9 @@ enum mpcd_net_kind {
  *             "fp16 hidden with MFMA GEMM"); U-Net only (an MLP net returns MPCD_EUNSUP).
  * MPCD_F32X3: fp32-accurate split-bf16 MFMA (MLP and U-Net): each fp32 operand = three bf16 terms, the six
  *             partial products >= 2^-16 of the leading one accumulated in fp32 (error at the level of
- *             the fp32 MFMA's). MLP: needs a context shared by all candidates (or none); a
- *             per-candidate context runs the MPCD_F32 kernel.
+ *             the fp32 MFMA's). MLP: needs one context row per workgroup, i.e. a context shared by all
+ *             candidates, none, or one row per group of consecutive candidates (mpcd_sample_grouped); a
+ *             per-candidate context (mpcd_sample with context_shared = 0) runs the MPCD_F32 kernel.
  * MPCD_F16X2: two-term fp16 MFMA (MLP: csrc/mlp_h2.hip; U-Net: the fused P = 2 program) - NOT fp32 arithmetic:
  *             each operand = hi + lo (two fp16, the weights scaled per layer by an exact power of two, the
  *             activations unscaled), three products per 32-k chunk accumulated in fp32. 22 significant bits per
@@ -63,7 +64,7 @@ enum mpcd_net_kind {
  *             then re-runs the step in MPCD_F32X3, see mpcd_force_f32x3), activations below 2^-14 keep an
  *             absolute, not relative, precision of 2^-25. Used for the CFG-DDPM sampler and the eps forward (MLP at
  *             H*d = 32 / 64 with a shared context); every other case (unclamped DDIM, whose unbounded x leaves
- *             the fp16 range; per-candidate contexts; H*d = 128) runs the MPCD_F32X3 kernels of the same net. */
+ *             the fp16 range; per-candidate and grouped contexts; H*d = 128) runs the MPCD_F32X3 kernels of the same net. */
 enum mpcd_dtype { MPCD_F32 = 0, MPCD_F16 = 1, MPCD_F32X3 = 2, MPCD_F16X2 = 3 };
 
 typedef struct {
@@ -142,6 +143,16 @@ int mpcd_philox_noise(uint64_t seed, int64_t global_offset, int64_t n_cand, int3
 /* Number of denoise steps S a call makes (DDPM: N + n_wo_noise; DDIM: grid pairs). */
 int mpcd_sample_steps(mpcd_ctx *ctx, const mpcd_sample_args *args, int32_t *n_steps);
 int mpcd_sample(mpcd_ctx *ctx, const mpcd_sample_args *args, void *hip_stream);
+/* mpcd_sample with one context row per GROUP of `group` consecutive candidates: args->context is dev
+ * [batch / group][C] (context_shared is ignored), batch % group == 0, group >= 1. Candidate b uses row b / group.
+ * Everything else (Philox keyed by global_offset + b, noise / chain / chain_absmax layouts) is mpcd_sample's.
+ * This is a closed-loop batch (M plant states x n candidates each) without M x n context rows: an MPCD_F32X3 MLP
+ * runs its split-bf16 kernels with the workgroups aligned to the groups, and group m's results are bit for bit
+ * those of a shared-context mpcd_sample of `group` candidates with row m and global_offset + m * group. An MPCD_F32
+ * MLP indexes its per-candidate table by b / group; an MPCD_F16X2 MLP runs its MPCD_F32X3 programs; a U-Net gets the
+ * rows' projections replicated per candidate. MPCD_EINVAL: group < 1, batch % group != 0, no context pointer, a
+ * net with context_dim == 0. */
+int mpcd_sample_grouped(mpcd_ctx *ctx, const mpcd_sample_args *args, int64_t group, void *hip_stream);
 
 /* One noise-net forward at diffusion time t (the model(x, t, context, mask) calls of
  * p_mean_variance_CFG, diffusion_model_base.py:166-168): x dev [B][H][d]; eps_cond dev [B][H][d] =
@@ -368,6 +379,11 @@ int mpcd_mlp_layout(int64_t batch, int32_t cfg_masked, int32_t *layout_out);
  * mlp_rw_kernel), 2 two-term fp16 (mlp_h2_kernel); out[1] = the bf16x3 layout (as mpcd_mlp_layout) or -1;
  * out[2] = rows per workgroup (32 or 16). MPCD_EUNSUP on a U-Net context. */
 int mpcd_mlp_form(mpcd_ctx *ctx, int32_t sampler, int64_t batch, int32_t out[3]);
+/* The same for an mpcd_sample_grouped call of n_groups x group candidates: out[0] is 0 or 1 (never 2: the fp16
+ * kernel takes no grouped call); the layout is chosen for the workgroups such a call launches,
+ * n_groups * ceil(group / candidates per workgroup), with 16 rows where a group fills at most half of a 32-row
+ * workgroup. mpcd_mlp_force_layout wins here too. */
+int mpcd_mlp_form_grouped(mpcd_ctx *ctx, int32_t sampler, int64_t n_groups, int64_t group, int32_t out[3]);
 /* on != 0: an MPCD_F16X2 net runs its split-bf16 (MPCD_F32X3) programs for every call on this context until turned
  * off again (mpcd_mpc_step does this by itself for one re-run when an MPCD_F16X2 step's samples come back with a NaN
  * or without a finite cost: the fp16 range was left; MPCD_STEP_F32X3_RERUN flags it). */

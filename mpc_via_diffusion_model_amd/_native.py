@@ -75,6 +75,7 @@ EXPORTS = {
     "mpcd_set_schedule": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p], ctypes.c_int),
     "mpcd_sample_steps": ([ctypes.c_void_p, ctypes.POINTER(SampleArgs), ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
     "mpcd_sample": ([ctypes.c_void_p, ctypes.POINTER(SampleArgs), ctypes.c_void_p], ctypes.c_int),
+    "mpcd_sample_grouped": ([ctypes.c_void_p, ctypes.POINTER(SampleArgs), ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
     "mpcd_eps": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "mpcd_clip_flag": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p],
@@ -109,6 +110,8 @@ EXPORTS = {
     "mpcd_force_f32x3": ([ctypes.c_void_p, ctypes.c_int32], ctypes.c_int),
     "mpcd_mlp_layout": ([ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
     "mpcd_mlp_form": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "mpcd_mlp_form_grouped": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
+                               ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
     "mpcd_unet_force_path": ([ctypes.c_int32], ctypes.c_int),
     "mpcd_unet_form": ([ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
     "mpcd_comm_init_loopback": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64], ctypes.c_int),

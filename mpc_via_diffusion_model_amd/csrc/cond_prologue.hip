@@ -85,7 +85,25 @@ __global__ __launch_bounds__(256) void ctx_prologue_row_kernel(const CtxRowArg r
     cproj[col] = ctx_proj_col(row, ctx_dim, layers, n_layers, cond_dim, col);
 }
 
+// Grouped contexts for the U-Net (mpcd_sample_grouped): one projection row per group of `group` consecutive
+// candidates spread to the per-candidate table its kernels read, dst[b] = src[b / group]
+__global__ __launch_bounds__(256) void ctx_replicate_kernel(const float *src, int64_t batch, int64_t group, int cond_total,
+                                                            float *dst)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= batch * cond_total) return;
+    const int64_t b = i / cond_total;
+    dst[i] = src[(b / group) * cond_total + (i - b * cond_total)];
+}
+
 }  // namespace
+
+void launch_ctx_replicate(const float *src, int64_t batch, int64_t group, int cond_total, float *dst, hipStream_t stream)
+{
+    const int64_t n = batch * cond_total;
+    hipLaunchKernelGGL(ctx_replicate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, src, batch, group,
+                       cond_total, dst);
+}
 
 void launch_ctx_prologue_row(const CtxRowArg &row, int ctx_dim, const CondLayer *layers_dev, int n_layers,
                              int cond_dim, int cond_total, float *cproj, hipStream_t stream)

@@ -26,6 +26,9 @@ void launch_time_prologue(const StepPlan *plan, int n_steps, const float *time_w
 // Context prologue: cproj[b][off_j + n] = cond_mlp_j.W[n, T:] . Mish(ctx_b)   (no bias)
 void launch_ctx_prologue(const float *ctx, int64_t n_rows, int ctx_dim, const CondLayer *layers_dev, int n_layers,
                          int cond_dim, int cond_total, float *cproj, hipStream_t stream);
+// dst[b][:] = src[b / group][:] for b < batch (rows of cond_total floats): a grouped call's projections as the
+// per-candidate table of the U-Net kernels
+void launch_ctx_replicate(const float *src, int64_t batch, int64_t group, int cond_total, float *dst, hipStream_t stream);
 // one shared context row passed by value (mpcd_mpc_step: no host-to-device copy before the sampler)
 constexpr int kCtxRowMax = 64;
 struct CtxRowArg {
@@ -92,8 +95,8 @@ struct MlpSampleArgs {
     const float *wpack;      // packed linear layers (see mlp_sampler.hip)
     const StepPlan *plan;    // [S]
     const float *tproj;      // [S][448]
-    const float *cproj;      // [B or 1][448] or null (no context / NB == 1 unconditioned)
-    int64_t cproj_stride;    // 448 or 0 (shared context)
+    const float *cproj;      // [B or 1][448], [B / group][448] if grouped, or null (no context / NB == 1 unconditioned)
+    int64_t cproj_stride;    // 448 or 0 (shared context); 448 for a grouped call
     const float *noise;      // [S+1][B][D0] or null
     float *x_out;            // [B][D0]
     float *chain;            // [S+1][B][D0] or null
@@ -112,15 +115,21 @@ struct MlpSampleArgs {
     int32_t ctx_dim, n_cond, cond_dim;
     const CondLayer *cond_layers;
     CtxRowArg ctx_row;
+    // mpcd_sample_grouped: candidate b uses context row b / group (cproj [batch / group][448]); 0 = not grouped
+    // (cproj_stride says shared or per candidate). group_wgs = ceil(group / candidates per workgroup): set by the
+    // split-bf16 launchers for their own layout (their workgroups never straddle a group), 0 elsewhere
+    int64_t group;
+    int32_t group_wgs;
 };
 
 int mlp_packed_floats(int d0);
 void mlp_pack_weights(int d0, const float *const *lin_w, const float *const *lin_b, float *out);
 hipError_t launch_mlp_sampler(int d0, int nb, const MlpSampleArgs &a, hipStream_t stream);
-// fp32-accurate split-bf16 variant (mlp_x3.hip); shared or no context only
+// fp32-accurate split-bf16 variant (mlp_x3.hip); shared, grouped (MlpSampleArgs::group) or no context
 int mlp_packed_floats_x3(int d0);
 void mlp_x3_force_layout(int layout);  // mpcd_mlp_force_layout
 int mlp_x3_layout_of(int64_t batch, int nb);  // mpcd_mlp_layout: the layout a call of this batch runs
+int mlp_x3_layout_grouped(int64_t n_groups, int64_t group, int nb);  // ... and a grouped call of n_groups x group
 void mlp_pack_weights_x3(int d0, const float *const *lin_w, const float *const *lin_b, float *out);
 hipError_t launch_mlp_x3(int d0, int nb, const MlpSampleArgs &a, hipStream_t stream);
 // resident-weight variant (mlp_rw.hip), selected by mlp_x3's layout choice: rows = 32 or 16 per workgroup

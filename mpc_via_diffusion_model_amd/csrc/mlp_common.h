@@ -64,6 +64,57 @@ MPCD_DEV StepPlan load_plan(const StepPlan *plan, int s)
     return r;
 }
 
+// The candidates [cand0, cand0 + n) and the context projection row of one split-bf16 workgroup (CPW candidates per
+// workgroup, n <= CPW). A plain call (GRP = false): workgroup i starts at i CPW, ends with the batch and reads row 0;
+// that is the code these kernels had before grouped calls existed, n is unused and the bound is candidate < batch.
+// A grouped call (GRP = true, mpcd_sample_grouped; group_wgs = ceil(group / CPW) from the launcher): workgroup j of
+// group m starts at m group + j CPW, ends with the group and reads row m, so that a workgroup holds candidates of one
+// context row only; its columns past n are the idle rows that columns past the batch are in a plain call (zero
+// input, no global write). Everything here is wave-uniform (scalar registers). GRP is a template flag and not a
+// run-time branch because the 8-wave resident-weight kernels have no register to spare: a run-time form of this put
+// three of their H*d = 128 instantiations into scratch (profiles/grouped_kernel_resources.txt).
+struct CandSpan {
+    int64_t cand0;
+    int32_t n;
+    const float *cproj;
+};
+template <int CPW, bool GRP>
+MPCD_DEV CandSpan cand_span(const float *cproj, int64_t group, int32_t group_wgs)
+{
+    if constexpr (!GRP) {
+        return CandSpan{(int64_t)blockIdx.x * CPW, 0, cproj};
+    } else {
+        const uint32_t m = __builtin_amdgcn_readfirstlane(blockIdx.x / (uint32_t)group_wgs);
+        const uint32_t j = blockIdx.x - m * (uint32_t)group_wgs;
+        const int64_t left = group - (int64_t)j * CPW;  // >= 1: j < ceil(group / CPW)
+        return CandSpan{(int64_t)m * group + (int64_t)j * CPW, left < CPW ? (int32_t)left : CPW,
+                        cproj + (size_t)m * COND_TOTAL};
+    }
+}
+// column / local candidate c of the workgroup holds a candidate of the call
+template <bool GRP>
+MPCD_DEV bool in_span(int64_t batch, int64_t cand0, int n, int c)
+{
+    if constexpr (GRP) return c < n;
+    else return cand0 + c < batch;
+}
+
+// Host side of cand_span: the grid of a call and, for a grouped one (group > 0), the workgroups per group. false: a
+// batch that is no whole number of groups, or a grid past the launch limit.
+inline bool cand_grid(int cpw, int64_t batch, int64_t group, int64_t *blocks, int32_t *group_wgs)
+{
+    *group_wgs = 0;
+    *blocks = (batch + cpw - 1) / cpw;
+    if (group > 0) {
+        if (batch % group != 0) return false;
+        const int64_t wgs = (group + cpw - 1) / cpw;
+        if (wgs > INT32_MAX) return false;
+        *group_wgs = (int32_t)wgs;
+        *blocks = batch / group * wgs;
+    }
+    return *blocks <= INT32_MAX;
+}
+
 // |v| as an ordered integer: max over these bits is max |v| and propagates a NaN (its magnitude bits
 // exceed +inf's), which is what the chain clip test needs (mpcd_sample_args.chain_absmax).
 MPCD_DEV uint32_t abs_bits(float v) { return __builtin_bit_cast(uint32_t, v) & 0x7fffffffu; }

@@ -186,8 +186,10 @@ MPCD_DEV f32x4 mfma_agpr1(const u32x4 &w, const u32x4 &x, f32x4 acc)
 
 // W = 4: one wave per SIMD (rw32 / rw16). W = 8: two per SIMD, 32 rows (rw32x8), the same sums in the same
 // order; only which wave computes a pass, and when, differs.
-template <int D0, int SMODE, bool CTX, int R, int W = RW_W>
+// GRP: the grouped-context form (mlp_rw_grouped_kernel; see cand_span), a CTX instantiation of its own.
+template <int D0, int SMODE, bool CTX, int R, int W = RW_W, bool GRP = false>
 struct MlpRw {
+    static_assert(CTX || !GRP, "grouped contexts need a context");
     static constexpr int NB = (SMODE == MODE_DDIM || SMODE == MODE_EPS1) ? 1 : 2;
     static constexpr bool IS_DDPM = SMODE == MODE_DDPM_CFG || SMODE == MODE_DDPM_XN;
     static_assert(R == 32 || R == 16, "32 or 16 rows per workgroup");
@@ -726,8 +728,8 @@ struct MlpRw {
     }
 
     static MPCD_DEV void final_and_update(const FW &f, char *lds, const MlpSampleArgs &p, const StepPlan &sp, int s,
-                                          int64_t cand0, const f32x4 (&nz)[NZT][NB], uint32_t (&am)[2],
-                                          f32x4 (&xr)[NZT][XG], int wave, int lane MPCD_FINAL_PROF)
+                                          int64_t cand0, int n_cand, const f32x4 (&nz)[NZT][NB],
+                                          uint32_t (&am)[2], f32x4 (&xr)[NZT][XG], int wave, int lane MPCD_FINAL_PROF)
     {
 #ifdef MPCD_PROF_LAYERS
         uint64_t tmark = __builtin_readcyclecounter();
@@ -805,7 +807,7 @@ struct MlpRw {
                 const f32x4 eu = acc[j][1];
                 const int64_t gc = cand0 + cl;
                 if (SMODE == MODE_EPS || SMODE == MODE_EPS1) {
-                    if (gc < p.batch) {
+                    if (in_span<GRP>(p.batch, cand0, n_cand, cl)) {
                         *reinterpret_cast<f32x4 *>(p.x_out + (size_t)gc * D0 + n) = ec;
                         if (SMODE == MODE_EPS) *reinterpret_cast<f32x4 *>(p.chain + (size_t)gc * D0 + n) = eu;
                     }
@@ -860,7 +862,7 @@ struct MlpRw {
                 }
                 store_x<!XREG>(lds, cl, n, xn);
                 if (XREG) xr[j][g] = xn;
-                if (gc < p.batch) {
+                if (in_span<GRP>(p.batch, cand0, n_cand, cl)) {
                     if (p.chain) *reinterpret_cast<f32x4 *>(p.chain + ((size_t)(s + 1) * p.batch + gc) * D0 + n) = xn;
                     if (last) *reinterpret_cast<f32x4 *>(p.x_out + (size_t)gc * D0 + n) = xn;
                 }
@@ -871,7 +873,7 @@ struct MlpRw {
 
     // noise of step s (slice s+1) for this lane's quads, fetched one step ahead of use
     static MPCD_DEV void fetch_noise(f32x4 (&nz)[NZT][NB], const MlpSampleArgs &p, const StepPlan &sp, int s,
-                                     int64_t cand0, int wave, int lane)
+                                     int64_t cand0, int n_cand, int wave, int lane)
     {
         constexpr int NT = D0 / 16;
 #pragma unroll
@@ -886,7 +888,7 @@ struct MlpRw {
             if (NT % 4 != 0 && nt >= NT) continue;
             const int n = nt * 16 + 4 * q;
             const int64_t gc = cand0 + col;  // DDPM-CFG: NB == 2, one candidate per column (R = 16: columns < 8)
-            if (gc >= p.batch || (R == 16 && col >= 8)) continue;
+            if (!in_span<GRP>(p.batch, cand0, n_cand, col) || (R == 16 && col >= 8)) continue;
             if (SMODE == MODE_DDPM_XN)
                 nz[j][0] = *reinterpret_cast<const f32x4 *>(p.noise + ((size_t)(s + 1) * p.batch + gc) * D0 + n);
             else
@@ -961,12 +963,12 @@ struct MlpRw {
     }
     // fetch_noise's result from the staged draw: zeros where fetch_noise draws none
     static MPCD_DEV void ph_take(f32x4 (&nz)[NZT][NB], const PhSt &st, const StepPlan &sp, int64_t cand0,
-                                 const MlpSampleArgs &p, int wave, int lane)
+                                 int n_cand, const MlpSampleArgs &p, int wave, int lane)
     {
         const int col = lane & 15;
 #pragma unroll
         for (int g = 0; g < NB; ++g) nz[0][g] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const bool ok = (sp.flags & PLAN_NOISE) && (D0 / 16 % 4 == 0 || wave < D0 / 16) && cand0 + col < p.batch &&
+        const bool ok = (sp.flags & PLAN_NOISE) && (D0 / 16 % 4 == 0 || wave < D0 / 16) && in_span<GRP>(p.batch, cand0, n_cand, col) &&
                         !(R == 16 && col >= 8);
         if (ok) nz[0][0] = f32x4{st.z[0], st.z[1], st.z[2], st.z[3]};
     }
@@ -977,7 +979,9 @@ struct MlpRw {
         char *lds = reinterpret_cast<char *>(lds_f);
         const int lane = threadIdx.x & 63;
         const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        const int64_t cand0 = (int64_t)blockIdx.x * CPW;
+        const CandSpan span = cand_span<CPW, GRP>(p.cproj, p.group, p.group_wgs);
+        const int64_t cand0 = span.cand0;
+        const int n_cand = span.n;  // grouped: columns c < n_cand hold candidate cand0 + c, the others idle
         int lane16 = lane * 16;
         const float *wp = p.wpack;
         float *bi = reinterpret_cast<float *>(lds + L::BI);
@@ -1001,14 +1005,14 @@ struct MlpRw {
         for (int i = threadIdx.x; i < COND_TOTAL; i += NTH)
             cps[i] = !CTX ? 0.f
                           : p.ctx_fused ? ctx_proj_col(p.ctx_row, p.ctx_dim, p.cond_layers, p.n_cond, p.cond_dim, i)
-                                        : p.cproj[i];
+                                        : span.cproj[i];
         if (threadIdx.x < CPW) reinterpret_cast<uint32_t *>(lds + L::AMX)[threadIdx.x] = 0u;
         uint32_t am[2] = {0u, 0u};
         for (int i = threadIdx.x; i < CPW * QUADS; i += NTH) {  // x_T (fp32 + planes)
             const int c = i / QUADS, qd = i - c * QUADS;
             const int64_t gc = cand0 + c;
             f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (gc < p.batch) {
+            if (in_span<GRP>(p.batch, cand0, n_cand, c)) {
                 z = p.noise ? *reinterpret_cast<const f32x4 *>(p.noise + (size_t)gc * D0 + qd * 4)
                             : philox_normal4(p.seed, (uint64_t)(p.global_offset + gc), 0u, (uint32_t)qd);
                 if (p.chain && SMODE != MODE_EPS) *reinterpret_cast<f32x4 *>(p.chain + (size_t)gc * D0 + qd * 4) = z;
@@ -1026,7 +1030,7 @@ struct MlpRw {
         load_ws<0>(w0, wp, wave, lane16);
         f32x4 nz[NZT][NB];
         StepPlan sp = load_plan(p.plan, 0);
-        if constexpr (W == 4) fetch_noise(nz, p, sp, 0, cand0, wave, lane);
+        if constexpr (W == 4) fetch_noise(nz, p, sp, 0, cand0, n_cand, wave, lane);
         const int tpi = threadIdx.x < COND_TOTAL / 4 ? (int)threadIdx.x : threadIdx.x < COND_TOTAL / 2 ? (int)threadIdx.x - COND_TOTAL / 4 : 0;
         f32x4 tpre = reinterpret_cast<const f32x4 *>(p.tproj)[tpi];
 #ifdef MPCD_PROF_LAYERS
@@ -1118,12 +1122,12 @@ struct MlpRw {
 #pragma unroll
                     for (int g = 0; g < NB; ++g) nzc[j][g] = nz[j][g];
                 if (STAGED_NOISE && s + 1 < p.n_steps) {
-                    ph_take(nz, ph, sp, cand0, p, wave, lane);
+                    ph_take(nz, ph, sp, cand0, n_cand, p, wave, lane);
                 } else if (s + 1 < p.n_steps) {
 #ifdef MPCD_PROF_LAYERS
                     const uint64_t tn0 = __builtin_readcyclecounter();
 #endif
-                    fetch_noise(nz, p, sp, s + 1, cand0, wave, lane);
+                    fetch_noise(nz, p, sp, s + 1, cand0, n_cand, wave, lane);
 #ifdef MPCD_PROF_LAYERS
                     asm volatile("" ::: "memory");
                     tacc[31] += __builtin_readcyclecounter() - tn0;  // "tail" row, wait column: the noise draws
@@ -1200,7 +1204,7 @@ struct MlpRw {
                 if constexpr (IS_DDPM)
                     if (wave >= 4) {
                         f32x4 nzh[NZT][NB];
-                        fetch_noise(nzh, p, cur, s, cand0, wave - 4, lane);
+                        fetch_noise(nzh, p, cur, s, cand0, n_cand, wave - 4, lane);
 #pragma unroll
                         for (int j = 0; j < NZT; ++j)
                             *reinterpret_cast<f32x4 *>(lds + L::C0 + ((j * 4 + wave - 4) * 64 + lane) * 16) = nzh[j][0];
@@ -1252,9 +1256,9 @@ struct MlpRw {
                 }
             }
 #ifdef MPCD_PROF_LAYERS
-            final_and_update(w13, lds, p, cur, s, cand0, nzc, am, xr, wave, lane, tacc);  // "-" row: MFMAs / update
+            final_and_update(w13, lds, p, cur, s, cand0, n_cand, nzc, am, xr, wave, lane, tacc);  // "-" row: MFMAs / update
 #else
-            final_and_update(w13, lds, p, cur, s, cand0, nzc, am, xr, wave, lane);
+            final_and_update(w13, lds, p, cur, s, cand0, n_cand, nzc, am, xr, wave, lane);
 #endif
             if constexpr (W == 8 && W0_LATE) load_ws<0>(w0, ws, wave, lane16);  // H*d = 128: after the update's registers
         }
@@ -1278,7 +1282,7 @@ struct MlpRw {
             const int col = lane & 15;
             store_chain_absmax<CPW, NTH>(reinterpret_cast<uint32_t *>(lds + L::AMX), am, col,
                                           (NB == 2 || R == 16) ? -1 : 16 + col, NB == 1 || R == 32 || col < 8,
-                                          p.chain_absmax, cand0, p.batch);
+                                          p.chain_absmax, cand0, GRP ? cand0 + n_cand : p.batch);
         }
     }
 };
@@ -1289,34 +1293,62 @@ __global__ __launch_bounds__(64 * W, 1) void mlp_rw_kernel(const MlpSampleArgs p
     MlpRw<D0, SMODE, CTX, R, W>::run(p);
 }
 
-template <int D0, int SMODE, bool CTX, int R, int W>
+// the grouped-context form (mpcd_sample_grouped): the same program with its workgroups aligned to the groups
+template <int D0, int SMODE, int R, int W>
+__global__ __launch_bounds__(64 * W, 1) void mlp_rw_grouped_kernel(const MlpSampleArgs p)
+{
+    MlpRw<D0, SMODE, true, R, W, true>::run(p);
+}
+
+template <int D0, int SMODE, bool CTX, int R, int W, bool GRP = false>
 hipError_t launch_rw_r(const MlpSampleArgs &a, hipStream_t stream)
 {
     using L = Lds3<D0, MlpRw<D0, SMODE, CTX, R, W>::NB, R>;
     static_assert(L::total <= 160 * 1024, "LDS budget (160 KiB per CU)");
-    if (hipError_t e = allow_max_lds<&mlp_rw_kernel<D0, SMODE, CTX, R, W>>(); e != hipSuccess) return e;
-    const int64_t blocks = (a.batch + L::CPW - 1) / L::CPW;
-    return launch_sampler_kernel(mlp_rw_kernel<D0, SMODE, CTX, R, W>, dim3((unsigned)blocks), dim3(64 * W), (size_t)L::total, stream, a);
+    int64_t blocks;
+    int32_t group_wgs;
+    if (!cand_grid(L::CPW, a.batch, GRP ? a.group : 0, &blocks, &group_wgs)) return hipErrorInvalidValue;
+    if constexpr (GRP) {
+        static_assert(CTX, "grouped contexts need a context");
+        if (hipError_t e = allow_max_lds<&mlp_rw_grouped_kernel<D0, SMODE, R, W>>(); e != hipSuccess) return e;
+        MlpSampleArgs g = a;  // the workgroups of this layout per group
+        g.group_wgs = group_wgs;
+        return launch_sampler_kernel(mlp_rw_grouped_kernel<D0, SMODE, R, W>, dim3((unsigned)blocks), dim3(64 * W), (size_t)L::total, stream, g);
+    } else {
+        if (hipError_t e = allow_max_lds<&mlp_rw_kernel<D0, SMODE, CTX, R, W>>(); e != hipSuccess) return e;
+        return launch_sampler_kernel(mlp_rw_kernel<D0, SMODE, CTX, R, W>, dim3((unsigned)blocks), dim3(64 * W), (size_t)L::total, stream, a);
+    }
 }
 
 // the 8-wave form exists for the default arms of the MPCD_RW_* switches (an experiment build of another arm has none)
 constexpr bool RW8_BUILT = MPCD_RW_ILV && MPCD_RW_EPI_STEPS && MPCD_RW_PKTAIL && MPCD_RW_XREG && MPCD_RW_TABLE_EARLY &&
                            MPCD_RW_TABLE_SIDE && !MPCD_RW_EXP_NOLASTEPI && !MPCD_RW_EXP_BAR2 && !MPCD_RW_EXP_NOVM;
 
-template <int D0, int SMODE, bool CTX>
+template <int D0, int SMODE, bool CTX, bool GRP = false>
 hipError_t launch_rw(const MlpSampleArgs &a, int rows, int waves, hipStream_t stream)
 {
     if (waves == 8) {
-        if constexpr (RW8_BUILT) return rows == 32 ? launch_rw_r<D0, SMODE, CTX, 32, 8>(a, stream) : hipErrorInvalidValue;
+        if constexpr (RW8_BUILT) return rows == 32 ? launch_rw_r<D0, SMODE, CTX, 32, 8, GRP>(a, stream) : hipErrorInvalidValue;
         else return hipErrorInvalidValue;
     }
-    return rows == 16 ? launch_rw_r<D0, SMODE, CTX, 16, 4>(a, stream) : launch_rw_r<D0, SMODE, CTX, 32, 4>(a, stream);
+    return rows == 16 ? launch_rw_r<D0, SMODE, CTX, 16, 4, GRP>(a, stream) : launch_rw_r<D0, SMODE, CTX, 32, 4, GRP>(a, stream);
 }
 
 template <int D0>
 hipError_t launch_rw_d0(const MlpSampleArgs &a, int rows, int waves, hipStream_t stream)
 {
     const bool ctx = a.cproj != nullptr;
+    if (a.group > 0) {  // grouped contexts: the samplers (mpcd_sample_grouped), with a context
+        if (!ctx) return hipErrorInvalidValue;
+        switch (a.mode) {
+        case MODE_DDPM_CFG:
+            return a.noise ? launch_rw<D0, MODE_DDPM_XN, true, true>(a, rows, waves, stream)
+                           : launch_rw<D0, MODE_DDPM_CFG, true, true>(a, rows, waves, stream);
+        case MODE_DDIM_CFG: return launch_rw<D0, MODE_DDIM_CFG, true, true>(a, rows, waves, stream);
+        case MODE_DDIM: return launch_rw<D0, MODE_DDIM, true, true>(a, rows, waves, stream);
+        }
+        return hipErrorInvalidValue;
+    }
     switch (a.mode) {
     case MODE_DDPM_CFG:
         if (a.noise) return ctx ? launch_rw<D0, MODE_DDPM_XN, true>(a, rows, waves, stream) : launch_rw<D0, MODE_DDPM_XN, false>(a, rows, waves, stream);

@@ -363,7 +363,9 @@ struct MlpKernel {
             for (int i = threadIdx.x; i < CPW * COND_TOTAL; i += THREADS) {
                 const int c = i / COND_TOTAL, k = i - c * COND_TOTAL;
                 const int64_t gc = cand0 + c;
-                lds[L::CP + c * CP_STRIDE + k] = gc < p.batch ? p.cproj[(size_t)(p.cproj_stride ? gc : 0) * COND_TOTAL + k] : 0.f;
+                // grouped (mpcd_sample_grouped): candidate gc's row is gc / group (once per launch, off the step loop)
+                const int64_t row = p.group > 0 ? gc / p.group : p.cproj_stride ? gc : 0;
+                lds[L::CP + c * CP_STRIDE + k] = gc < p.batch ? p.cproj[(size_t)row * COND_TOTAL + k] : 0.f;
             }
         }
         if (threadIdx.x < CPW) reinterpret_cast<uint32_t *>(lds + L::AMX)[threadIdx.x] = 0u;

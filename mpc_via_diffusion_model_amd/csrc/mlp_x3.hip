@@ -19,7 +19,9 @@
 // Net and conditioning as in mlp_sampler.hip. This variant takes a context shared by all candidates
 // (mpc_step's case: one measured state per control step) or none; the time part, the Linear bias
 // and the shared context part of every cond_mlp are pre-summed into the accumulator init per step
-// (TPC: context rows, TPU: masked rows). Per-candidate contexts use the exact-f32 kernel.
+// (TPC: context rows, TPU: masked rows). A grouped call (mpcd_sample_grouped: one context row per group of
+// consecutive candidates) aligns the workgroups to the groups, so each still stages one row (cand_span).
+// Per-candidate contexts use the exact-f32 kernel.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -31,8 +33,10 @@
 namespace {
 using namespace mlpx3;
 
-template <int D0, int SMODE, bool CTX, int R, int W = WAVES>
+// GRP: the grouped-context form (mlp_x3_grouped_kernel; see cand_span), a CTX instantiation of its own
+template <int D0, int SMODE, bool CTX, int R, int W = WAVES, bool GRP = false>
 struct MlpX3 {
+    static_assert(CTX || !GRP, "grouped contexts need a context");
     static constexpr int NTHR = 64 * W;  // threads per workgroup
     static constexpr int NB = (SMODE == MODE_DDIM || SMODE == MODE_EPS1) ? 1 : 2;
     static constexpr bool IS_DDPM = SMODE == MODE_DDPM_CFG || SMODE == MODE_DDPM_XN;
@@ -276,8 +280,8 @@ struct MlpX3 {
 
     // final Linear (32 -> D0) + the denoise update (reference op order, see mlp_sampler.hip)
     static MPCD_DEV void final_and_update(const FW &f, char *lds, const MlpSampleArgs &p, const StepPlan &sp, int s,
-                                          int64_t cand0, const f32x4 (&nz)[NZT][NB], uint32_t (&am)[2], int wave,
-                                          int lane)
+                                          int64_t cand0, int n_cand, const f32x4 (&nz)[NZT][NB],
+                                          uint32_t (&am)[2], int wave, int lane)
     {
         constexpr int T = FW::T, NT = D0 / 16;
         const int col = lane & 15, q = lane >> 4;
@@ -327,7 +331,7 @@ struct MlpX3 {
                 const f32x4 eu = acc[j][1];
                 const int64_t gc = cand0 + cl;
                 if (SMODE == MODE_EPS || SMODE == MODE_EPS1) {
-                    if (gc < p.batch) {
+                    if (in_span<GRP>(p.batch, cand0, n_cand, cl)) {
                         *reinterpret_cast<f32x4 *>(p.x_out + (size_t)gc * D0 + n) = ec;
                         if (SMODE == MODE_EPS) *reinterpret_cast<f32x4 *>(p.chain + (size_t)gc * D0 + n) = eu;
                     }
@@ -361,7 +365,7 @@ struct MlpX3 {
                     am[g] = max(am[g], max(abs_bits(xv), abs_bits(o)));
                 }
                 store_x(lds, cl, n, xn);
-                if (gc < p.batch) {
+                if (in_span<GRP>(p.batch, cand0, n_cand, cl)) {
                     if (p.chain) *reinterpret_cast<f32x4 *>(p.chain + ((size_t)(s + 1) * p.batch + gc) * D0 + n) = xn;
                     if (last) *reinterpret_cast<f32x4 *>(p.x_out + (size_t)gc * D0 + n) = xn;
                 }
@@ -371,7 +375,7 @@ struct MlpX3 {
 
     // noise of step s (slice s+1) for this lane's quads, fetched one step ahead of use
     static MPCD_DEV void fetch_noise(f32x4 (&nz)[NZT][NB], const MlpSampleArgs &p, const StepPlan &sp, int s,
-                                     int64_t cand0, int wave, int lane)
+                                     int64_t cand0, int n_cand, int wave, int lane)
     {
         constexpr int NT = D0 / 16;
 #pragma unroll
@@ -386,7 +390,7 @@ struct MlpX3 {
             if (NT % 4 != 0 && nt >= NT) continue;
             const int n = nt * 16 + 4 * q;
             const int64_t gc = cand0 + col;  // DDPM-CFG: NB == 2, one candidate per column (R = 16: columns < 8)
-            if (gc >= p.batch || (R == 16 && col >= 8)) continue;
+            if (!in_span<GRP>(p.batch, cand0, n_cand, col) || (R == 16 && col >= 8)) continue;
             if (SMODE == MODE_DDPM_XN)
                 nz[j][0] = *reinterpret_cast<const f32x4 *>(p.noise + ((size_t)(s + 1) * p.batch + gc) * D0 + n);
             else
@@ -400,7 +404,9 @@ struct MlpX3 {
         char *lds = reinterpret_cast<char *>(lds_f);
         const int lane = threadIdx.x & 63;
         const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        const int64_t cand0 = (int64_t)blockIdx.x * CPW;
+        const CandSpan span = cand_span<CPW, GRP>(p.cproj, p.group, p.group_wgs);
+        const int64_t cand0 = span.cand0;
+        const int n_cand = span.n;  // grouped: columns c < n_cand hold candidate cand0 + c, the others idle
         int lane16 = lane * 16;
         const float *wp = p.wpack;
         int wofs = 0;
@@ -417,7 +423,7 @@ struct MlpX3 {
         for (int i = threadIdx.x; i < COND_TOTAL; i += NTHR)  // ctx_fused: as mlp_rw.hip
             cps[i] = !CTX ? 0.f
                           : p.ctx_fused ? ctx_proj_col(p.ctx_row, p.ctx_dim, p.cond_layers, p.n_cond, p.cond_dim, i)
-                                        : p.cproj[i];
+                                        : span.cproj[i];
         if (threadIdx.x < CPW) reinterpret_cast<uint32_t *>(lds + L::AMX)[threadIdx.x] = 0u;
         uint32_t am[2] = {0u, 0u};
         // x_T (fp32 + planes)
@@ -425,7 +431,7 @@ struct MlpX3 {
             const int c = i / QUADS, qd = i - c * QUADS;
             const int64_t gc = cand0 + c;
             f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (gc < p.batch) {
+            if (in_span<GRP>(p.batch, cand0, n_cand, c)) {
                 z = p.noise ? *reinterpret_cast<const f32x4 *>(p.noise + (size_t)gc * D0 + qd * 4)
                             : philox_normal4(p.seed, (uint64_t)(p.global_offset + gc), 0u, (uint32_t)qd);
                 if (p.chain && SMODE != MODE_EPS) *reinterpret_cast<f32x4 *>(p.chain + (size_t)gc * D0 + qd * 4) = z;
@@ -437,7 +443,7 @@ struct MlpX3 {
         load_w3(w0, wptr(0), wave, lane16);
         f32x4 nz[NZT][NB];
         StepPlan sp = load_plan(p.plan, 0);
-        if (wave < 4) fetch_noise(nz, p, sp, 0, cand0, wave, lane);
+        if (wave < 4) fetch_noise(nz, p, sp, 0, cand0, n_cand, wave, lane);
         const int tpi = threadIdx.x < COND_TOTAL / 4 ? (int)threadIdx.x : 0;
         f32x4 tpre = reinterpret_cast<const f32x4 *>(p.tproj)[tpi];
 
@@ -536,7 +542,7 @@ struct MlpX3 {
                 for (int g = 0; g < NB; ++g) nzc[j][g] = nz[j][g];
             if (s + 1 < p.n_steps) {
                 sp = load_plan(p.plan, s + 1);
-                if (wave < 4) fetch_noise(nz, p, sp, s + 1, cand0, wave, lane);
+                if (wave < 4) fetch_noise(nz, p, sp, s + 1, cand0, n_cand, wave, lane);
             }
             // next step's layer-0 weights; unconditional (a path-dependent load count drains vmcnt(0))
             load_w3(w0, wptr(0), wave, lane16);
@@ -544,14 +550,14 @@ struct MlpX3 {
             if (wave < 4) {
                 FW f13;
                 to_planes(w13, f13);
-                final_and_update(f13, lds, p, cur, s, cand0, nzc, am, wave, lane);
+                final_and_update(f13, lds, p, cur, s, cand0, n_cand, nzc, am, wave, lane);
             }
         }
         if (SMODE != MODE_EPS && SMODE != MODE_EPS1 && p.chain_absmax) {
             const int col = lane & 15;
             store_chain_absmax<CPW, NTHR>(reinterpret_cast<uint32_t *>(lds + L::AMX), am, col,
                                              (NB == 2 || R == 16) ? -1 : 16 + col,
-                                             wave < 4 && (NB == 1 || R == 32 || col < 8), p.chain_absmax, cand0, p.batch);
+                                             wave < 4 && (NB == 1 || R == 32 || col < 8), p.chain_absmax, cand0, GRP ? cand0 + n_cand : p.batch);
         }
 #ifdef MPCD_PROF_LAYERS
         {
@@ -579,15 +585,32 @@ __global__ __launch_bounds__(64 * W, W == 4 ? 2 : 1) void mlp_x3_kernel(const Ml
     MlpX3<D0, SMODE, CTX, R, W>::run(p);
 }
 
-template <int D0, int SMODE, bool CTX, int R, int W>
+// the grouped-context form (mpcd_sample_grouped): the same program with its workgroups aligned to the groups
+template <int D0, int SMODE, int R, int W>
+__global__ __launch_bounds__(64 * W, W == 4 ? 2 : 1) void mlp_x3_grouped_kernel(const MlpSampleArgs p)
+{
+    MlpX3<D0, SMODE, true, R, W, true>::run(p);
+}
+
+template <int D0, int SMODE, bool CTX, int R, int W, bool GRP = false>
 hipError_t launch_x3_r(const MlpSampleArgs &a, hipStream_t stream)
 {
     using L = Lds3<D0, MlpX3<D0, SMODE, CTX, R, W>::NB, R>;
     static_assert(W == 8 || 2 * L::total <= 160 * 1024, "two 4-wave workgroups per CU");
     static_assert(L::total <= 160 * 1024, "LDS budget (160 KiB per CU)");
-    if (hipError_t e = allow_max_lds<&mlp_x3_kernel<D0, SMODE, CTX, R, W>>(); e != hipSuccess) return e;
-    const int64_t blocks = (a.batch + L::CPW - 1) / L::CPW;
-    return launch_sampler_kernel(mlp_x3_kernel<D0, SMODE, CTX, R, W>, dim3((unsigned)blocks), dim3(64 * W), (size_t)L::total, stream, a);
+    int64_t blocks;
+    int32_t group_wgs;
+    if (!cand_grid(L::CPW, a.batch, GRP ? a.group : 0, &blocks, &group_wgs)) return hipErrorInvalidValue;
+    if constexpr (GRP) {
+        static_assert(CTX, "grouped contexts need a context");
+        if (hipError_t e = allow_max_lds<&mlp_x3_grouped_kernel<D0, SMODE, R, W>>(); e != hipSuccess) return e;
+        MlpSampleArgs g = a;  // the workgroups of this layout per group
+        g.group_wgs = group_wgs;
+        return launch_sampler_kernel(mlp_x3_grouped_kernel<D0, SMODE, R, W>, dim3((unsigned)blocks), dim3(64 * W), (size_t)L::total, stream, g);
+    } else {
+        if (hipError_t e = allow_max_lds<&mlp_x3_kernel<D0, SMODE, CTX, R, W>>(); e != hipSuccess) return e;
+        return launch_sampler_kernel(mlp_x3_kernel<D0, SMODE, CTX, R, W>, dim3((unsigned)blocks), dim3(64 * W), (size_t)L::total, stream, a);
+    }
 }
 
 // Workgroup layout (rows x waves): 32x8 (one per CU), 16x8 when 32-row workgroups would leave CUs idle
@@ -597,7 +620,8 @@ hipError_t launch_x3_r(const MlpSampleArgs &a, hipStream_t stream)
 // rw32x8: mlp_rw.hip's 8-wave form (two waves per SIMD, 32 rows, Linear 5, 6 and half of 7 resident).
 enum { LAYOUT_32x8 = 0, LAYOUT_16x8 = 1, LAYOUT_16x4 = 2, LAYOUT_RW32 = 3, LAYOUT_RW16 = 4, LAYOUT_RW32X8 = 5 };
 std::atomic<int> g_force_layout{-1};  // mpcd_mlp_force_layout (tests: every layout against the oracle)
-int mlp_x3_layout(int64_t batch, int nb)
+// n_groups x group candidates, each group on workgroups of its own (mpcd_sample_grouped); a plain call is one group
+int mlp_x3_layout(int64_t n_groups, int64_t group, int nb)
 {
     if (const int f = g_force_layout.load(); f >= 0) return f;
     static const int forced = [] {
@@ -614,20 +638,26 @@ int mlp_x3_layout(int64_t batch, int nb)
     // The 32-row form on 8 waves (rw32x8) since it beat rw32 beyond the run-to-run spread in alternating runs on
     // one box: kernel 1.069 vs 1.084 ms at 4,096 candidates, 2.128 vs 2.164 at 8,192, 4.246 vs 4.313 at 16,384
     // (profiles/rw8_ab.txt)
+    // A grouped call: the same rule on the 32-row workgroups it would launch, and 16 rows where a group's rows fill
+    // at most half of a 32-row workgroup: a launch takes (rounds of workgroups over the CUs) x (one round's time),
+    // and a round of rw16 is 0.757 ms where one of rw32x8 is 1.07 - 1.10 (cfg2 shape; 512 groups of 8: 1.517 ms in
+    // two rounds of rw16 - profiles/grouped_ab.txt, which has no run with the 32-row layout forced at that split)
+    if (n_groups > 1 && group * nb <= 16) return LAYOUT_RW16;
     const int n_cu = device_cu_count();
-    return (batch * nb + 31) / 32 < n_cu ? LAYOUT_RW16 : LAYOUT_RW32X8;
+    return n_groups * ((group * nb + 31) / 32) < n_cu ? LAYOUT_RW16 : LAYOUT_RW32X8;
 }
+int mlp_x3_layout(int64_t batch, int nb) { return mlp_x3_layout(1, batch, nb); }
 
-template <int D0, int SMODE, bool CTX>
+template <int D0, int SMODE, bool CTX, bool GRP = false>
 hipError_t launch_x3(const MlpSampleArgs &a, int layout, hipStream_t stream)
 {
     constexpr int NB = MlpX3<D0, SMODE, CTX, 32>::NB;
     switch (layout) {
-    case LAYOUT_16x8: return launch_x3_r<D0, SMODE, CTX, 16, 8>(a, stream);
+    case LAYOUT_16x8: return launch_x3_r<D0, SMODE, CTX, 16, 8, GRP>(a, stream);
     case LAYOUT_16x4:  // where two 16-row workgroups fit the CU's LDS (else 16x8)
-        if constexpr (2 * Lds3<D0, NB, 16>::total <= 160 * 1024) return launch_x3_r<D0, SMODE, CTX, 16, 4>(a, stream);
-        else return launch_x3_r<D0, SMODE, CTX, 16, 8>(a, stream);
-    default: return launch_x3_r<D0, SMODE, CTX, 32, WAVES>(a, stream);
+        if constexpr (2 * Lds3<D0, NB, 16>::total <= 160 * 1024) return launch_x3_r<D0, SMODE, CTX, 16, 4, GRP>(a, stream);
+        else return launch_x3_r<D0, SMODE, CTX, 16, 8, GRP>(a, stream);
+    default: return launch_x3_r<D0, SMODE, CTX, 32, WAVES, GRP>(a, stream);
     }
 }
 
@@ -635,6 +665,16 @@ template <int D0>
 hipError_t launch_x3_d0(const MlpSampleArgs &a, int lay, hipStream_t stream)
 {
     const bool ctx = a.cproj != nullptr;
+    if (a.group > 0) {  // grouped contexts: the samplers (mpcd_sample_grouped), with a context
+        if (!ctx) return hipErrorInvalidValue;
+        switch (a.mode) {
+        case MODE_DDPM_CFG:
+            return a.noise ? launch_x3<D0, MODE_DDPM_XN, true, true>(a, lay, stream) : launch_x3<D0, MODE_DDPM_CFG, true, true>(a, lay, stream);
+        case MODE_DDIM_CFG: return launch_x3<D0, MODE_DDIM_CFG, true, true>(a, lay, stream);
+        case MODE_DDIM: return launch_x3<D0, MODE_DDIM, true, true>(a, lay, stream);
+        }
+        return hipErrorInvalidValue;
+    }
     switch (a.mode) {
     case MODE_DDPM_CFG:
         if (a.noise) return ctx ? launch_x3<D0, MODE_DDPM_XN, true>(a, lay, stream) : launch_x3<D0, MODE_DDPM_XN, false>(a, lay, stream);
@@ -651,6 +691,7 @@ hipError_t launch_x3_d0(const MlpSampleArgs &a, int lay, hipStream_t stream)
 
 void mlp_x3_force_layout(int layout) { g_force_layout.store(layout); }
 int mlp_x3_layout_of(int64_t batch, int nb) { return mlp_x3_layout(batch, nb); }
+int mlp_x3_layout_grouped(int64_t n_groups, int64_t group, int nb) { return mlp_x3_layout(n_groups, group, nb); }
 
 int mlp_packed_floats_x3(int d0)
 {
@@ -717,8 +758,11 @@ void mlp_pack_weights_x3(int d0, const float *const *lin_w, const float *const *
 hipError_t launch_mlp_x3(int d0, int nb, const MlpSampleArgs &a, hipStream_t stream)
 {
     if ((nb == 1) != (a.mode == MODE_DDIM || a.mode == MODE_EPS1)) return hipErrorInvalidValue;
-    if (a.cproj && a.cproj_stride != 0) return hipErrorInvalidValue;  // shared context only
-    const int lay = mlp_x3_layout(a.batch, nb);  // decided once per call
+    // one projection row per workgroup: a shared context, or one row per group of candidates
+    if (a.cproj && a.cproj_stride != 0 && a.group <= 0) return hipErrorInvalidValue;
+    if (a.group > 0 && (!a.cproj || a.batch % a.group != 0 || a.ctx_fused)) return hipErrorInvalidValue;
+    // decided once per call
+    const int lay = a.group > 0 ? mlp_x3_layout(a.batch / a.group, a.group, nb) : mlp_x3_layout(a.batch, nb);
     if (lay == LAYOUT_RW32X8) return launch_mlp_rw(d0, 32, 8, a, stream);
     if (lay == LAYOUT_RW32 || lay == LAYOUT_RW16) return launch_mlp_rw(d0, lay == LAYOUT_RW32 ? 32 : 16, 4, a, stream);
     switch (d0) {

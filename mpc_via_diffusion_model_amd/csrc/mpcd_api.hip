@@ -484,20 +484,21 @@ int upload_net(mpcd_ctx *c, const mpcd_net_desc &d, const float *blob, size_t n_
 namespace {
 // MLP kernel choice (mlp_kernel_of): the two-term fp16 kernel for an MPCD_F16X2 net where it applies (CFG-DDPM or
 // the eps forward, H*d 32 / 64, shared context), the split-bf16 kernels for MPCD_F32X3 / the other MPCD_F16X2 cases
-// with a shared (or no) context, else the exact-f32 kernel. All are GPU kernels with fp32-level results.
+// with a shared (or no) context or one row per group of candidates (grouped: mpcd_sample_grouped, which the fp16
+// kernel does not take), else the exact-f32 kernel. All are GPU kernels with fp32-level results.
 enum { MLPK_F32 = 0, MLPK_X3 = 1, MLPK_H2 = 2 };
-int mlp_kernel_of(const mpcd_ctx *c, int mode, bool shared_ctx)
+int mlp_kernel_of(const mpcd_ctx *c, int mode, bool shared_ctx, bool grouped = false)
 {
     const int d0 = c->desc.horizon * c->desc.state_dim;
-    if (c->desc.dtype == MPCD_F16X2 && !c->force_x3 && shared_ctx && c->wpackh.p && mlp_h2_supports(d0, mode))
+    if (c->desc.dtype == MPCD_F16X2 && !c->force_x3 && shared_ctx && !grouped && c->wpackh.p && mlp_h2_supports(d0, mode))
         return MLPK_H2;
-    if ((c->desc.dtype == MPCD_F32X3 || c->desc.dtype == MPCD_F16X2) && shared_ctx) return MLPK_X3;
+    if ((c->desc.dtype == MPCD_F32X3 || c->desc.dtype == MPCD_F16X2) && (shared_ctx || grouped)) return MLPK_X3;
     return MLPK_F32;
 }
 hipError_t launch_mlp(mpcd_ctx *c, MlpSampleArgs &m, int nb, hipStream_t st)
 {
     const int d0 = c->desc.horizon * c->desc.state_dim;
-    const int k = mlp_kernel_of(c, m.mode, m.cproj == nullptr || m.cproj_stride == 0);
+    const int k = mlp_kernel_of(c, m.mode, m.cproj == nullptr || m.cproj_stride == 0, m.group > 0);
     if (k == MLPK_H2) {
         m.wpack = c->wpackh.as<float>();
         const int lay = mlp_x3_layout_of(m.batch, nb);  // the bf16x3 layouts' row choice: 16x8, 16x4, rw16 -> 16 rows
@@ -635,14 +636,29 @@ int mpcd_sample_steps(mpcd_ctx *c, const mpcd_sample_args *a, int32_t *n)
 
 // ctx_row: mpcd_mpc_step's one shared context row by value (the ctx prologue reads it from its kernel
 // arguments: no host-to-device copy); nullptr: a->context on the device (the C-ABI mpcd_sample)
-static int sample_impl(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr, const CtxRowArg *ctx_row);
+// group: mpcd_sample_grouped's candidates per context row (a->context is [batch / group][C]); 0: mpcd_sample
+static int sample_impl(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr, const CtxRowArg *ctx_row,
+                       int64_t group = 0);
 
 int mpcd_sample(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr)
 {
     return sample_impl(c, a, stream_ptr, nullptr);
 }
 
-static int sample_impl(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr, const CtxRowArg *ctx_row)
+int mpcd_sample_grouped(mpcd_ctx *c, const mpcd_sample_args *a, int64_t group, void *stream_ptr)
+{
+    if (!c || !a) return fail(MPCD_EINVAL, "null argument");
+    if (group < 1) return fail(MPCD_EINVAL, "mpcd_sample_grouped: group %lld < 1", (long long)group);
+    if (a->batch < 1 || a->batch % group != 0)
+        return fail(MPCD_EINVAL, "mpcd_sample_grouped: batch %lld is not a multiple of group %lld", (long long)a->batch,
+                    (long long)group);
+    if (c->net_loaded && c->desc.context_dim == 0)
+        return fail(MPCD_EINVAL, "mpcd_sample_grouped: the net has no context (context_dim == 0)");
+    if (!a->context) return fail(MPCD_EINVAL, "mpcd_sample_grouped: no context given");
+    return sample_impl(c, a, stream_ptr, nullptr, group);
+}
+
+static int sample_impl(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr, const CtxRowArg *ctx_row, int64_t group)
 {
     if (!c || !a) return fail(MPCD_EINVAL, "null argument");
     if (!c->net_loaded) return fail(MPCD_ESTATE, "no net loaded");
@@ -686,9 +702,11 @@ static int sample_impl(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr,
     const int mk = d.kind == MPCD_NET_MLP ? mlp_kernel_of(c, a->sampler, true) : -1;
     const bool fuse_ctx = ctx_row && (mk == MLPK_H2 || mk == MLPK_X3);
     if (d.context_dim > 0) {
-        const bool shared = ctx_row || a->context_shared;
-        const int64_t rows = shared ? 1 : a->batch;
-        if ((rc = c->cproj.ensure(sizeof(float) * (size_t)rows * c->cond_total))) return rc;
+        const bool shared = group == 0 && (ctx_row || a->context_shared);
+        const int64_t rows = shared ? 1 : group > 0 ? a->batch / group : a->batch;
+        // grouped U-Net: the rows' projections, then their per-candidate copy behind them (below)
+        const int64_t spread = group > 0 && d.kind != MPCD_NET_MLP ? a->batch : 0;
+        if ((rc = c->cproj.ensure(sizeof(float) * (size_t)(rows + spread) * c->cond_total))) return rc;
         if (fuse_ctx) {
             // computed by the sampler launch itself (ctx_proj_col)
         } else if (ctx_row)
@@ -700,6 +718,12 @@ static int sample_impl(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr,
         HIP_TRY(hipGetLastError());
         cproj = c->cproj.as<float>();
         cstride = shared ? 0 : c->cond_total;
+        if (spread) {  // the U-Net kernels index their table per candidate: row b = projection b / group
+            float *per_cand = c->cproj.as<float>() + (size_t)rows * c->cond_total;
+            launch_ctx_replicate(cproj, a->batch, group, c->cond_total, per_cand, st);
+            HIP_TRY(hipGetLastError());
+            cproj = per_cand;
+        }
     }
     const float wp1 = (float)(1.0 + a->w), wf = (float)a->w;
     c->ev0 = c->evr[0][c->ev_n % mpcd_ctx::kEvRing];
@@ -727,6 +751,7 @@ static int sample_impl(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr,
         m.clamp_x0 = a->clamp_x0;
         m.wp1 = wp1;
         m.wf = wf;
+        m.group = group;
         if (fuse_ctx) {
             m.ctx_fused = 1;
             m.ctx_row = *ctx_row;
@@ -896,6 +921,20 @@ int mpcd_mlp_form(mpcd_ctx *c, int32_t sampler, int64_t batch, int32_t out[3])
     out[0] = k;
     out[1] = k == MLPK_X3 ? lay : -1;
     out[2] = (lay == 1 || lay == 2 || lay == 4) ? 16 : 32;
+    return MPCD_OK;
+}
+
+int mpcd_mlp_form_grouped(mpcd_ctx *c, int32_t sampler, int64_t n_groups, int64_t group, int32_t out[3])
+{
+    if (!c || !out || n_groups < 1 || group < 1) return fail(MPCD_EINVAL, "bad argument");
+    if (!c->net_loaded || c->desc.kind != MPCD_NET_MLP) return fail(MPCD_EUNSUP, "not an MLP context");
+    if (sampler < MPCD_DDPM_CFG || sampler > MPCD_DDIM) return fail(MPCD_EINVAL, "bad sampler %d", sampler);
+    DEVICE_GUARD(c->device);
+    const int k = mlp_kernel_of(c, sampler, false, true);
+    const int lay = mlp_x3_layout_grouped(n_groups, group, c->desc.cfg_masked ? 2 : 1);
+    out[0] = k;
+    out[1] = k == MLPK_X3 ? lay : -1;
+    out[2] = k == MLPK_X3 && (lay == 1 || lay == 2 || lay == 4) ? 16 : 32;  // the exact-f32 kernel has 32 rows
     return MPCD_OK;
 }
 

@@ -81,7 +81,7 @@ class NetSpec:
     time_emb_dim: int = 32
     cfg: bool = True          # 4-arg net with the CFG context mask
     # GEMM numerics (include/mpcd.h mpcd_dtype): "f32" exact fp32 MFMA; "f32x3" fp32-accurate split-bf16
-    # MFMA (MLP: shared or no context; UNet: any); "f16" fp16 operands / fp32 accumulate (UNet, cfg 5); "f16x2"
+    # MFMA (MLP: shared, grouped (context_group) or no context; UNet: any); "f16" fp16 operands / fp32 accumulate (UNet, cfg 5); "f16x2"
     # two-term fp16 MFMA - NOT fp32 arithmetic: 22-bit operands in the fp16 range (MLP: the CFG-DDPM sampler / eps
     # forward at H*d 32 or 64 with a shared context; U-Net: the fused CFG-DDPM program; the other cases of such a
     # net run its f32x3 kernels). A call that leaves the fp16 range (NaN in the chain) is re-run in f32x3.
@@ -234,9 +234,18 @@ class DiffusionMPC:
         return _SAMPLERS[name]
 
     def _args(self, sampler, batch, context, w, n_wo_noise, ddim_steps, clamp_x0, seed, global_offset, noise,
-              x_out, chain, absmax=None):
+              x_out, chain, absmax=None, group=None):
         a = N.SampleArgs()
-        if self.spec.context_dim > 0 and context is not _STEP_CONTEXT:
+        if group is not None:  # mpcd_sample_grouped: one context row per `group` consecutive candidates
+            if self.spec.context_dim == 0:
+                raise ValueError("context_group needs a net with a context")
+            if group < 1 or batch % group != 0:
+                raise ValueError(f"context_group={group} must be >= 1 and divide n_samples={batch}")
+            if context is None or context is _STEP_CONTEXT or context.shape[0] != batch // group:
+                rows = None if context is None or context is _STEP_CONTEXT else context.shape[0]
+                raise ValueError(f"context rows {rows} must be n_samples / context_group = {batch // group}")
+            a.context = context.data_ptr()
+        elif self.spec.context_dim > 0 and context is not _STEP_CONTEXT:
             if context is None:
                 raise ValueError("this net needs a context")
             a.context = context.data_ptr()
@@ -278,9 +287,12 @@ class DiffusionMPC:
 
     def sample_trajectories(self, context=None, n_samples=1, horizon=None, w=0.01, sample_fn="ddpm_cfg",
                             n_wo_noise=0, ddim_steps=None, clamp_x0=False, seed=0, global_offset=0, noise=None,
-                            return_chain=False, out=None, absmax_out=None):
+                            return_chain=False, out=None, absmax_out=None, context_group=None):
         """Normalised candidate trajectories [B, H, d] (or the chain [S+1, B, H, d]).
         context: [1, C] (shared) or [B, C] normalised fp32; noise: optional injected [S+1, B, H, d].
+        context_group=g: context is [B / g, C], candidate b uses row b // g (mpcd_sample_grouped: a closed-loop
+        batch of B / g plant states with g candidates each; an f32x3 MLP keeps its split-bf16 kernels, where a
+        [B, C] context runs the exact-f32 one). Anything but B / g rows raises ValueError.
         absmax_out: optional fp32 [B] device tensor <- per candidate max |x| over the whole chain
         (x_T .. x_0; NaN if any NaN): the input of the reference's chain-wide clip test without
         materialising the chain."""
@@ -311,14 +323,23 @@ class DiffusionMPC:
         amax = absmax_out
         if guard and amax is None:
             amax = torch.empty(B, dtype=torch.float32, device=self.device)
+        group = None if context_group is None else int(context_group)
         a = self._args(sampler, B, context, w, n_wo_noise, ddim_steps, clamp_x0, seed, global_offset, noise, x, chain,
-                       amax)
-        N.check(self._lib.mpcd_sample(self._ctx, ctypes.byref(a), self._stream()), "mpcd_sample")
+                       amax, group)
+
+        def run(what):
+            if group is None:
+                N.check(self._lib.mpcd_sample(self._ctx, ctypes.byref(a), self._stream()), what)
+            else:
+                N.check(self._lib.mpcd_sample_grouped(self._ctx, ctypes.byref(a), group, self._stream()),
+                        what.replace("mpcd_sample", "mpcd_sample_grouped"))
+
+        run("mpcd_sample")
         self.last_f32x3_rerun = False
         if guard and bool(torch.isnan(amax).any()):
             N.check(self._lib.mpcd_force_f32x3(self._ctx, 1), "mpcd_force_f32x3")
             try:
-                N.check(self._lib.mpcd_sample(self._ctx, ctypes.byref(a), self._stream()), "mpcd_sample (f32x3 re-run)")
+                run("mpcd_sample (f32x3 re-run)")
             finally:
                 N.check(self._lib.mpcd_force_f32x3(self._ctx, 0), "mpcd_force_f32x3")
             self.last_f32x3_rerun = True
@@ -374,6 +395,34 @@ class DiffusionMPC:
         lay = {v: k for k, v in MLP_LAYOUTS.items()}.get(out[1]) if out[1] >= 0 else None
         return {"kernel": ("f32", "x3", "h2")[out[0]], "layout": lay, "rows_per_workgroup": int(out[2])}
 
+    def mlp_form_grouped(self, n_groups, group, sample_fn="ddpm_cfg"):
+        """mlp_form for a sample call with context_group=group over n_groups context rows (mpcd_mlp_form_grouped):
+        the kernel is "x3" for an f32x3 / f16x2 net and "f32" for an f32 one, never "h2"."""
+        out = (ctypes.c_int32 * 3)()
+        N.check(self._lib.mpcd_mlp_form_grouped(self._ctx, self._sampler_id(sample_fn), int(n_groups), int(group), out),
+                "mpcd_mlp_form_grouped")
+        lay = {v: k for k, v in MLP_LAYOUTS.items()}.get(out[1]) if out[1] >= 0 else None
+        return {"kernel": ("f32", "x3", "h2")[out[0]], "layout": lay, "rows_per_workgroup": int(out[2])}
+
+    # Sampler-kernel time of one round of workgroups (one per CU) relative to the exact-f32 kernel's, measured at the
+    # cfg2 net shape on an MI355X (profiles/grouped_ab.txt): rw32x8 1.09 ms, rw16 0.757 ms, exact f32 1.68 ms
+    _ROUND_COST = {32: 0.65, 16: 0.45}
+
+    def grouped_pays(self, n_groups, group, sample_fn="ddpm_cfg"):
+        """Whether a grouped sample call of n_groups x group candidates is expected to beat the same call with one
+        context row per candidate. Only an MLP on the split-bf16 kernels can lose: its workgroups hold candidates of
+        one group only, so small groups leave them part empty (one candidate per group: 12.0 against 1.68 ms at 4,096
+        candidates). Both kernels take (rounds of workgroups over the CUs) x (the time of one round), which is what
+        is compared, with the measured round times."""
+        if self.spec.kind != "mlp" or self.mlp_form_grouped(n_groups, group, sample_fn)["kernel"] != "x3":
+            return True  # the same kernel either way, and no repeated rows to build
+        rows = self.mlp_form_grouped(n_groups, group, sample_fn)["rows_per_workgroup"]
+        n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
+        nb = 2 if self.spec.cfg else 1
+        wgs = n_groups * -(-group * nb // rows)
+        wgs_f32 = -(-n_groups * group * nb // 32)
+        return -(-wgs // n_cu) * self._ROUND_COST[rows] < -(-wgs_f32 // n_cu) * 1.0
+
     def last_sample_ms(self):
         ms = ctypes.c_float()
         N.check(self._lib.mpcd_last_sample_ms(self._ctx, ctypes.byref(ms)), "mpcd_last_sample_ms")
@@ -416,7 +465,7 @@ class DiffusionMPC:
 
     def closed_loop(self, x0_states, system: System, iterations, n_samples=1, w=0.01, sample_fn="ddpm_cfg",
                     n_wo_noise=0, ddim_steps=None, clamp_x0=False, select="argmin", decimals=4, seed=0, noise=None,
-                    clip_rule="chain"):
+                    clip_rule="chain", grouped=False):
         """Closed-loop diffusion MPC for M plant states at once, resident on the device.
         The reference runs one initial state at a time on the host (Cart_Diffusion_inference.py:405-512:
         normalize_condition -> run_CFG -> unnormalize -> u0 = round(u[0], 4) -> x = f(x, u0), repeated
@@ -424,8 +473,15 @@ class DiffusionMPC:
         (mpcd_normalize_states), n_samples candidates per state in one sampler launch, per-state clip flags,
         rollout + cost from each state's own x, and mpcd_control_step (per-state selection, u0, plant step);
         nothing returns to the host until the end. select: "argmin" (lowest cost) or "first" (candidate 0 of
-        each group: the reference scripts with n_samples = 1). Per-state contexts use the exact-f32 MLP
-        kernel (the split-bf16 one needs a shared context). noise: optional callable it -> injected sampler
+        each group: the reference scripts with n_samples = 1). grouped=False (the default) hands the sampler one
+        context row per candidate (each state's row repeated n_samples times): an MLP then runs the exact-f32
+        kernel whatever spec.dtype says. grouped=True hands it the [M, C] rows with context_group=n_samples
+        (mpcd_sample_grouped): an f32x3 or f16x2 MLP runs the split-bf16 kernels with workgroups aligned to the
+        states, each state's samples bit-identical to a shared-context call for that state; an f32 MLP and a
+        U-Net compute what grouped=False computes. Measured at 4,096 candidates (profiles/grouped_ab.txt): 64 x 64
+        and 256 x 16 take the shared-context time, 1.07 - 1.10 ms against 1.68 ms per candidate, but the part-empty
+        workgroups of small groups lose (4,096 x 1: 12.0 ms), so grouped=True falls back to per-candidate rows
+        where grouped_pays() says so. noise: optional callable it -> injected sampler
         noise [S+1, M*n_samples, H, d] (parity tests); default in-kernel Philox keyed by (seed + it).
         clip_rule: "chain" (the reference: run_CFG(return_chain=True) then unnormalize_states of the whole
         chain, so each state's clip test also sees its x_T) or "final" (the final samples only)."""
@@ -454,13 +510,14 @@ class DiffusionMPC:
         u_norm = torch.empty((B, H, d), dtype=torch.float32, device=dev)
         absmax = torch.empty(B, dtype=torch.float32, device=dev) if clip_rule == "chain" else None
         ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        grouped = bool(grouped) and self.grouped_pays(M, n, sample_fn)
         xs[0] = x
         for it in range(T):
             N.check(self._lib.mpcd_normalize_states(self._ctx, ptr(x), M, nx, self.ctx_min.ctypes.data,
                                                     self.ctx_max.ctypes.data, ptr(ctx), st), "mpcd_normalize_states")
-            self.sample_trajectories(ctx.repeat_interleave(n, dim=0), B, H, w, sample_fn, n_wo_noise, ddim_steps,
-                                     clamp_x0, seed + it, 0, None if noise is None else noise(it), False, out=u_norm,
-                                     absmax_out=absmax)
+            self.sample_trajectories(ctx if grouped else ctx.repeat_interleave(n, dim=0), B, H, w, sample_fn, n_wo_noise,
+                                     ddim_steps, clamp_x0, seed + it, 0, None if noise is None else noise(it), False,
+                                     out=u_norm, absmax_out=absmax, context_group=n if grouped else None)
             if absmax is not None:  # each state's flag over its candidates' chains
                 N.check(self._lib.mpcd_clip_flags(self._ctx, ptr(absmax), M, n, ptr(flags), st), "mpcd_clip_flags")
             else:
