@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 namespace mlpc {
@@ -40,6 +42,10 @@ struct Arch {
     }
     static constexpr int btotal() { return boff(NLAYER); }
 };
+
+// Arch<d0>'s layer shapes for host code that has d0 at run time (the weight packers)
+inline int layer_k(int d0, int l) { return l == 0 ? d0 : Arch<32>::K[l]; }
+inline int layer_n(int d0, int l) { return l == NLAYER - 1 ? d0 : Arch<32>::N[l]; }
 
 // cond block j (0..5) -> column offset in the 448-wide tables
 __host__ __device__ constexpr int cond_off(int j) { return j == 0 ? 0 : j == 1 ? 32 : j == 2 ? 96 : j == 3 ? 224 : j == 4 ? 352 : 416; }
@@ -114,6 +120,107 @@ inline bool cand_grid(int cpw, int64_t batch, int64_t group, int64_t *blocks, in
     }
     return *blocks <= INT32_MAX;
 }
+
+// A call's run-time choices -> the template parameters of the MLP sampler kernels, once for the four families:
+// f(D0, SMODE, CTX, GRP) is called with std::integral_constants (usable as template arguments) for H*d = d0, the
+// sampler mode (CFG-DDPM with caller-supplied noise is MODE_DDPM_XN), context or none, grouped contexts or not.
+// hipErrorInvalidValue where no kernel has the combination: an unknown d0 or mode, a grouped call without a context
+// or of the eps forwards (grouped calls are the samplers': mpcd_sample_grouped). A family rejects what else it does
+// not build with if constexpr, and one with no grouped form passes grouped = false.
+template <class F>
+hipError_t sampler_dispatch(int d0, int mode, bool noise, bool ctx, bool grouped, F f)
+{
+    auto with_d0 = [&](auto D0) -> hipError_t {
+        auto with_mode = [&](auto SMODE) -> hipError_t {
+            constexpr std::true_type yes{};
+            constexpr std::false_type no{};
+            if (grouped) {
+                if constexpr (SMODE != MODE_EPS && SMODE != MODE_EPS1)
+                    if (ctx) return f(D0, SMODE, yes, yes);
+                return hipErrorInvalidValue;
+            }
+            return ctx ? f(D0, SMODE, yes, no) : f(D0, SMODE, no, no);
+        };
+        switch (mode) {
+        case MODE_DDPM_CFG:
+            return noise ? with_mode(std::integral_constant<int, MODE_DDPM_XN>{})
+                         : with_mode(std::integral_constant<int, MODE_DDPM_CFG>{});
+        case MODE_DDIM_CFG: return with_mode(std::integral_constant<int, MODE_DDIM_CFG>{});
+        case MODE_DDIM: return with_mode(std::integral_constant<int, MODE_DDIM>{});
+        case MODE_EPS: return with_mode(std::integral_constant<int, MODE_EPS>{});
+        case MODE_EPS1: return with_mode(std::integral_constant<int, MODE_EPS1>{});
+        }
+        return hipErrorInvalidValue;
+    };
+    switch (d0) {
+    case 32: return with_d0(std::integral_constant<int, 32>{});
+    case 64: return with_d0(std::integral_constant<int, 64>{});
+    case 128: return with_d0(std::integral_constant<int, 128>{});
+    }
+    return hipErrorInvalidValue;
+}
+
+// Layer profile of the MLP sampler kernels (tools/layer_prof.py, tools/mlp_prof.sh). Only a build with
+// -DMPCD_PROF_LAYERS measures: per-wave shader-clock cycles of each barrier-to-barrier segment k (work, then the
+// barrier wait) in tacc[2 k] / tacc[2 k + 1], dumped to MlpSampleArgs::dbg at the kernel's end. A kernel keeps
+//     ProfAcc tacc = {}; const uint64_t rt0 = prof_realtime(); uint64_t tprev = prof_now(); const uint64_t ct0 = tprev;
+// In the product build ProfAcc is empty, the clocks read 0, prof_barrier() is lds_barrier() and the rest does nothing:
+// the kernels carry no trace of it.
+#ifdef MPCD_PROF_LAYERS
+typedef uint64_t ProfAcc[2 * 16];
+MPCD_DEV uint64_t prof_now() { return __builtin_readcyclecounter(); }
+MPCD_DEV uint64_t prof_realtime() { return __builtin_amdgcn_s_memrealtime(); }
+MPCD_DEV void prof_barrier(ProfAcc &tacc, uint64_t &tprev, int k)  // ends segment k
+{
+    uint64_t t = __builtin_readcyclecounter();
+    tacc[2 * k] += t - tprev;
+    lds_barrier();
+    tprev = __builtin_readcyclecounter();
+    tacc[2 * k + 1] += tprev - t;
+}
+// cycles of a stretch inside a segment: t0 = prof_now() ... prof_mark(tacc, t0, k, dep) adds the cycles since t0 to
+// tacc[k] once dep is computed, and moves t0 on
+template <class T>
+MPCD_DEV void prof_mark(ProfAcc &tacc, uint64_t &t0, int k, const T &dep)
+{
+    asm volatile("" ::"v"(dep) : "memory");
+    const uint64_t t = __builtin_readcyclecounter();
+    tacc[k] += t - t0;
+    t0 = t;
+}
+MPCD_DEV void prof_mark(ProfAcc &tacc, uint64_t t0, int k)
+{
+    asm volatile("" ::: "memory");
+    tacc[k] += __builtin_readcyclecounter() - t0;
+}
+// The end-of-kernel dump, in a scope with the four variables above and the MlpSampleArgs p. W waves per workgroup: the
+// first 32 / W workgroups fill the 32 wave slots. A macro, not a function: as a function it changed the profile
+// build's register allocation and schedule in every kernel (profiles/mlp_switch_cleanup_isa.txt).
+#define MPCD_PROF_DUMP(W, wave, lane)                                                                                  \
+    do {                                                                                                               \
+        const uint64_t t = __builtin_readcyclecounter();                                                               \
+        tacc[2 * 15] += t - tprev;                                                                                     \
+        if (p.dbg && blockIdx.x < 32 / (W) && (lane) == 0)                                                             \
+            for (int i = 0; i < 32; ++i) p.dbg[(blockIdx.x * (W) + (wave)) * 32 + i] = (float)tacc[i];                 \
+        if (p.dbg && threadIdx.x == 0) { /* per-block loop start / end (memrealtime, low 32 bits) */                   \
+            p.dbg[4096 + blockIdx.x * 2] = __builtin_bit_cast(float, (uint32_t)rt0);                                   \
+            p.dbg[4096 + blockIdx.x * 2 + 1] = __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_s_memrealtime()); \
+        }                                                                                                              \
+        if (p.dbg && blockIdx.x < 8 && threadIdx.x == 0) { /* shader clock = d(memtime) / d(memrealtime) x 100 MHz */  \
+            p.dbg[8 * 4 * 32 + blockIdx.x * 2] = (float)(t - ct0);                                                     \
+            p.dbg[8 * 4 * 32 + blockIdx.x * 2 + 1] = (float)(__builtin_amdgcn_s_memrealtime() - rt0);                  \
+        }                                                                                                              \
+    } while (0)
+#else
+struct ProfAcc {};
+MPCD_DEV uint64_t prof_now() { return 0; }
+MPCD_DEV uint64_t prof_realtime() { return 0; }
+MPCD_DEV void prof_barrier(ProfAcc &, uint64_t &, int) { lds_barrier(); }
+template <class T>
+MPCD_DEV void prof_mark(ProfAcc &, uint64_t &, int, const T &) {}
+MPCD_DEV void prof_mark(ProfAcc &, uint64_t, int) {}
+#define MPCD_PROF_DUMP(W, wave, lane) (void)0
+#endif
 
 // |v| as an ordered integer: max over these bits is max |v| and propagates a NaN (its magnitude bits
 // exceed +inf's), which is what the chain clip test needs (mpcd_sample_args.chain_absmax).

@@ -630,26 +630,17 @@ struct MlpH2 {
         const int tblk = tcol < 32 ? 0 : tcol < 96 ? 1 : tcol < 224 ? 2 : tcol < 352 ? 3 : tcol < 416 ? 4 : 5;
         const float tscale = p.wpack[2 * tblk + 1];  // s of cond layer 2 * block + 1
         f32x4 tpre = reinterpret_cast<const f32x4 *>(p.tproj)[tpi];
-#ifdef MPCD_PROF_LAYERS
-        // experiment build only: per-wave shader-clock cycles of each barrier-to-barrier segment (work, then the
-        // barrier wait), the dump format of mlp_rw.hip (tools/layer_prof.py, H2=1: segment 0 = the cond tables +
-        // Linear 0, 1..12 = Linear 1..12, 13 = the final Linear + update)
-        uint64_t tacc[2 * 16] = {};
-        const uint64_t rt0 = __builtin_amdgcn_s_memrealtime();
-        uint64_t tprev = __builtin_readcyclecounter();
+        // MPCD_PROF_LAYERS build (mlp_common.h; tools/layer_prof.py, H2=1): segment 0 = the cond tables + Linear 0, 1..12 = Linear 1..12,
+        // 13 = the final Linear + update
+        ProfAcc tacc = {};
+        const uint64_t rt0 = prof_realtime();
+        uint64_t tprev = prof_now();
         const uint64_t ct0 = tprev;
-        int bk = 0;
+        int bk = 0;  // the segment: 14 barriers per denoise step
         auto bar = [&] {
-            uint64_t t = __builtin_readcyclecounter();
-            tacc[2 * bk] += t - tprev;
-            lds_barrier();
-            tprev = __builtin_readcyclecounter();
-            tacc[2 * bk + 1] += tprev - t;
+            prof_barrier(tacc, tprev, bk);
             bk = bk == 13 ? 0 : bk + 1;
         };
-#else
-        auto bar = [] { lds_barrier(); };
-#endif
         int wofs = 0;
 
         bar();  // x_T, tables and biases staged
@@ -711,22 +702,7 @@ struct MlpH2 {
             final_and_update(w13, sc_of(lds, 13), lds, p, cur, s, cand0, nzc, am, wave, lane);
             bar();  // x planes of the next step written; this step's last reads of TPC / TPU long done
         }
-#ifdef MPCD_PROF_LAYERS
-        {
-            const uint64_t t = __builtin_readcyclecounter();
-            tacc[2 * 15] += t - tprev;
-            if (p.dbg && blockIdx.x < 32 / H2_W && lane == 0)
-                for (int i = 0; i < 32; ++i) p.dbg[(blockIdx.x * H2_W + (threadIdx.x >> 6)) * 32 + i] = (float)tacc[i];
-            if (p.dbg && threadIdx.x == 0) {
-                p.dbg[4096 + blockIdx.x * 2] = __builtin_bit_cast(float, (uint32_t)rt0);
-                p.dbg[4096 + blockIdx.x * 2 + 1] = __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_s_memrealtime());
-            }
-            if (p.dbg && blockIdx.x < 8 && threadIdx.x == 0) {
-                p.dbg[8 * 4 * 32 + blockIdx.x * 2] = (float)(t - ct0);
-                p.dbg[8 * 4 * 32 + blockIdx.x * 2 + 1] = (float)(__builtin_amdgcn_s_memrealtime() - rt0);
-            }
-        }
-#endif
+        MPCD_PROF_DUMP(H2_W, threadIdx.x >> 6, lane);
         if (SMODE != MODE_EPS && p.chain_absmax) {
             const int col = lane & 15;
             store_chain_absmax<CPW, H2_T>(reinterpret_cast<uint32_t *>(lds + L::AMX), am, col, -1, R == 32 || col < 8,
@@ -757,19 +733,6 @@ hipError_t launch_h2(const MlpSampleArgs &a, int rows, hipStream_t stream)
     return rows == 16 ? launch_h2_r<D0, SMODE, CTX, 16>(a, stream) : launch_h2_r<D0, SMODE, CTX, 32>(a, stream);
 }
 
-template <int D0>
-hipError_t launch_h2_d0(const MlpSampleArgs &a, int rows, hipStream_t stream)
-{
-    const bool ctx = a.cproj != nullptr;
-    switch (a.mode) {
-    case MODE_DDPM_CFG:
-        if (a.noise) return ctx ? launch_h2<D0, MODE_DDPM_XN, true>(a, rows, stream) : launch_h2<D0, MODE_DDPM_XN, false>(a, rows, stream);
-        return ctx ? launch_h2<D0, MODE_DDPM_CFG, true>(a, rows, stream) : launch_h2<D0, MODE_DDPM_CFG, false>(a, rows, stream);
-    case MODE_EPS: return ctx ? launch_h2<D0, MODE_EPS, true>(a, rows, stream) : launch_h2<D0, MODE_EPS, false>(a, rows, stream);
-    }
-    return hipErrorInvalidValue;
-}
-
 uint16_t f16_rne(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
 
 }  // namespace
@@ -791,12 +754,10 @@ int mlp_packed_floats_h2(int d0)
 // fp32 bias [N] (unscaled: the kernel scales it). Header: s, 1/s, fp32(log2 e)/s, -2/s per layer.
 void mlp_pack_weights_h2(int d0, const float *const *lin_w, const float *const *lin_b, float *out)
 {
-    const int Ks[NLAYER] = {d0, 32, 32, 64, 64, 128, 128, 128, 256, 64, 128, 32, 32, 32};
-    const int Ns[NLAYER] = {32, 32, 64, 64, 128, 128, 128, 128, 64, 64, 32, 32, 32, d0};
     for (int i = 0; i < HDR; ++i) out[i] = 0.f;
     size_t o = HDR;
     for (int l = 0; l < NLAYER; ++l) {
-        const int K = Ks[l], N = Ns[l], KC = K / 32, NT = N / 16;
+        const int K = layer_k(d0, l), N = layer_n(d0, l), KC = K / 32, NT = N / 16;
         float mx = 0.f;
         for (size_t i = 0; i < (size_t)K * N; ++i) mx = fmaxf(mx, fabsf(lin_w[l][i]));
         int e = 0;
@@ -832,9 +793,9 @@ void mlp_pack_weights_h2(int d0, const float *const *lin_w, const float *const *
 hipError_t launch_mlp_h2(int d0, int rows, const MlpSampleArgs &a, hipStream_t stream)
 {
     if (a.cproj && a.cproj_stride != 0) return hipErrorInvalidValue;  // shared context only
-    switch (d0) {
-    case 32: return launch_h2_d0<32>(a, rows, stream);
-    case 64: return launch_h2_d0<64>(a, rows, stream);
-    }
-    return hipErrorInvalidValue;
+    // CFG-DDPM and the eps forward at H*d 32 / 64 (mlp_h2_supports); no grouped form (mlp_kernel_of sends none here)
+    return sampler_dispatch(d0, a.mode, a.noise != nullptr, a.cproj != nullptr, false, [&](auto D0, auto SMODE, auto CTX, auto) {
+        if constexpr (D0 <= 64 && (SMODE == MODE_DDPM_CFG || SMODE == MODE_DDPM_XN || SMODE == MODE_EPS)) return launch_h2<D0, SMODE, CTX>(a, rows, stream);
+        else return hipErrorInvalidValue;
+    });
 }

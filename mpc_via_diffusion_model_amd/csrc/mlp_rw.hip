@@ -44,28 +44,6 @@ constexpr int RES_AG = 21;             // groups 0..20 resident in AGPRs (63 fra
 // AGPRs), k-chunks 2-3 of Linear 7 stream each step. Waves w and w + 4 share a SIMD.
 constexpr int RES_AG8 = 10;
 
-// Six partial products of one 32-k chunk with the weight planes in AGPRs (the A operand of an MFMA may be
-// an AGPR on gfx950; hipcc does not allocate builtin operands there, so the chain is written out). One
-// statement of six dependent MFMAs: back-to-back srcC forwarding of the same opcode needs no wait states
-// (hipcc emits none between the builtin form of this chain). The leading s_nop covers a VALU write of
-// acc right before the statement (the 2-wait-state VALU-write -> MFMA-read rule, which the compiler's
-// hazard pass does not apply to inline asm); the MFMA result -> VALU read wait after the statement is
-// inserted by the compiler (checked in tests/test_isa.py).
-MPCD_DEV f32x4 mfma_x3_agpr(const u32x4 &w0, const u32x4 &w1, const u32x4 &w2, const u32x4 (&x)[3], f32x4 acc)
-{
-    asm("s_nop 1\n\t"
-        "v_mfma_f32_16x16x32_bf16 %0, %3, %4, %0\n\t"   // w2 x0
-        "v_mfma_f32_16x16x32_bf16 %0, %2, %5, %0\n\t"   // w1 x1
-        "v_mfma_f32_16x16x32_bf16 %0, %1, %6, %0\n\t"   // w0 x2
-        "v_mfma_f32_16x16x32_bf16 %0, %2, %4, %0\n\t"   // w1 x0
-        "v_mfma_f32_16x16x32_bf16 %0, %1, %5, %0\n\t"   // w0 x1
-        "v_mfma_f32_16x16x32_bf16 %0, %1, %4, %0\n\t"  // w0 x0
-        "s_nop 7"                                        // result -> VALU read (see mfma_agpr1)
-        : "+v"(acc)
-        : "a"(w0), "a"(w1), "a"(w2), "v"(x[0]), "v"(x[1]), "v"(x[2]));
-    return acc;
-}
-
 // Transcendental pairs for packed consumers: both issued, then 2 wait states before a packed op may read them (a
 // packed read one wait state behind a v_exp / v_rcp gave wrong results on gfx950: unet_fused.hip exp2_pair,
 // profiles/r3_hazard_ab.txt). The same instructions as __builtin_amdgcn_exp2f / rcpf: the same bits.
@@ -107,83 +85,6 @@ MPCD_DEV f32x4 mfma_agpr1(const u32x4 &w, const u32x4 &x, f32x4 acc)
     return acc;
 }
 
-// MPCD_RW_ILV = 1: each hidden layer as a pipeline of passes (one n-tile x one column tile: a chain of 6 KC
-// MFMAs), the previous pass's epilogue (4 Mish, the split, 3 LDS stores) issued one unit after each of this
-// pass's first MFMAs (pinned with sched_barrier: a bf16 MFMA leaves the SIMD's vector issue free for 8 of its
-// 16 cycles), the next activation fragments read two k-chunks ahead; 0 = the plain form (hidden()).
-#ifndef MPCD_RW_ILV
-#define MPCD_RW_ILV 1
-#endif
-// MPCD_RW_PF: k-chunks of operand fragments read ahead of the MFMAs in hidden_ilv (2: a ring of three)
-#ifndef MPCD_RW_PF
-#define MPCD_RW_PF 2
-#endif
-// MPCD_RW_TABLE_EARLY = 1: the next step's cond tables (TPC / TPU) are written after Linear 11 (the last layer that
-// reads them) instead of at the step's start, where their LDS round trip delayed Linear 0's first operand reads
-#ifndef MPCD_RW_TABLE_EARLY
-#define MPCD_RW_TABLE_EARLY 1
-#endif
-// MPCD_RW_W8_SPLIT = 1 (default): Linear 8's streamed fragments issued half in Linear 5's MFMA slots, half in
-// Linear 6's (0: all 24 in Linear 6's; profiles/r6_mlp_tuning_ab.txt)
-#ifndef MPCD_RW_W8_SPLIT
-#define MPCD_RW_W8_SPLIT 1
-#endif
-// MPCD_RW_TABLE_SIDE = 1 (default, with TABLE_EARLY): the table's two reads and its write ride in Linear 12's
-// MFMA slots
-#ifndef MPCD_RW_TABLE_SIDE
-#define MPCD_RW_TABLE_SIDE 1
-#endif
-// MPCD_RW_PKTAIL = 1 (default): the exposed epilogue of a layer's last pass (nothing left to hide it under) with two
-// values per packed instruction (v_pk_mul / v_pk_add / v_pk_fma_f32, the same roundings) instead of the fenced scalar
-// micro-steps: loop VALU 1,631 -> 1,459 per wave-step, kernel -0.5 % (profiles/r6_mlp_tuning_ab.txt)
-#ifndef MPCD_RW_PKTAIL
-#define MPCD_RW_PKTAIL 1
-#endif
-// MPCD_RW_XREG = 1 (default): each lane keeps its x_t quads in registers across steps (the fp32 copy in LDS goes),
-// and the update's x-only products (a x, c2 x, std z) are formed while the final layer's operand reads are in
-// flight. Together with TABLE_SIDE: kernel 1.098 -> 1.090 ms at cfg2 (profiles/r6_mlp_tuning_ab.txt, 3 repeats)
-#ifndef MPCD_RW_XREG
-#define MPCD_RW_XREG 1
-#endif
-// MPCD_RW_EPI_STEPS = 1: the epilogue spread as 1-2 VALU ops per MFMA slot (hidden_ilv); 0: five units
-#ifndef MPCD_RW_EPI_STEPS
-#define MPCD_RW_EPI_STEPS 1
-#endif
-
-// timing experiments (wrong results): MPCD_RW_EXP_NOLASTEPI drops the last-pass epilogue of the multi-pass
-// layers (hidden_ilv); MPCD_RW_EXP_BAR2 doubles every layer barrier (profiles/r4_mlp_defer_ab.txt)
-#ifndef MPCD_RW_EXP_NOLASTEPI
-#define MPCD_RW_EXP_NOLASTEPI 0
-#endif
-#ifndef MPCD_RW_EXP_BAR2
-#define MPCD_RW_EXP_BAR2 0
-#endif
-// MPCD_RW_EXP_NOVM: the streamed layers' buffer descriptor has zero records (every streamed weight load returns 0
-// without a memory access): the cost of the per-step weight stream, read as cycles per step in an MPCD_PROF_LAYERS
-// build (zero operands also raise the clock, so wall time would overstate it)
-#ifndef MPCD_RW_EXP_NOVM
-#define MPCD_RW_EXP_NOVM 0
-#endif
-#if !defined(MPCD_VARIANT) && (MPCD_RW_EXP_NOLASTEPI || MPCD_RW_EXP_BAR2 || MPCD_RW_EXP_NOVM || defined(MPCD_PROF_FINAL_MFMA_ONLY))
-#error "wrong-result timing switches build only as an experiment variant (build.py variant: -DMPCD_VARIANT)"
-#endif
-
-// The 8-wave form's own tuning switches (same results either way; profiles/rw8_ab.txt):
-// MPCD_RW8_PF: operand k-chunks read ahead (1: the partner wave of the SIMD covers LDS latency too; 2 measured 0.7 %
-// slower at 16,384 candidates and the same at 4,096)
-#ifndef MPCD_RW8_PF
-#define MPCD_RW8_PF 1
-#endif
-// MPCD_RW8_FLIP = 1: waves 4-7 run the two column tiles of a 128-wide layer in the opposite order to waves 0-3
-// (a phase offset between the two waves of a SIMD, which otherwise reach MFMAs, epilogue and barrier together)
-#ifndef MPCD_RW8_FLIP
-#define MPCD_RW8_FLIP 1
-#endif
-// MPCD_RW8_PRIO = 1: one static s_setprio 1 for waves 4-7 before the step loop
-#ifndef MPCD_RW8_PRIO
-#define MPCD_RW8_PRIO 0
-#endif
-
 // W = 4: one wave per SIMD (rw32 / rw16). W = 8: two per SIMD, 32 rows (rw32x8), the same sums in the same
 // order; only which wave computes a pass, and when, differs.
 // GRP: the grouped-context form (mlp_rw_grouped_kernel; see cand_span), a CTX instantiation of its own.
@@ -194,14 +95,13 @@ struct MlpRw {
     static constexpr bool IS_DDPM = SMODE == MODE_DDPM_CFG || SMODE == MODE_DDPM_XN;
     static_assert(R == 32 || R == 16, "32 or 16 rows per workgroup");
     static_assert(W == 4 || (W == 8 && R == 32), "4 waves, or 8 waves at 32 rows");
-    // the 8-wave form implements the default arms of the MPCD_RW_* switches only
-    static_assert(W == 4 || (MPCD_RW_ILV && MPCD_RW_EPI_STEPS && MPCD_RW_PKTAIL && MPCD_RW_XREG && MPCD_RW_TABLE_EARLY &&
-                             MPCD_RW_TABLE_SIDE && !MPCD_RW_EXP_NOLASTEPI && !MPCD_RW_EXP_BAR2 && !MPCD_RW_EXP_NOVM),
-                  "rw32x8 builds with the default MPCD_RW_* arms");
     static constexpr int NTH = 64 * W;      // threads
-    // W = 8 at H*d = 128 (Linear 0's 12 fragments, two update quads per lane): operands one k-chunk ahead and the next
-    // step's Linear 0 fragments issued after the update, or the kernel spills
-    static constexpr int PF8 = D0 == 128 ? 1 : MPCD_RW8_PF;
+    // k-chunks of operand fragments read ahead of the MFMAs in hidden_ilv (a ring of PF + 1). W = 4: 2. W = 8: 1, the
+    // partner wave of the SIMD covers LDS latency too (2 measured 0.7 % slower at 16,384 candidates and the same at
+    // 4,096, profiles/rw8_ab.txt; at H*d = 128 it spills)
+    static constexpr int PF = W == 8 ? 1 : 2;
+    // W = 8 at H*d = 128 (Linear 0's 12 fragments, two update quads per lane): the next step's Linear 0 fragments
+    // issued after the update, or the kernel spills
     static constexpr bool W0_LATE = D0 == 128;
     static constexpr int TPL = 8 / W;       // n-tiles of a 128-wide layer per wave
     static constexpr int NRG = RES_NL * TPL * 4;          // groups (layer, n-tile j, k-chunk) per wave
@@ -232,7 +132,8 @@ struct MlpRw {
     // a clamped copy and computes nothing.
     //
     // W = 8, hidden layers (one pass or two per wave, T = 1): N = 128: wave w -> n-tile w, both column tiles (waves
-    // 4-7 in the opposite order, MPCD_RW8_FLIP); N = 64: n-tile w & 3, column tile w >> 2; N = 32: waves 0-3 as
+    // 4-7 in the opposite order: a phase offset between the two waves of a SIMD, which otherwise reach MFMAs, epilogue
+    // and barrier together); N = 64: n-tile w & 3, column tile w >> 2; N = 32: waves 0-3 as
     // at W = 4, waves 4-7 idle. The final layer (l = 13) keeps the 4-wave mapping on waves 0-3 (n-tiles w + 4j,
     // a candidate's two CFG rows in one lane); waves 4-7 load clamped copies and skip it.
     template <int l> static constexpr bool HID = l != NLAYER - 1;
@@ -246,7 +147,7 @@ struct MlpRw {
     }
     template <int l> static MPCD_DEV int ct_of(int wave, int c)
     {
-        if constexpr (W == 8) return !SPL<l> ? (MPCD_RW8_FLIP && HID<l> ? c ^ (wave >> 2) : c) : A::N[l] == 64 ? (wave >> 2) : ((wave >> 1) & 1);
+        if constexpr (W == 8) return !SPL<l> ? (HID<l> ? c ^ (wave >> 2) : c) : A::N[l] == 64 ? (wave >> 2) : ((wave >> 1) & 1);
         return SPL<l> ? (wave >> 1) : c;
     }
     // a wave with no tile in hidden layer l (it still runs the layer's side work, loads and barriers)
@@ -261,8 +162,8 @@ struct MlpRw {
     {
         const uint64_t a = (uint64_t)wp;
         const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), (short)0,
-                                                 MPCD_RW_EXP_NOVM ? 0 : (int)(woffx<D0>(NLAYER) * 4), 0x00020000);
+        return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), (short)0, (int)(woffx<D0>(NLAYER) * 4),
+                                                 0x00020000);
     }
 
     // streamed fragments of layer l for this wave
@@ -347,87 +248,13 @@ struct MlpRw {
         }
     }
 
-    // Hidden layer l: per n-tile pass j, k-chunks in order over this wave's column tiles; pass j's epilogue
-    // (Mish, 3-way split, LDS stores of the next layer's operand planes) is issued behind pass j + 1's MFMAs.
-    // MM(j, kc, x[3], acc) -> acc: the six partial products with this wave's fragments of (j, kc).
-    template <int l, class MM>
-    static MPCD_DEV void hidden(MM mm, char *lds, int wave, int lane)
-    {
-        constexpr int K = A::K[l], N = A::N[l], KC = K / 32, NT = N / 16, T = TL<l>, NC = CL<l>, EPI = epi_of(l);
-        const int col = lane & 15, q = lane >> 4;
-        constexpr bool in_shared = l == 0 && NB == 2;  // CFG: both branches read the candidate's x
-        static_assert(T == 1 || NT % 4 == 0, "only a one-tile layer can leave a wave idle");
-        if constexpr (NT < 4 && !SPL<l>)
-            if (wave >= NT) return;  // N = 32 at 16 rows: waves 2, 3 have no tile
-        f32x4 acc[T][NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int ct = ct_of<l>(wave, c);
-            const float *init = reinterpret_cast<const float *>(
-                lds + (EPI == EPI_CMISH ? (masked_of(ct, col) ? L::TPU : L::TPC) + cond_off(l / 2) * 4
-                                        : L::BI + A::boff(l) * 4));
-#pragma unroll
-            for (int j = 0; j < T; ++j)
-                acc[j][c] = *reinterpret_cast<const f32x4 *>(init + min(nt_of<l>(wave, j), NT - 1) * 16 + 4 * q);
-        }
-        auto ldx = [&](u32x4 (&x)[NC][3], int kc) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const int ct = ct_of<l>(wave, c);
-                const int row = in_shared ? cand_of(ct, col) : ct * 16 + col;
-                load_x3(x[c], lds + L::in_off(l) + row * L::in_rs(l) + kc * 64 + 16 * (q ^ swz(row)), L::in_pl(l));
-            }
-        };
-        auto epi = [&](int j, int c) {
-            const int n = nt_of<l>(wave, j) * 16 + 4 * q;
-            f32x4 v = acc[j][c];
-            if (EPI != EPI_NONE) {
-                v.x = mish_scalar(v.x);
-                v.y = mish_scalar(v.y);
-                v.z = mish_scalar(v.z);
-                v.w = mish_scalar(v.w);
-            }
-            u32x2 p0, p1, p2;
-            split3(v, p0, p1, p2);
-            const int ro = ct_of<l>(wave, c) * 16 + col;
-            char *o = lds + L::out_off(l) + ro * L::out_rs(l) + st_off(n, q, ro);
-            *reinterpret_cast<u32x2 *>(o) = p0;
-            *reinterpret_cast<u32x2 *>(o + L::out_pl(l)) = p1;
-            *reinterpret_cast<u32x2 *>(o + 2 * L::out_pl(l)) = p2;
-        };
-#pragma unroll
-        for (int j = 0; j < T; ++j) {
-            u32x4 xc[NC][3], xn[NC][3];
-            ldx(xc, 0);
-#pragma unroll
-            for (int kc = 0; kc < KC; ++kc) {
-                if (kc + 1 < KC) ldx(xn, kc + 1);
-#pragma unroll
-                for (int c = 0; c < NC; ++c) acc[j][c] = mm(j, kc, xc[c], acc[j][c]);
-                if (j > 0 && kc == 0) {
-                    // the previous pass's epilogue in this pass's MFMA shadow
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) epi(j - 1, c);
-                }
-                if (kc + 1 < KC)
-#pragma unroll
-                    for (int c = 0; c < NC; ++c)
-#pragma unroll
-                        for (int pl = 0; pl < 3; ++pl) xc[c][pl] = xn[c][pl];
-            }
-            if (j == T - 1)
-#pragma unroll
-                for (int c = 0; c < NC; ++c) epi(j, c);
-        }
-    }
-
-    // Pipelined form of hidden(). MM1(j, kc, m, x[3], acc) -> acc: partial product m (0..5, smallest first:
-    // the mfma_x3 order) of k-chunk kc of n-tile j. Same products in the same order as hidden(): bit-identical.
-    // free MFMA slots of layer l's pipeline (the first 5 of every pass but the first carry epilogue units)
-    template <int l>
-    static constexpr int FREE = TL<l> * CL<l> * (A::K[l] / 32) * 6 - 5 * (TL<l> * CL<l> - 1);
-
-    // SIDE(k), k < NS: side work, one item per free slot in order; items beyond the free slots (and all of them
+    // Hidden layer l as a pipeline of passes (one n-tile x one column tile: a chain of 6 KC MFMAs, k-chunks in order):
+    // the previous pass's epilogue (4 Mish, the 3-way split, the LDS stores of the next layer's operand planes) is
+    // issued one micro-step after each of this pass's first MFMAs (pinned with sched_barrier: a bf16 MFMA leaves the
+    // SIMD's vector issue free for 8 of its 16 cycles), the next activation fragments are read PF k-chunks ahead.
+    // MM1(j, kc, m, x[3], acc) -> acc: partial product m (0..5, smallest first: the mfma_x3 order) of k-chunk kc of
+    // n-tile j with this wave's fragments.
+    // SIDE(k), k < NS: side work, one item per MFMA slot in order; items beyond the layer's slots (and all of them
     // on a wave with no tile) run after the layer's MFMAs
     template <int l, int NS, class MM1, class SIDE>
     static MPCD_DEV void hidden_ilv(MM1 mm1, SIDE side, char *lds, int wave, int lane)
@@ -463,29 +290,11 @@ struct MlpRw {
             const int row = in_shared ? cand_of(ct, col) : ct * 16 + col;
             load_x3(x, lds + L::in_off(l) + row * L::in_rs(l) + kc * 64 + 16 * (q ^ swz(row)), L::in_pl(l));
         };
-        // epilogue of pass p in five units: Mish of element 0..3, then the split + the three plane stores
-        auto epi_unit = [&](int u, f32x4 &v, int p) {
-            if (u < 4) {
-                if (EPI != EPI_NONE) v[u] = mish_scalar(v[u]);
-                return;
-            }
-            const int n = nt_of<l>(wave, jp(p)) * 16 + 4 * q;
-            u32x2 p0, p1, p2;
-            split3(v, p0, p1, p2);
-            const int ro = ct_of<l>(wave, cp(p)) * 16 + col;
-            char *o = lds + L::out_off(l) + ro * L::out_rs(l) + st_off(n, q, ro);
-            *reinterpret_cast<u32x2 *>(o) = p0;
-            *reinterpret_cast<u32x2 *>(o + L::out_pl(l)) = p1;
-            *reinterpret_cast<u32x2 *>(o + 2 * L::out_pl(l)) = p2;
-        };
-        // operand fragments read PF k-chunks ahead (a ring of PF + 1)
-        constexpr int PF = W == 8 ? PF8 : MPCD_RW_PF;
-        u32x4 xb[PF + 1][3];
+        u32x4 xb[PF + 1][3];  // operand fragments read PF k-chunks ahead
 #pragma unroll
         for (int i = 0; i < PF; ++i)
             if (i < NI) ldx(xb[i], i);
         f32x4 acc = init_of(0), nxt = acc, ev = acc;
-#if MPCD_RW_EPI_STEPS
         // The previous pass's epilogue as NSTEP micro-steps of one or two VALU instructions, one after each MFMA:
         // a bf16 MFMA leaves the SIMD's vector issue free for 8 of its 16 cycles, i.e. about two VALU ops. Stage
         // by stage over the four values (the dependent ops of one value 4 slots apart), the exact operations of
@@ -546,7 +355,9 @@ struct MlpRw {
             ev = acc;
             acc = nxt;
         }
-        // the last pass's epilogue, exposed (MPCD_RW_PKTAIL: packed, two values per instruction; epi_step's operations)
+        // The last pass's epilogue, exposed (nothing left to hide it under): two values per packed instruction (v_pk_mul /
+        // v_pk_add / v_pk_fma_f32; epi_step's operations, the same roundings) instead of the fenced scalar micro-steps:
+        // loop VALU 1,631 -> 1,459 per wave-step, kernel -0.5 % (profiles/r6_mlp_tuning_ab.txt)
         auto epi_tail = [&](int p) {
             f32x2 a = {ev[0], ev[1]}, b = {ev[2], ev[3]};
             if constexpr (EPI != EPI_NONE) {
@@ -573,64 +384,22 @@ struct MlpRw {
             b = b - f32x2{bf_lo(q1.y), bf_hi(q1.y)};
             *reinterpret_cast<u32x2 *>(o + 2 * L::out_pl(l)) = u32x2{pk_bf16(a[0], a[1]), pk_bf16(b[0], b[1])};
         };
-        // MPCD_RW_EXP_NOLASTEPI (timing experiment only, wrong results): drop the exposed last-pass epilogue of
-        // the multi-pass layers - the bound on what deferring it into the next layer could gain
-        if (!(MPCD_RW_EXP_NOLASTEPI && NP >= 2)) {
-            if constexpr (MPCD_RW_PKTAIL) {
-                epi_tail(NP - 1);
-            } else {
-#pragma unroll
-                for (int u = 0; u < NSTEP; ++u) epi_step(u, NP - 1);
-            }
-        }
+        epi_tail(NP - 1);
 #pragma unroll
         for (int k = NI * 6; k < NS; ++k) side(k);
-#else
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            if (p + 1 < NP) nxt = init_of(p + 1);
-#pragma unroll
-            for (int kc = 0; kc < KC; ++kc) {
-                const int i = p * KC + kc;
-                if (i + PF < NI) ldx(xb[(i + PF) % (PF + 1)], i + PF);
-#pragma unroll
-                for (int m = 0; m < 6; ++m) {
-                    acc = mm1(jp(p), kc, m, xb[i % (PF + 1)], acc);
-                    const int u = kc * 6 + m;
-                    if (p > 0 && u < 5) epi_unit(u, ev, p - 1);
-                    else if (i * 6 + m - 5 * p < NS) side(i * 6 + m - 5 * p);  // the k-th free slot
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            ev = acc;
-            acc = nxt;
-        }
-#pragma unroll
-        for (int u = 0; u < 5; ++u) epi_unit(u, ev, NP - 1);
-#pragma unroll
-        for (int k = FREE<l>; k < NS; ++k) side(k);
-#endif
     }
 
     template <int l, int NS = 0, class SIDE>
     static MPCD_DEV void layer(const WS<l> &w, SIDE side, char *lds, int wave, int lane)
     {
-#if MPCD_RW_ILV
         hidden_ilv<l, NS>(
             [&](int j, int kc, int m, const u32x4 (&x)[3], f32x4 acc) { return mfma_bf(w.v[j][kc][wpl(m)], x[xpl(m)], acc); },
             side, lds, wave, lane);
-#else
-        hidden<l>([&](int j, int kc, const u32x4 (&x)[3], f32x4 acc) { return mfma_x3(w.v[j][kc], x, acc); }, lds, wave,
-                  lane);
-#pragma unroll
-        for (int k = 0; k < NS; ++k) side(k);
-#endif
     }
 
     template <int li, int NS = 0, class SIDE>
     static MPCD_DEV void layer_res(const Res &r, const Tail &t, SIDE side, char *lds, int wave, int lane)
     {
-#if MPCD_RW_ILV
         hidden_ilv<RES_L0 + li, NS>(
             [&](int j, int kc, int m, const u32x4 (&x)[3], f32x4 acc) {
                 const int g = (li * TPL + j) * 4 + kc;
@@ -645,17 +414,6 @@ struct MlpRw {
                 return mfma_agpr1<false, false>(r.a[g][wpl(m)], x[xpl(m)], acc);
             },
             side, lds, wave, lane);
-#else
-        hidden<RES_L0 + li>(
-            [&](int j, int kc, const u32x4 (&x)[3], f32x4 acc) {
-                const int g = (li * TPL + j) * 4 + kc;
-                if (g < NAG) return mfma_x3_agpr(r.a[g][0], r.a[g][1], r.a[g][2], x, acc);
-                return mfma_x3(t.v[g - NAG], x, acc);
-            },
-            lds, wave, lane);
-#pragma unroll
-        for (int k = 0; k < NS; ++k) side(k);
-#endif
     }
 
     // x (4 features) -> fp32 row in XB and the three bf16 planes layer 0 reads
@@ -692,24 +450,14 @@ struct MlpRw {
     static constexpr int NZT = TL<13>;
 
     // final Linear (32 -> D0) + the denoise update (reference op order, mlp_x3.hip final_and_update)
-#ifdef MPCD_PROF_LAYERS
-#define MPCD_FINAL_PROF , uint64_t(&tacc)[32]
-#define MPCD_FINAL_MARK(k, dep)                                                                                      \
-    do {                                                                                                             \
-        asm volatile("" ::"v"(dep) : "memory");                                                                     \
-        const uint64_t t_ = __builtin_readcyclecounter();                                                            \
-        tacc[k] += t_ - tmark;                                                                                       \
-        tmark = t_;                                                                                                  \
-    } while (0)
-#else
-#define MPCD_FINAL_PROF
-#define MPCD_FINAL_MARK(k, dep)
-#endif
-    // x_t of the update's (n-tile j, column group g) quads, when MPCD_RW_XREG keeps it in registers
+    // x_t of the update's (n-tile j, column group g) quads, when XREG keeps it in registers
     static constexpr int XG = NB == 2 ? 1 : NCT;
-    // x_t in registers (MPCD_RW_XREG); the 8-wave form only where that is one quad per lane, else the fp32 copy in
-    // LDS (the same values: 256 registers per wave do not hold 2-4 quads beside the final layer's operands)
-    static constexpr bool XREG = MPCD_RW_XREG && (W == 4 || (D0 / 16 + 3) / 4 * XG == 1);
+    // XREG: each lane keeps its x_t quads in registers across steps (the fp32 copy in LDS goes), and the update's x-only
+    // products (a x, c2 x, std z) are formed while the final layer's operand reads are in flight. With the cond tables
+    // as Linear 12's side work: kernel 1.098 -> 1.090 ms at cfg2 (profiles/r6_mlp_tuning_ab.txt, 3 repeats). The
+    // 8-wave form only where that is one quad per lane, else the fp32 copy in LDS (the same values: 256 registers per
+    // wave do not hold 2-4 quads beside the final layer's operands)
+    static constexpr bool XREG = W == 4 || (D0 / 16 + 3) / 4 * XG == 1;
     static MPCD_DEV bool x_lane(int j, int wave, int col)
     {
         return upd_wave(wave) && (D0 / 16 % 4 == 0 || wave + 4 * j < D0 / 16) && !(R == 16 && NB == 2 && col >= 8);
@@ -729,11 +477,9 @@ struct MlpRw {
 
     static MPCD_DEV void final_and_update(const FW &f, char *lds, const MlpSampleArgs &p, const StepPlan &sp, int s,
                                           int64_t cand0, int n_cand, const f32x4 (&nz)[NZT][NB],
-                                          uint32_t (&am)[2], f32x4 (&xr)[NZT][XG], int wave, int lane MPCD_FINAL_PROF)
+                                          uint32_t (&am)[2], f32x4 (&xr)[NZT][XG], int wave, int lane, ProfAcc &tacc)
     {
-#ifdef MPCD_PROF_LAYERS
-        uint64_t tmark = __builtin_readcyclecounter();
-#endif
+        uint64_t tmark = prof_now();
         if (!upd_wave(wave)) return;  // W = 8: waves 0-3 run the final layer (no barrier, no global load inside)
         constexpr int T = NZT, NT = D0 / 16;
         const int col = lane & 15, q = lane >> 4;
@@ -775,12 +521,7 @@ struct MlpRw {
 #pragma unroll
             for (int j = 0; j < T; ++j)
                 if (NT % 4 == 0 || wave + 4 * j < NT) acc[j][c] = mfma_x3(f.v[j][0], xf[c], acc[j][c]);
-        MPCD_FINAL_MARK(28, acc[0][1]);  // experiment build: the final layer's operand reads and MFMAs
-#ifdef MPCD_PROF_FINAL_MFMA_ONLY
-        // timing experiment (wrong results): the final layer's MFMAs only, no update
-        if (acc[0][0][0] == 12345.f && acc[0][1][1] == 54321.f) am[0] = 1u;
-        return;
-#endif
+        prof_mark(tacc, tmark, 28, acc[0][1]);  // profile: the final layer's operand reads and MFMAs ("-" row)
         if (R == 16 && NB == 2) {
             // column c holds candidate c & 7's context row (c < 8) or masked row (c >= 8): bring the masked
             // row's eps next to the context row's (DPP row_ror:8 swaps the two halves of each 16-lane row)
@@ -868,7 +609,7 @@ struct MlpRw {
                 }
             }
         }
-        MPCD_FINAL_MARK(29, am[0]);  // experiment build: the update, the stores
+        prof_mark(tacc, tmark, 29, am[0]);  // profile: the update, the stores
     }
 
     // noise of step s (slice s+1) for this lane's quads, fetched one step ahead of use
@@ -988,11 +729,6 @@ struct MlpRw {
         float *bic = reinterpret_cast<float *>(lds + L::BIC);
         float *cps = reinterpret_cast<float *>(lds + L::CPS);
 
-#if MPCD_RW_EXP_NOLASTEPI
-        // the timing experiment leaves output tiles unwritten: start from a zeroed LDS so they read finite values
-        for (int i = threadIdx.x; i < L::total / 16; i += NTH) reinterpret_cast<u32x4 *>(lds)[i] = u32x4{0u, 0u, 0u, 0u};
-        lds_barrier();
-#endif
         Res res;
         load_res(res, wp, wave, lane);
         for (int l = 0; l < NLAYER; ++l)
@@ -1033,32 +769,22 @@ struct MlpRw {
         if constexpr (W == 4) fetch_noise(nz, p, sp, 0, cand0, n_cand, wave, lane);
         const int tpi = threadIdx.x < COND_TOTAL / 4 ? (int)threadIdx.x : threadIdx.x < COND_TOTAL / 2 ? (int)threadIdx.x - COND_TOTAL / 4 : 0;
         f32x4 tpre = reinterpret_cast<const f32x4 *>(p.tproj)[tpi];
-#ifdef MPCD_PROF_LAYERS
-        // experiment build only: per-wave shader-clock cycles of each segment (work, then barrier wait), the
-        // dump format of mlp_x3.hip (tools/layer_prof.py)
-        uint64_t tacc[2 * 16] = {};
-        const uint64_t rt0 = __builtin_amdgcn_s_memrealtime();
-        uint64_t tprev = __builtin_readcyclecounter();
+        // MPCD_PROF_LAYERS build (mlp_common.h): cycles of each barrier-to-barrier segment (tools/layer_prof.py)
+        ProfAcc tacc = {};
+        const uint64_t rt0 = prof_realtime();
+        uint64_t tprev = prof_now();
         const uint64_t ct0 = tprev;
-        int bk = 0;
+#ifdef MPCD_PROF_LAYERS
+        int bk = 0;  // the segment: 14 barriers per denoise step
         auto bar = [&] {
-            uint64_t t = __builtin_readcyclecounter();
-            tacc[2 * bk] += t - tprev;
-            lds_barrier();
-            tprev = __builtin_readcyclecounter();
-            tacc[2 * bk + 1] += tprev - t;
+            prof_barrier(tacc, tprev, bk);
             bk = bk == 13 ? 0 : bk + 1;
         };
 #else
-#if MPCD_RW_EXP_BAR2
-        auto bar = [] { lds_barrier(); lds_barrier(); };  // timing experiment: the cost of one more barrier per layer
-#else
+        // No capture here and no mark in noise_next below in the product build: the empty forms of both in the lambdas'
+        // closures changed the order of two scalar copies in three rw32 kernels (profiles/mlp_switch_cleanup_isa.txt)
         auto bar = [] { lds_barrier(); };
 #endif
-#endif
-
-        if constexpr (W == 8 && MPCD_RW8_PRIO)
-            if (wave >= 4) __builtin_amdgcn_s_setprio(1);
         int lane_l = lane;
         for (int s = 0; s < p.n_steps; ++s) {
             // launder the weight base: stops LICM hoisting the streamed layers' loads out of the loop
@@ -1078,7 +804,9 @@ struct MlpRw {
             WS<2> w2;
             load_ws<2>(w2, ws, wave, lane16);
             bar();
-            // this step's time projections + cond biases (+ shared context part) -> TPU / TPC: one f32x4 per thread
+            // A step's time projections + cond biases (+ shared context part) -> TPU / TPC: one f32x4 per thread. The
+            // first step's here; step s + 1's are written after Linear 11 (the last layer that reads step s's) and not at
+            // the step's start, where their LDS round trip delayed Linear 0's first operand reads
             auto table = [&] {
                 if (threadIdx.x < COND_TOTAL / 2) {
                     const bool ctx_half = threadIdx.x >= COND_TOTAL / 4;
@@ -1088,7 +816,7 @@ struct MlpRw {
                     reinterpret_cast<f32x4 *>(lds + (ctx_half ? L::TPC : L::TPU))[k] = u;
                 }
             };
-            if (!MPCD_RW_TABLE_EARLY || s == 0) {
+            if (s == 0) {
                 table();
                 tpre = reinterpret_cast<const f32x4 *>(p.tproj + (size_t)(s + 1 < p.n_steps ? s + 1 : s) * COND_TOTAL)[tpi];
             }
@@ -1125,12 +853,11 @@ struct MlpRw {
                     ph_take(nz, ph, sp, cand0, n_cand, p, wave, lane);
                 } else if (s + 1 < p.n_steps) {
 #ifdef MPCD_PROF_LAYERS
-                    const uint64_t tn0 = __builtin_readcyclecounter();
+                    const uint64_t tn0 = prof_now();
 #endif
                     fetch_noise(nz, p, sp, s + 1, cand0, n_cand, wave, lane);
 #ifdef MPCD_PROF_LAYERS
-                    asm volatile("" ::: "memory");
-                    tacc[31] += __builtin_readcyclecounter() - tn0;  // "tail" row, wait column: the noise draws
+                    prof_mark(tacc, tn0, 31);  // the noise draws ("tail" row, wait column)
 #endif
                 }
             };
@@ -1170,7 +897,9 @@ struct MlpRw {
                 load_ws<10>(w10, ws, wave, lane16);
                 bar();
             } else {
-                constexpr int W8A = MPCD_RW_W8_SPLIT ? NFRAG<8> / 2 : 0;  // Linear 8 fragments issued during Linear 5
+                // Linear 8's streamed fragments issued half in Linear 5's MFMA slots, half in Linear 6's (all 24 in
+                // Linear 6's measured slower, profiles/r6_mlp_tuning_ab.txt)
+                constexpr int W8A = NFRAG<8> / 2;
                 layer_res<0, W8A>(res, tail, [&](int k) { load_ws1<8>(w8, ws, wave, lane16, k); }, lds, wave, lane);
                 bar();
                 layer_res<1, NFRAG<8> - W8A>(res, tail, [&](int k) { load_ws1<8>(w8, ws, wave, lane16, W8A + k); }, lds, wave,
@@ -1220,7 +949,7 @@ struct MlpRw {
             bar();
             layer<11>(w11, none, lds, wave, lane);
             bar();
-            if constexpr (MPCD_RW_TABLE_EARLY && MPCD_RW_TABLE_SIDE) {
+            {
                 // step s + 1's tables as Linear 12's side work: both reads in its first MFMA slot, the add and the
                 // write in its last (Linear 11 read step s's tables last; the barrier above orders them)
                 constexpr int NS12 = TL<12> * CL<12> * (A::K[12] / 32) * 6;
@@ -1238,12 +967,6 @@ struct MlpRw {
                 }, lds, wave, lane);
                 if (s + 1 < p.n_steps)
                     tpre = reinterpret_cast<const f32x4 *>(p.tproj + (size_t)(s + 2 < p.n_steps ? s + 2 : s + 1) * COND_TOTAL)[tpi];
-            } else {
-                if (MPCD_RW_TABLE_EARLY && s + 1 < p.n_steps) {  // step s + 1's tables (Linear 11 read step s's last)
-                    table();
-                    tpre = reinterpret_cast<const f32x4 *>(p.tproj + (size_t)(s + 2 < p.n_steps ? s + 2 : s + 1) * COND_TOTAL)[tpi];
-                }
-                layer<12>(w12, none, lds, wave, lane);
             }
             if constexpr (W == 8 && !W0_LATE) load_ws<0>(w0, ws, wave, lane16);  // next step's layer 0, behind the final layer
             bar();
@@ -1255,29 +978,10 @@ struct MlpRw {
                     if (IS_DDPM && wave < 4) nzc[j][0] = *reinterpret_cast<const f32x4 *>(lds + L::C0 + ((j * 4 + wave) * 64 + lane) * 16);
                 }
             }
-#ifdef MPCD_PROF_LAYERS
-            final_and_update(w13, lds, p, cur, s, cand0, n_cand, nzc, am, xr, wave, lane, tacc);  // "-" row: MFMAs / update
-#else
-            final_and_update(w13, lds, p, cur, s, cand0, n_cand, nzc, am, xr, wave, lane);
-#endif
+            final_and_update(w13, lds, p, cur, s, cand0, n_cand, nzc, am, xr, wave, lane, tacc);
             if constexpr (W == 8 && W0_LATE) load_ws<0>(w0, ws, wave, lane16);  // H*d = 128: after the update's registers
         }
-#ifdef MPCD_PROF_LAYERS
-        {
-            const uint64_t t = __builtin_readcyclecounter();
-            tacc[2 * 15] += t - tprev;
-            if (p.dbg && blockIdx.x < 32 / W && lane == 0)  // 32 wave slots
-                for (int i = 0; i < 32; ++i) p.dbg[(blockIdx.x * W + (threadIdx.x >> 6)) * 32 + i] = (float)tacc[i];
-            if (p.dbg && threadIdx.x == 0) {  // per-block loop start / end (memrealtime, low 32 bits)
-                p.dbg[4096 + blockIdx.x * 2] = __builtin_bit_cast(float, (uint32_t)rt0);
-                p.dbg[4096 + blockIdx.x * 2 + 1] = __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_s_memrealtime());
-            }
-            if (p.dbg && blockIdx.x < 8 && threadIdx.x == 0) {  // shader clock = d(memtime) / d(memrealtime) x 100 MHz
-                p.dbg[8 * 4 * 32 + blockIdx.x * 2] = (float)(t - ct0);
-                p.dbg[8 * 4 * 32 + blockIdx.x * 2 + 1] = (float)(__builtin_amdgcn_s_memrealtime() - rt0);
-            }
-        }
-#endif
+        MPCD_PROF_DUMP(W, threadIdx.x >> 6, lane);
         if (SMODE != MODE_EPS && SMODE != MODE_EPS1 && p.chain_absmax) {
             const int col = lane & 15;
             store_chain_absmax<CPW, NTH>(reinterpret_cast<uint32_t *>(lds + L::AMX), am, col,
@@ -1320,45 +1024,11 @@ hipError_t launch_rw_r(const MlpSampleArgs &a, hipStream_t stream)
     }
 }
 
-// the 8-wave form exists for the default arms of the MPCD_RW_* switches (an experiment build of another arm has none)
-constexpr bool RW8_BUILT = MPCD_RW_ILV && MPCD_RW_EPI_STEPS && MPCD_RW_PKTAIL && MPCD_RW_XREG && MPCD_RW_TABLE_EARLY &&
-                           MPCD_RW_TABLE_SIDE && !MPCD_RW_EXP_NOLASTEPI && !MPCD_RW_EXP_BAR2 && !MPCD_RW_EXP_NOVM;
-
 template <int D0, int SMODE, bool CTX, bool GRP = false>
 hipError_t launch_rw(const MlpSampleArgs &a, int rows, int waves, hipStream_t stream)
 {
-    if (waves == 8) {
-        if constexpr (RW8_BUILT) return rows == 32 ? launch_rw_r<D0, SMODE, CTX, 32, 8, GRP>(a, stream) : hipErrorInvalidValue;
-        else return hipErrorInvalidValue;
-    }
+    if (waves == 8) return rows == 32 ? launch_rw_r<D0, SMODE, CTX, 32, 8, GRP>(a, stream) : hipErrorInvalidValue;
     return rows == 16 ? launch_rw_r<D0, SMODE, CTX, 16, 4, GRP>(a, stream) : launch_rw_r<D0, SMODE, CTX, 32, 4, GRP>(a, stream);
-}
-
-template <int D0>
-hipError_t launch_rw_d0(const MlpSampleArgs &a, int rows, int waves, hipStream_t stream)
-{
-    const bool ctx = a.cproj != nullptr;
-    if (a.group > 0) {  // grouped contexts: the samplers (mpcd_sample_grouped), with a context
-        if (!ctx) return hipErrorInvalidValue;
-        switch (a.mode) {
-        case MODE_DDPM_CFG:
-            return a.noise ? launch_rw<D0, MODE_DDPM_XN, true, true>(a, rows, waves, stream)
-                           : launch_rw<D0, MODE_DDPM_CFG, true, true>(a, rows, waves, stream);
-        case MODE_DDIM_CFG: return launch_rw<D0, MODE_DDIM_CFG, true, true>(a, rows, waves, stream);
-        case MODE_DDIM: return launch_rw<D0, MODE_DDIM, true, true>(a, rows, waves, stream);
-        }
-        return hipErrorInvalidValue;
-    }
-    switch (a.mode) {
-    case MODE_DDPM_CFG:
-        if (a.noise) return ctx ? launch_rw<D0, MODE_DDPM_XN, true>(a, rows, waves, stream) : launch_rw<D0, MODE_DDPM_XN, false>(a, rows, waves, stream);
-        return ctx ? launch_rw<D0, MODE_DDPM_CFG, true>(a, rows, waves, stream) : launch_rw<D0, MODE_DDPM_CFG, false>(a, rows, waves, stream);
-    case MODE_DDIM_CFG: return ctx ? launch_rw<D0, MODE_DDIM_CFG, true>(a, rows, waves, stream) : launch_rw<D0, MODE_DDIM_CFG, false>(a, rows, waves, stream);
-    case MODE_DDIM: return ctx ? launch_rw<D0, MODE_DDIM, true>(a, rows, waves, stream) : launch_rw<D0, MODE_DDIM, false>(a, rows, waves, stream);
-    case MODE_EPS: return ctx ? launch_rw<D0, MODE_EPS, true>(a, rows, waves, stream) : launch_rw<D0, MODE_EPS, false>(a, rows, waves, stream);
-    case MODE_EPS1: return ctx ? launch_rw<D0, MODE_EPS1, true>(a, rows, waves, stream) : launch_rw<D0, MODE_EPS1, false>(a, rows, waves, stream);
-    }
-    return hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -1366,10 +1036,6 @@ hipError_t launch_rw_d0(const MlpSampleArgs &a, int rows, int waves, hipStream_t
 // rows: 32 or 16 per workgroup, waves: 4, or 8 at 32 rows (mlp_x3.hip picks, as for its own layouts)
 hipError_t launch_mlp_rw(int d0, int rows, int waves, const MlpSampleArgs &a, hipStream_t stream)
 {
-    switch (d0) {
-    case 32: return launch_rw_d0<32>(a, rows, waves, stream);
-    case 64: return launch_rw_d0<64>(a, rows, waves, stream);
-    case 128: return launch_rw_d0<128>(a, rows, waves, stream);
-    }
-    return hipErrorInvalidValue;
+    return sampler_dispatch(d0, a.mode, a.noise != nullptr, a.cproj != nullptr, a.group > 0,
+                            [&](auto D0, auto SMODE, auto CTX, auto GRP) { return launch_rw<D0, SMODE, CTX, GRP>(a, rows, waves, stream); });
 }

@@ -20,9 +20,6 @@
 
 #include "internal.h"
 #include "mlp_common.h"
-#if !defined(MPCD_VARIANT) && (defined(MPCD_DIAG_NOMFMA) || defined(MPCD_DIAG_NOMISH))
-#error "wrong-result timing diagnostics build only as an experiment variant (build.py variant: -DMPCD_VARIANT)"
-#endif
 
 namespace {
 using namespace mlpc;
@@ -154,15 +151,6 @@ MPCD_DEV void hidden_layer(const WFrag<K, N, MODE> &f, const float *init, const 
     for (int j = 0; j < T; ++j) i4[j] = *reinterpret_cast<const f32x4 *>(init + ntile_of<K, N, MODE>(wave, j) * 16 + 4 * q);
 
     f32x4 acc[G][2];
-#ifdef MPCD_DIAG_NOMFMA
-    // timing diagnostic only (wrong results): no MFMAs, activations folded in so loads stay live
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        acc[g][0] = i4[BYJ ? g : 0] + a[BYJ ? 0 : g][0];
-        acc[g][1] = a[BYJ ? 1 % NCT : g][KB - 1] + f.v[BYJ ? g : 0][KB - 1];
-    }
-    if (false)
-#endif
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         if (BYJ) {
@@ -199,14 +187,12 @@ MPCD_DEV void hidden_layer(const WFrag<K, N, MODE> &f, const float *init, const 
                 v = v + cpv;
             }
         }
-#ifndef MPCD_DIAG_NOMISH
         if (EPI != EPI_NONE) {
             v.x = mish_scalar(v.x);
             v.y = mish_scalar(v.y);
             v.z = mish_scalar(v.z);
             v.w = mish_scalar(v.w);
         }
-#endif
         *reinterpret_cast<f32x4 *>(out + (size_t)(ct * 16 + col) * out_stride + n) = v;
     }
 }
@@ -393,22 +379,12 @@ struct MlpKernel {
         const int tpi = threadIdx.x < COND_TOTAL / 4 ? (int)threadIdx.x : 0;
         f32x4 tpre = reinterpret_cast<const f32x4 *>(p.tproj)[tpi];
 
-#ifdef MPCD_PROF_LAYERS
-        // experiment build only: per-wave shader-clock cycles of each layer (work, then barrier wait)
-        uint64_t tacc[2 * 16] = {};
-        const uint64_t rt0 = __builtin_amdgcn_s_memrealtime();
-        uint64_t tprev = __builtin_readcyclecounter();
+        // MPCD_PROF_LAYERS build (mlp_common.h): cycles of each layer (work, then barrier wait)
+        ProfAcc tacc = {};
+        const uint64_t rt0 = prof_realtime();
+        uint64_t tprev = prof_now();
         const uint64_t ct0 = tprev;
-        auto bar = [&](int k) {
-            uint64_t t = __builtin_readcyclecounter();
-            tacc[2 * k] += t - tprev;
-            lds_barrier();
-            tprev = __builtin_readcyclecounter();
-            tacc[2 * k + 1] += tprev - t;
-        };
-#else
-        auto bar = [](int) { lds_barrier(); };
-#endif
+        auto bar = [&](int k) { prof_barrier(tacc, tprev, k); };
         for (int s = 0; s < p.n_steps; ++s) {
             // Launder the weight base every step: the weights are loop-invariant, and without this
             // LICM hoists all 14 layers' loads out of the step loop (hundreds of live VGPRs -> spills).
@@ -506,22 +482,7 @@ struct MlpKernel {
             store_chain_absmax<CPW, THREADS>(reinterpret_cast<uint32_t *>(lds + L::AMX), am, col, NB == 2 ? -1 : 16 + col,
                                              true, p.chain_absmax, cand0, p.batch);
         }
-#ifdef MPCD_PROF_LAYERS
-        {
-            const uint64_t t = __builtin_readcyclecounter();
-            tacc[2 * 15] += t - tprev;
-            if (p.dbg && blockIdx.x < 8 && lane == 0)
-                for (int i = 0; i < 32; ++i) p.dbg[(blockIdx.x * 4 + wave) * 32 + i] = (float)tacc[i];
-            if (p.dbg && threadIdx.x == 0) {  // per-block loop start / end (memrealtime, low 32 bits)
-                p.dbg[4096 + blockIdx.x * 2] = __builtin_bit_cast(float, (uint32_t)rt0);
-                p.dbg[4096 + blockIdx.x * 2 + 1] = __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_s_memrealtime());
-            }
-            if (p.dbg && blockIdx.x < 8 && threadIdx.x == 0) {  // shader clock = d(memtime) / d(memrealtime) x 100 MHz
-                p.dbg[8 * 4 * 32 + blockIdx.x * 2] = (float)(t - ct0);
-                p.dbg[8 * 4 * 32 + blockIdx.x * 2 + 1] = (float)(__builtin_amdgcn_s_memrealtime() - rt0);
-            }
-        }
-#endif
+        MPCD_PROF_DUMP(THREADS / 64, wave, lane);
     }
 };
 
@@ -542,22 +503,6 @@ hipError_t launch_impl(const MlpSampleArgs &a, hipStream_t stream)
     return launch_sampler_kernel(mlp_sample_kernel<D0, SMODE, CTX>, dim3((unsigned)blocks), dim3(THREADS), lds_bytes, stream, a);
 }
 
-template <int D0>
-hipError_t launch_d0(const MlpSampleArgs &a, hipStream_t stream)
-{
-    const bool ctx = a.cproj != nullptr;
-    switch (a.mode) {
-    case MODE_DDPM_CFG:
-        if (a.noise) return ctx ? launch_impl<D0, MODE_DDPM_XN, true>(a, stream) : launch_impl<D0, MODE_DDPM_XN, false>(a, stream);
-        return ctx ? launch_impl<D0, MODE_DDPM_CFG, true>(a, stream) : launch_impl<D0, MODE_DDPM_CFG, false>(a, stream);
-    case MODE_DDIM_CFG: return ctx ? launch_impl<D0, MODE_DDIM_CFG, true>(a, stream) : launch_impl<D0, MODE_DDIM_CFG, false>(a, stream);
-    case MODE_DDIM: return ctx ? launch_impl<D0, MODE_DDIM, true>(a, stream) : launch_impl<D0, MODE_DDIM, false>(a, stream);
-    case MODE_EPS: return ctx ? launch_impl<D0, MODE_EPS, true>(a, stream) : launch_impl<D0, MODE_EPS, false>(a, stream);
-    case MODE_EPS1: return ctx ? launch_impl<D0, MODE_EPS1, true>(a, stream) : launch_impl<D0, MODE_EPS1, false>(a, stream);
-    }
-    return hipErrorInvalidValue;
-}
-
 }  // namespace
 
 int mlp_packed_floats(int d0)
@@ -574,11 +519,9 @@ int mlp_packed_floats(int d0)
 // packed[((nt*KB + kb)*64 + lane)*4 + s] = W[nt*16 + (lane&15)][kb*16 + 4*(lane>>4) + s], then bias.
 void mlp_pack_weights(int d0, const float *const *lin_w, const float *const *lin_b, float *out)
 {
-    const int Ks[NLAYER] = {d0, 32, 32, 64, 64, 128, 128, 128, 256, 64, 128, 32, 32, 32};
-    const int Ns[NLAYER] = {32, 32, 64, 64, 128, 128, 128, 128, 64, 64, 32, 32, 32, d0};
     size_t o = 0;
     for (int l = 0; l < NLAYER; ++l) {
-        const int K = Ks[l], N = Ns[l], KB = K / 16, NT = N / 16;
+        const int K = layer_k(d0, l), N = layer_n(d0, l), KB = K / 16, NT = N / 16;
         for (int nt = 0; nt < NT; ++nt)
             for (int kb = 0; kb < KB; ++kb)
                 for (int lane = 0; lane < 64; ++lane)
@@ -594,10 +537,7 @@ void mlp_pack_weights(int d0, const float *const *lin_w, const float *const *lin
 hipError_t launch_mlp_sampler(int d0, int nb, const MlpSampleArgs &a, hipStream_t stream)
 {
     if ((nb == 1) != (a.mode == MODE_DDIM || a.mode == MODE_EPS1)) return hipErrorInvalidValue;
-    switch (d0) {
-    case 32: return launch_d0<32>(a, stream);
-    case 64: return launch_d0<64>(a, stream);
-    case 128: return launch_d0<128>(a, stream);
-    }
-    return hipErrorInvalidValue;
+    // no grouped form: a grouped call reaches this kernel with one projection row per candidate
+    return sampler_dispatch(d0, a.mode, a.noise != nullptr, a.cproj != nullptr, false,
+                            [&](auto D0, auto SMODE, auto CTX, auto) { return launch_impl<D0, SMODE, CTX>(a, stream); });
 }

@@ -20,42 +20,11 @@ constexpr int ROWS_MAX = 32;
 // one wave's Mish / split VALU runs under the other's MFMAs. Hidden layers then map as PAIR8
 // (N = 128: wave w -> n-tile w, both column tiles) or WIDE8 (N <= 64: wave w -> column tile w >> 2,
 // n-tiles (w & 3) + 4j); the final layer, which pairs a candidate's two CFG rows, runs on waves 0-3
-// in the PAIRED form. WAVES = 4 keeps the one-wave-per-SIMD schedule (hidden()).
-#ifndef MPCD_X3_WAVES
-#define MPCD_X3_WAVES 8
-#endif
-// MPCD_X3_ILV = 1: the N = 128 layers overlap one column tile's epilogue with the other's MFMAs
-// MPCD_X3_PAIR_MIN: narrowest layer mapped PAIR8 at 32 rows (each weight fragment loaded by one wave)
-#ifndef MPCD_X3_PAIR_MIN
-#define MPCD_X3_PAIR_MIN 128
-#endif
-#ifndef MPCD_X3_LEAD2
-#define MPCD_X3_LEAD2 0
-#endif
-#ifndef MPCD_X3_XALL
-#define MPCD_X3_XALL 0
-#endif
-#ifndef MPCD_X3_ILV
-#define MPCD_X3_ILV 1
-#endif
-// Experiment switches, all off in the product build (profiles/r3_mlp_vmem_ab.txt: every one measured slower):
-// MPCD_X3_WF32 fp32 weight stream split in registers (unfinished: also fails the cfg1 headline parity test),
-// MPCD_X3_SKIP_IDLE 1/2 idle waves issue no weight loads (branch / lane mask), MPCD_X3_EXP_NOPL2 timing probe
-// with the third weight plane's loads not issued (wrong results).
-#ifndef MPCD_X3_WF32
-#define MPCD_X3_WF32 0
-#endif
-#ifndef MPCD_X3_SKIP_IDLE
-#define MPCD_X3_SKIP_IDLE 0
-#endif
-#ifndef MPCD_X3_EXP_NOPL2
-#define MPCD_X3_EXP_NOPL2 0
-#endif
-#if !defined(MPCD_VARIANT) && (MPCD_X3_WF32 || MPCD_X3_EXP_NOPL2)
-#error "unfinished / wrong-result experiment switches build only as a variant (build.py variant: -DMPCD_VARIANT)"
-#endif
-constexpr int THREADS = 64 * MPCD_X3_WAVES;
-constexpr int WAVES = THREADS / 64;
+// in the PAIRED form. The 16x4 layout runs 4 waves (two workgroups per CU).
+constexpr int WAVES = 8;
+constexpr int THREADS = 64 * WAVES;
+// narrowest layer mapped PAIR8 at 32 rows (each weight fragment loaded by one wave)
+constexpr int PAIR_MIN = 128;
 enum { SPLIT = 0, PAIRED = 1, WIDE8 = 2, PAIR8 = 3 };
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -138,7 +107,7 @@ struct Lds3 {
 template <int N, int R = 32, int W = WAVES>
 constexpr int mode_for()
 {
-    return W == 8 ? ((N >= MPCD_X3_PAIR_MIN || R == 16) ? PAIR8 : WIDE8) : R == 16 ? PAIRED : N == 32 ? SPLIT : PAIRED;
+    return W == 8 ? ((N >= PAIR_MIN || R == 16) ? PAIR8 : WIDE8) : R == 16 ? PAIRED : N == 32 ? SPLIT : PAIRED;
 }
 
 constexpr int epi_of(int l) { return l == 12 ? EPI_NONE : (l % 2 == 1) ? EPI_CMISH : EPI_MISH; }
@@ -153,11 +122,10 @@ struct WFrag3 {
     u32x4 v[T][KC][3];
 };
 
-// What one wave loads for a layer: per (n-tile, k-chunk) WPL 16-byte pieces per lane — the three bf16
-// planes, or (MPCD_X3_WF32) the 8 fp32 weights as two halves, split into the planes in registers right
-// before the layer (to_planes: the same round-to-nearest-even split the host does, so the MFMA operands
-// are bit-identical) — 4 instead of 6 bytes per weight streamed from L2 every step.
-constexpr int WPL = MPCD_X3_WF32 ? 2 : 3;
+// What one wave loads for a layer: per (n-tile, k-chunk) the WPL = 3 bf16 planes, 16 bytes per lane each. (Streaming
+// the fp32 weights and splitting them in registers, 4 instead of 6 bytes per weight, measured slower:
+// profiles/r3_mlp_vmem_ab.txt.)
+constexpr int WPL = 3;
 template <int K, int N, int MODE>
 struct WLoad {
     using F = WFrag3<K, N, MODE>;
@@ -171,19 +139,9 @@ MPCD_DEV void to_planes(const WLoad<K, N, MODE> &w, WFrag3<K, N, MODE> &f)
 #pragma unroll
     for (int j = 0; j < WFrag3<K, N, MODE>::T; ++j)
 #pragma unroll
-        for (int kc = 0; kc < WFrag3<K, N, MODE>::KC; ++kc) {
-            if constexpr (WPL == 3) {
+        for (int kc = 0; kc < WFrag3<K, N, MODE>::KC; ++kc)
 #pragma unroll
-                for (int pl = 0; pl < 3; ++pl) f.v[j][kc][pl] = w.v[j][kc][pl];
-            } else {
-                u32x2 a0, a1, a2, b0, b1, b2;
-                split3(__builtin_bit_cast(f32x4, w.v[j][kc][0]), a0, a1, a2);
-                split3(__builtin_bit_cast(f32x4, w.v[j][kc][1]), b0, b1, b2);
-                f.v[j][kc][0] = u32x4{a0.x, a0.y, b0.x, b0.y};
-                f.v[j][kc][1] = u32x4{a1.x, a1.y, b1.x, b1.y};
-                f.v[j][kc][2] = u32x4{a2.x, a2.y, b2.x, b2.y};
-            }
-        }
+            for (int pl = 0; pl < 3; ++pl) f.v[j][kc][pl] = w.v[j][kc][pl];
 }
 
 // packed floats per layer (weights, then the N fp32 biases) and layer offsets in the x3 pack
@@ -205,7 +163,7 @@ MPCD_DEV int ntile_of(int wave, int j)
 
 // One wave-uniform buffer descriptor per layer; chunk (nt, kc, plane) at soffset ((nt*KC+kc)*3+p) KiB.
 template <int K, int N, int MODE>
-MPCD_DEV void load_w3(WLoad<K, N, MODE> &f, const float *__restrict__ wp, int wave, int lane16, bool need = true)
+MPCD_DEV void load_w3(WLoad<K, N, MODE> &f, const float *__restrict__ wp, int wave, int lane16)
 {
     using F = WLoad<K, N, MODE>;
     constexpr int KC = F::KC, NT = F::NT;
@@ -216,47 +174,14 @@ MPCD_DEV void load_w3(WLoad<K, N, MODE> &f, const float *__restrict__ wp, int wa
 #pragma unroll
     for (int j = 0; j < F::T; ++j) {
         const int nt = min(ntile_of<K, N, MODE>(wave, j), NT - 1);
-#if MPCD_X3_SKIP_IDLE == 2
-        // A wave with no tile n (or need = false) runs its loads with every lane masked off: the
-        // instructions stay on every path (no control flow, so no vmcnt drain at a join) but move no data
-        const int lim = (need && ntile_of<K, N, MODE>(wave, j) < NT) ? 64 * 16 : 0;
+        // clamped, not skipped: the load count stays path-independent; a wave with no tile n uses nothing it loaded
+        // (idle waves issuing no loads, by branch or by lane mask, measured slower: profiles/r3_mlp_vmem_ab.txt)
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc)
 #pragma unroll
             for (int pl = 0; pl < WPL; ++pl) {
                 const int soff = __builtin_amdgcn_readfirstlane(((nt * KC + kc) * WPL + pl) * 1024);
-                u32x4 v = u32x4{0u, 0u, 0u, 0u};
-                if (lane16 < lim) v = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, soff, 0));
-                f.v[j][kc][pl] = v;
-            }
-        continue;
-#elif MPCD_X3_SKIP_IDLE
-        // A wave with no tile n (or that does not run the layer: need = false) issues no loads. The
-        // vector-memory pipe, not the L2, is what the weight stream saturates: every 16-byte-per-lane
-        // load costs a CU the same issue time whether or not its data is used (profiles/r3_mlp_vmem_ab.txt).
-        if (!need || ntile_of<K, N, MODE>(wave, j) >= NT) {
-#pragma unroll
-            for (int kc = 0; kc < KC; ++kc)
-#pragma unroll
-                for (int pl = 0; pl < WPL; ++pl) f.v[j][kc][pl] = u32x4{0u, 0u, 0u, 0u};
-            continue;
-        }
-#else
-        // clamped, not skipped: the load count stays path-independent; a wave with no tile n uses
-        // nothing it loaded
-        (void)need;
-#endif
-#pragma unroll
-        for (int kc = 0; kc < KC; ++kc)
-#pragma unroll
-            for (int pl = 0; pl < WPL; ++pl) {
-                const int soff = __builtin_amdgcn_readfirstlane(((nt * KC + kc) * WPL + pl) * 1024);
-#if MPCD_X3_EXP_NOPL2
-                // timing experiment only (wrong results): the third plane's load not issued
-                f.v[j][kc][pl] = pl == 2 ? u32x4{0u, 0u, 0u, 0u} : __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, soff, 0));
-#else
                 f.v[j][kc][pl] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, soff, 0));
-#endif
             }
     }
 }

@@ -185,7 +185,6 @@ struct MlpX3 {
             *reinterpret_cast<u32x2 *>(o + L::out_pl(l)) = p1;
             *reinterpret_cast<u32x2 *>(o + 2 * L::out_pl(l)) = p2;
         };
-#if MPCD_X3_ILV
         if constexpr (PR && NCT == 2 && T == 1 && !(l == 0 && NB == 2)) {
             // One n-tile, two column tiles (the N = 128 layers at 32 rows): column tile 0's chain first,
             // then column tile 1's MFMAs with column tile 0's Mish / split / LDS stores scheduled in their
@@ -195,14 +194,6 @@ struct MlpX3 {
                 load_x3(x, lds + L::in_off(l) + (c * 16 + col) * L::in_rs(l) + (kc * 32 + 8 * q) * 2, L::in_pl(l));
             };
             auto chain = [&](int c) {
-#if MPCD_X3_XALL
-                // every k-chunk's fragments first: one LDS round trip per chain instead of one per chunk
-                u32x4 xk[KC][3];
-#pragma unroll
-                for (int kc = 0; kc < KC; ++kc) ldx1(xk[kc], c, kc);
-#pragma unroll
-                for (int kc = 0; kc < KC; ++kc) acc[0][c] = mfma_x3(f.v[0][kc], xk[kc], acc[0][c]);
-#else
                 u32x4 xa[3], xb[3];
                 ldx1(xa, c, 0);
 #pragma unroll
@@ -210,7 +201,6 @@ struct MlpX3 {
                     if (kc + 1 < KC) ldx1((kc & 1) ? xa : xb, c, kc + 1);
                     acc[0][c] = mfma_x3(f.v[0][kc], (kc & 1) ? xb : xa, acc[0][c]);
                 }
-#endif
             };
             chain(0);
             __builtin_amdgcn_sched_barrier(0);
@@ -225,7 +215,6 @@ struct MlpX3 {
             epi_tile(0, 1);
             return;
         }
-#endif
         auto ldx = [&](u32x4 (&x)[NCT][3], int kc) {
 #pragma unroll
             for (int c = 0; c < NCT; ++c) {
@@ -447,22 +436,12 @@ struct MlpX3 {
         const int tpi = threadIdx.x < COND_TOTAL / 4 ? (int)threadIdx.x : 0;
         f32x4 tpre = reinterpret_cast<const f32x4 *>(p.tproj)[tpi];
 
-#ifdef MPCD_PROF_LAYERS
-        // experiment build only: per-wave shader-clock cycles of each layer (work, then barrier wait)
-        uint64_t tacc[2 * 16] = {};
-        const uint64_t rt0 = __builtin_amdgcn_s_memrealtime();
-        uint64_t tprev = __builtin_readcyclecounter();
+        // MPCD_PROF_LAYERS build (mlp_common.h): cycles of each layer (work, then barrier wait)
+        ProfAcc tacc = {};
+        const uint64_t rt0 = prof_realtime();
+        uint64_t tprev = prof_now();
         const uint64_t ct0 = tprev;
-        auto bar = [&](int k) {
-            uint64_t t = __builtin_readcyclecounter();
-            tacc[2 * k] += t - tprev;
-            lds_barrier();
-            tprev = __builtin_readcyclecounter();
-            tacc[2 * k + 1] += tprev - t;
-        };
-#else
-        auto bar = [](int) { lds_barrier(); };
-#endif
+        auto bar = [&](int k) { prof_barrier(tacc, tprev, k); };
         for (int s = 0; s < p.n_steps; ++s) {
             // launder the weight base: stops LICM hoisting every layer's weight loads out of the loop
             asm volatile("" : "+s"(wofs), "+v"(lane16));
@@ -492,22 +471,13 @@ struct MlpX3 {
             WLoad<A::K[5], A::N[5], mode_for<A::N[5], R, W>()> w5;
             load_w3(w5, wptr(5), wave, lane16);
             WLoad<A::K[6], A::N[6], mode_for<A::N[6], R, W>()> w6;
-#if MPCD_X3_LEAD2  // the 128-wide layers' weights two segments ahead (their L2 latency outlasts one segment)
-            load_w3(w6, wptr(6), wave, lane16);
-#endif
             bar(4);
             layer<4>(w4, lds, wave, lane);
             WLoad<A::K[7], A::N[7], mode_for<A::N[7], R, W>()> w7;
-#if MPCD_X3_LEAD2
-            load_w3(w7, wptr(7), wave, lane16);
-#else
             load_w3(w6, wptr(6), wave, lane16);
-#endif
             bar(5);
             layer<5>(w5, lds, wave, lane);
-#if !MPCD_X3_LEAD2
             load_w3(w7, wptr(7), wave, lane16);
-#endif
             bar(6);
             layer<6>(w6, lds, wave, lane);
             WLoad<A::K[8], A::N[8], mode_for<A::N[8], R, W>()> w8;
@@ -531,7 +501,7 @@ struct MlpX3 {
             bar(11);
             layer<11>(w11, lds, wave, lane);
             FWL w13;
-            load_w3(w13, wptr(13), wave, lane16, wave < 4);
+            load_w3(w13, wptr(13), wave, lane16);
             bar(12);
             layer<12>(w12, lds, wave, lane);
             const StepPlan cur = sp;
@@ -559,22 +529,7 @@ struct MlpX3 {
                                              (NB == 2 || R == 16) ? -1 : 16 + col,
                                              wave < 4 && (NB == 1 || R == 32 || col < 8), p.chain_absmax, cand0, GRP ? cand0 + n_cand : p.batch);
         }
-#ifdef MPCD_PROF_LAYERS
-        {
-            const uint64_t t = __builtin_readcyclecounter();
-            tacc[2 * 15] += t - tprev;
-            if (p.dbg && blockIdx.x < 32 / W && lane == 0)  // 32 wave slots
-                for (int i = 0; i < 32; ++i) p.dbg[(blockIdx.x * W + (threadIdx.x >> 6)) * 32 + i] = (float)tacc[i];
-            if (p.dbg && threadIdx.x == 0) {  // per-block loop start / end (memrealtime, low 32 bits)
-                p.dbg[4096 + blockIdx.x * 2] = __builtin_bit_cast(float, (uint32_t)rt0);
-                p.dbg[4096 + blockIdx.x * 2 + 1] = __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_s_memrealtime());
-            }
-            if (p.dbg && blockIdx.x < 8 && threadIdx.x == 0) {  // shader clock = d(memtime) / d(memrealtime) x 100 MHz
-                p.dbg[8 * 4 * 32 + blockIdx.x * 2] = (float)(t - ct0);
-                p.dbg[8 * 4 * 32 + blockIdx.x * 2 + 1] = (float)(__builtin_amdgcn_s_memrealtime() - rt0);
-            }
-        }
-#endif
+        MPCD_PROF_DUMP(W, threadIdx.x >> 6, lane);
     }
 };
 
@@ -661,32 +616,6 @@ hipError_t launch_x3(const MlpSampleArgs &a, int layout, hipStream_t stream)
     }
 }
 
-template <int D0>
-hipError_t launch_x3_d0(const MlpSampleArgs &a, int lay, hipStream_t stream)
-{
-    const bool ctx = a.cproj != nullptr;
-    if (a.group > 0) {  // grouped contexts: the samplers (mpcd_sample_grouped), with a context
-        if (!ctx) return hipErrorInvalidValue;
-        switch (a.mode) {
-        case MODE_DDPM_CFG:
-            return a.noise ? launch_x3<D0, MODE_DDPM_XN, true, true>(a, lay, stream) : launch_x3<D0, MODE_DDPM_CFG, true, true>(a, lay, stream);
-        case MODE_DDIM_CFG: return launch_x3<D0, MODE_DDIM_CFG, true, true>(a, lay, stream);
-        case MODE_DDIM: return launch_x3<D0, MODE_DDIM, true, true>(a, lay, stream);
-        }
-        return hipErrorInvalidValue;
-    }
-    switch (a.mode) {
-    case MODE_DDPM_CFG:
-        if (a.noise) return ctx ? launch_x3<D0, MODE_DDPM_XN, true>(a, lay, stream) : launch_x3<D0, MODE_DDPM_XN, false>(a, lay, stream);
-        return ctx ? launch_x3<D0, MODE_DDPM_CFG, true>(a, lay, stream) : launch_x3<D0, MODE_DDPM_CFG, false>(a, lay, stream);
-    case MODE_DDIM_CFG: return ctx ? launch_x3<D0, MODE_DDIM_CFG, true>(a, lay, stream) : launch_x3<D0, MODE_DDIM_CFG, false>(a, lay, stream);
-    case MODE_DDIM: return ctx ? launch_x3<D0, MODE_DDIM, true>(a, lay, stream) : launch_x3<D0, MODE_DDIM, false>(a, lay, stream);
-    case MODE_EPS: return ctx ? launch_x3<D0, MODE_EPS, true>(a, lay, stream) : launch_x3<D0, MODE_EPS, false>(a, lay, stream);
-    case MODE_EPS1: return ctx ? launch_x3<D0, MODE_EPS1, true>(a, lay, stream) : launch_x3<D0, MODE_EPS1, false>(a, lay, stream);
-    }
-    return hipErrorInvalidValue;
-}
-
 }  // namespace
 
 void mlp_x3_force_layout(int layout) { g_force_layout.store(layout); }
@@ -725,21 +654,15 @@ static float bf16_val(uint16_t h)
 
 void mlp_pack_weights_x3(int d0, const float *const *lin_w, const float *const *lin_b, float *out)
 {
-    const int Ks[NLAYER] = {d0, 32, 32, 64, 64, 128, 128, 128, 256, 64, 128, 32, 32, 32};
-    const int Ns[NLAYER] = {32, 32, 64, 64, 128, 128, 128, 128, 64, 64, 32, 32, 32, d0};
     size_t o = 0;  // in floats
     for (int l = 0; l < NLAYER; ++l) {
-        const int K = Ks[l], N = Ns[l], KC = K / 32, NT = N / 16;
+        const int K = layer_k(d0, l), N = layer_n(d0, l), KC = K / 32, NT = N / 16;
         uint16_t *pk = reinterpret_cast<uint16_t *>(out + o);
         for (int nt = 0; nt < NT; ++nt)
             for (int kc = 0; kc < KC; ++kc)
                 for (int lane = 0; lane < 64; ++lane)
                     for (int j = 0; j < 8; ++j) {
                         const float w = lin_w[l][(size_t)(nt * 16 + (lane & 15)) * K + kc * 32 + 8 * (lane >> 4) + j];
-                        if (WPL == 2) {  // fp32 as loaded; the kernel splits it (to_planes)
-                            out[o + ((size_t)(nt * KC + kc) * 64 + lane) * 8 + j] = w;
-                            continue;
-                        }
                         const uint16_t h0 = bf16_rne(w);
                         const float r1 = w - bf16_val(h0);
                         const uint16_t h1 = bf16_rne(r1);
@@ -765,10 +688,6 @@ hipError_t launch_mlp_x3(int d0, int nb, const MlpSampleArgs &a, hipStream_t str
     const int lay = a.group > 0 ? mlp_x3_layout(a.batch / a.group, a.group, nb) : mlp_x3_layout(a.batch, nb);
     if (lay == LAYOUT_RW32X8) return launch_mlp_rw(d0, 32, 8, a, stream);
     if (lay == LAYOUT_RW32 || lay == LAYOUT_RW16) return launch_mlp_rw(d0, lay == LAYOUT_RW32 ? 32 : 16, 4, a, stream);
-    switch (d0) {
-    case 32: return launch_x3_d0<32>(a, lay, stream);
-    case 64: return launch_x3_d0<64>(a, lay, stream);
-    case 128: return launch_x3_d0<128>(a, lay, stream);
-    }
-    return hipErrorInvalidValue;
+    return sampler_dispatch(d0, a.mode, a.noise != nullptr, a.cproj != nullptr, a.group > 0,
+                            [&](auto D0, auto SMODE, auto CTX, auto GRP) { return launch_x3<D0, SMODE, CTX, GRP>(a, lay, stream); });
 }

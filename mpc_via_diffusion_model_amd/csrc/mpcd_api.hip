@@ -513,9 +513,6 @@ hipError_t launch_mlp(mpcd_ctx *c, MlpSampleArgs &m, int nb, hipStream_t st)
 }
 }  // namespace
 
-#ifndef MPCD_SEPARATE_EVENT_RECORDS
-#define MPCD_SEPARATE_EVENT_RECORDS 0
-#endif
 thread_local LaunchEvents g_launch_ev{};
 
 extern "C" {
@@ -728,9 +725,9 @@ static int sample_impl(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr,
     const float wp1 = (float)(1.0 + a->w), wf = (float)a->w;
     c->ev0 = c->evr[0][c->ev_n % mpcd_ctx::kEvRing];
     c->ev1 = c->evr[1][c->ev_n % mpcd_ctx::kEvRing];
-    // the MLP sampler's launch records both events itself (MPCD_SEPARATE_EVENT_RECORDS: separate records, A/B build)
-    constexpr bool kExtEv = !MPCD_SEPARATE_EVENT_RECORDS;
-    if (d.kind != MPCD_NET_MLP || !kExtEv) HIP_TRY(hipEventRecord(c->ev0, st));
+    // the MLP sampler's launch records both events itself (against separate records around it:
+    // profiles/r6_ext_launch_events_ab.txt)
+    if (d.kind != MPCD_NET_MLP) HIP_TRY(hipEventRecord(c->ev0, st));
     if (d.kind == MPCD_NET_MLP) {
         MlpSampleArgs m{};
         m.dbg = c->dbg;  // read only by the MPCD_PROF_LAYERS experiment build
@@ -760,7 +757,7 @@ static int sample_impl(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr,
             m.n_cond = c->n_cond;
             m.cond_dim = c->cond_dim;
         }
-        if (kExtEv) g_launch_ev = LaunchEvents{c->ev0, c->ev1};
+        g_launch_ev = LaunchEvents{c->ev0, c->ev1};
         const hipError_t le = launch_mlp(c, m, cfg ? 2 : 1, st);
         g_launch_ev = LaunchEvents{};
         HIP_TRY(le);
@@ -791,7 +788,7 @@ static int sample_impl(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr,
         rc = unet_sample(d, c->unet, u, st);
         if (rc) return fail(rc, "unet_sample: %s", unet_last_error());
     }
-    if (d.kind != MPCD_NET_MLP || !kExtEv) HIP_TRY(hipEventRecord(c->ev1, st));
+    if (d.kind != MPCD_NET_MLP) HIP_TRY(hipEventRecord(c->ev1, st));
     c->timed = true;
     ++c->ev_n;
     return MPCD_OK;
