@@ -154,6 +154,45 @@ int mpcd_sample(mpcd_ctx *ctx, const mpcd_sample_args *args, void *hip_stream);
  * net with context_dim == 0. */
 int mpcd_sample_grouped(mpcd_ctx *ctx, const mpcd_sample_args *args, int64_t group, void *hip_stream);
 
+/* ---- Warm start: denoise from a noised prior plan instead of from x_T ~ N(0, 1) (CFG-DDPM only).
+ * Receding-horizon use: the previous control step's winning plan, shifted by one horizon point (mpcd_shift_plans),
+ * is noised to diffusion level K = t_start <= N and only the K last steps of the chain run:
+ *     x = fp32(sa * x_init[row(b)]) + fp32(sb * z0[b]),   sa = sqrt_alphas_cumprod[K - 1],
+ *                                                         sb = sqrt_one_minus_alphas_cumprod[K - 1]
+ * which is GaussianDiffusionModel.q_sample at t = K - 1 (diffusion_model_base.py q_sample; two separately rounded
+ * products, one add), then the steps t = K - 1 ... 0 and the n_wo_noise extra steps at t = 0 exactly as the cold
+ * chain runs them: S = K + n_wo_noise. z0 is noise slice 0 (noise[0] when injected, else Philox slice 0 under the
+ * cold call's key); slice k >= 1 is the draw of the call's k-th executed step; noise / chain_out are [S + 1][B][H][d]
+ * with chain_out slice 0 = the noised x above, and chain_absmax covers exactly those slices (x_T is not in it).
+ * row(b): 0 when rows == 1 (one prior for every candidate), b when rows == batch (an elite set), b / group when
+ * rows == batch / group in a grouped call (one prior per plant state). Sharding invariance holds as for the cold
+ * call (global_offset keys Philox; the prior rows are the shard's own).
+ * t_start == 0 is the cold start: x_init is ignored and the call is bit for bit mpcd_sample / mpcd_sample_grouped.
+ * The DDIM samplers with t_start > 0 return MPCD_EUNSUP: their time grids and the unclamped chain's conditioning
+ * under a truncated start are not implemented. How good a warm plan is depends on the model and on K, not on this
+ * code: K = N keeps every step and only replaces x_T by a fully noised prior; a small K trusts the prior. */
+typedef struct {
+    const float *x_init;  /* dev, normalised [rows][H][d]; ignored when t_start == 0 */
+    int64_t rows;         /* 1 | batch | batch / group (grouped call) */
+    int32_t t_start;      /* K: 0 = cold start; else 1 <= K <= n_steps, the chain starts at t = K - 1 */
+} mpcd_warm_start;
+
+/* mpcd_sample (group == 0) or mpcd_sample_grouped (group >= 1) with a warm start. MPCD_EINVAL: warm == NULL,
+ * t_start outside [0, n_steps], t_start > 0 with x_init == NULL or rows not one of the values above, a group that
+ * does not divide the batch (and mpcd_sample_grouped's other conditions). */
+int mpcd_sample_warm(mpcd_ctx *ctx, const mpcd_sample_args *args, int64_t group /* 0: as mpcd_sample */,
+                     const mpcd_warm_start *warm, void *hip_stream);
+/* mpcd_sample_steps of such a call: t_start + n_wo_noise (t_start == 0: mpcd_sample_steps) */
+int mpcd_sample_steps_warm(mpcd_ctx *ctx, const mpcd_sample_args *args, const mpcd_warm_start *warm, int32_t *n_steps);
+/* The next priors from finished plans: for m < n_states, out[m][h] = u_norm[index_dev[m] - index_offset][min(h + 1,
+ * H - 1)] - the candidate's normalised plan moved one horizon point ahead, its last point repeated. u_norm dev
+ * [batch][H][d] (d = the net's state_dim), index_dev dev int64 [n_states] of GLOBAL candidate indices (mpcd_control_step's
+ * best_index, or &best->index of a device mpcd_best); NULL = row m. A state whose index falls outside
+ * [index_offset, index_offset + batch) keeps its out[m] (a shard that does not own the winner). out must not
+ * overlap u_norm. One launch for any n_states. */
+int mpcd_shift_plans(mpcd_ctx *ctx, const float *u_norm, int64_t batch, int32_t horizon, const int64_t *index_dev,
+                     int64_t index_offset, int64_t n_states, float *out /* dev [n_states][H][d] */, void *hip_stream);
+
 /* One noise-net forward at diffusion time t (the model(x, t, context, mask) calls of
  * p_mean_variance_CFG, diffusion_model_base.py:166-168): x dev [B][H][d]; eps_cond dev [B][H][d] =
  * net(x, t, ctx, mask = 0); eps_uncond dev [B][H][d] = net(x, t, ctx, mask = 1) for a cfg_masked net
@@ -344,6 +383,21 @@ typedef struct {
  * every rank is NaN / Inf - garbage is never returned as a normal result. */
 int mpcd_mpc_step(mpcd_ctx *ctx, const mpcd_step_args *args, mpcd_best *best_host, float *u_best_host,
                   void *hip_stream);
+/* mpcd_mpc_step whose sampler call is mpcd_sample_warm with one prior for every candidate (warm->rows == 1; t_start
+ * == 0: a cold step), plus the next step's prior: when next_init_out != NULL (dev [H][d]) one mpcd_shift_plans launch
+ * on the winner's normalised plan follows the selection on hip_stream (one rank: row best.index - global_offset of
+ * sample.x_out; with a communicator: the all-reduced winner row, so every rank holds the same prior). It is a DEVICE
+ * output, ordered on hip_stream like sample.x_out, and may alias nothing the step reads - in particular not
+ * warm->x_init: keep two buffers and swap them. The MPCD_F16X2 re-run rule is mpcd_mpc_step's. mpcd_mpc_step itself
+ * is unchanged (no launch, no branch added).
+ * Clip rule: under MPCD_CLIP_CHAIN the tested chain of a warm step starts at the noised prior, not at x_T ~ N(0, 1),
+ * so the flag is no longer "practically always 1": it is 1 only if some chain value really leaves [-1 - 1e-4,
+ * 1 + 1e-4] (likely at K near N, where sb ~ 1; rare at a small K with a prior inside [-1, 1]). That is what the
+ * reference's whole-chain unnormalise would see for such a chain; a caller who wants the cold step's (clipping)
+ * behaviour at every K has no rule for it here. */
+int mpcd_mpc_step_warm(mpcd_ctx *ctx, const mpcd_step_args *args, const mpcd_warm_start *warm /* rows == 1 */,
+                       float *next_init_out /* dev [H][d] or NULL */, mpcd_best *best_host, float *u_best_host,
+                       void *hip_stream);
 
 /* Failure-detection flags of the last mpcd_mpc_step on this context (read after it returned):
  * bit 0 (MPCD_STEP_CLIPPED): LimitsNormalizer's global clip was applied; bit 1 (MPCD_STEP_NAN_SAMPLES): some

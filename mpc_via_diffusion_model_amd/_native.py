@@ -58,6 +58,10 @@ class StepArgs(ctypes.Structure):
                 ("costs_all", ctypes.c_void_p)]
 
 
+class WarmStart(ctypes.Structure):
+    _fields_ = [("x_init", ctypes.c_void_p), ("rows", ctypes.c_int64), ("t_start", ctypes.c_int32)]
+
+
 class TrainCfg(ctypes.Structure):
     _fields_ = [("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
                 ("ema_decay", ctypes.c_float), ("step_start_ema", ctypes.c_int32), ("update_ema_every", ctypes.c_int32)]
@@ -76,6 +80,14 @@ EXPORTS = {
     "mpcd_sample_steps": ([ctypes.c_void_p, ctypes.POINTER(SampleArgs), ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
     "mpcd_sample": ([ctypes.c_void_p, ctypes.POINTER(SampleArgs), ctypes.c_void_p], ctypes.c_int),
     "mpcd_sample_grouped": ([ctypes.c_void_p, ctypes.POINTER(SampleArgs), ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
+    "mpcd_sample_warm": ([ctypes.c_void_p, ctypes.POINTER(SampleArgs), ctypes.c_int64, ctypes.POINTER(WarmStart),
+                          ctypes.c_void_p], ctypes.c_int),
+    "mpcd_sample_steps_warm": ([ctypes.c_void_p, ctypes.POINTER(SampleArgs), ctypes.POINTER(WarmStart),
+                                ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "mpcd_shift_plans": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                          ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "mpcd_mpc_step_warm": ([ctypes.c_void_p, ctypes.POINTER(StepArgs), ctypes.POINTER(WarmStart), ctypes.c_void_p,
+                            ctypes.POINTER(Best), ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "mpcd_eps": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "mpcd_clip_flag": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p],

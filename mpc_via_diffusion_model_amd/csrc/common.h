@@ -141,6 +141,20 @@ MPCD_DEV f32x4 denoise_update4(const StepPlan &sp, int mode, int clamp_x0, float
     return o;
 }
 
+// Warm start (mpcd_warm_start): the chain's first x of one element quad, GaussianDiffusionModel.q_sample at
+// t = K - 1 (diffusion_model_base.py q_sample): sa = sqrt_alphas_cumprod[K - 1], sb =
+// sqrt_one_minus_alphas_cumprod[K - 1], x0 the prior plan, z noise slice 0. Two separately rounded products and
+// one add (-ffp-contract=off), as torch computes it.
+MPCD_DEV f32x4 q_sample4(float sa, float sb, const f32x4 &x0, const f32x4 &z)
+{
+    f32x4 o;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[r] = sa * x0[r] + sb * z[r];
+    return o;
+}
+// Which row of the prior candidate b starts from (mpcd_warm_start.rows): one for all, its own, or its group's
+enum { XINIT_SHARED = 0, XINIT_PER_CAND = 1, XINIT_PER_GROUP = 2 };
+
 // running chain |x| maximum of one element quad (bits of |x| as uint32: a NaN wins the integer max);
 // elements are copied to scalars first (a __builtin_bit_cast of a vector-element subscript compiled to
 // element 0 for every index)

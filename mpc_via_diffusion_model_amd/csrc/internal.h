@@ -120,6 +120,11 @@ struct MlpSampleArgs {
     // split-bf16 launchers for their own layout (their workgroups never straddle a group), 0 elsewhere
     int64_t group;
     int32_t group_wgs;
+    // warm start (mpcd_sample_warm): x_init [rows][D0] or null = start from noise slice 0 as it is; else the chain
+    // starts at q_sample4(x_sa, x_sb, x_init[row], slice 0) with row by x_init_kind (XINIT_*; per group: b / group)
+    int32_t x_init_kind;
+    const float *x_init;
+    float x_sa, x_sb;
 };
 
 int mlp_packed_floats(int d0);

@@ -83,18 +83,19 @@ struct CandSpan {
     int64_t cand0;
     int32_t n;
     const float *cproj;
+    int32_t m;  // the group (0 in a plain call): the row of a per-group warm-start prior
 };
 template <int CPW, bool GRP>
 MPCD_DEV CandSpan cand_span(const float *cproj, int64_t group, int32_t group_wgs)
 {
     if constexpr (!GRP) {
-        return CandSpan{(int64_t)blockIdx.x * CPW, 0, cproj};
+        return CandSpan{(int64_t)blockIdx.x * CPW, 0, cproj, 0};
     } else {
         const uint32_t m = __builtin_amdgcn_readfirstlane(blockIdx.x / (uint32_t)group_wgs);
         const uint32_t j = blockIdx.x - m * (uint32_t)group_wgs;
         const int64_t left = group - (int64_t)j * CPW;  // >= 1: j < ceil(group / CPW)
         return CandSpan{(int64_t)m * group + (int64_t)j * CPW, left < CPW ? (int32_t)left : CPW,
-                        cproj + (size_t)m * COND_TOTAL};
+                        cproj + (size_t)m * COND_TOTAL, (int32_t)m};
     }
 }
 // column / local candidate c of the workgroup holds a candidate of the call
@@ -221,6 +222,16 @@ MPCD_DEV void prof_mark(ProfAcc &, uint64_t &, int, const T &) {}
 MPCD_DEV void prof_mark(ProfAcc &, uint64_t, int) {}
 #define MPCD_PROF_DUMP(W, wave, lane) (void)0
 #endif
+
+// Warm start (MlpSampleArgs::x_init non-null): the x the chain starts from, for element quad qd of local candidate gc
+// whose noise slice 0 is z. grow = the candidate's row under XINIT_PER_GROUP. Called in the staging loops before the
+// step loop, for candidates of the call only (no read of the prior for an idle column).
+template <int D0>
+MPCD_DEV f32x4 warm_x(const float *x_init, int kind, float sa, float sb, int64_t gc, int64_t grow, int qd, const f32x4 &z)
+{
+    const int64_t row = kind == XINIT_SHARED ? 0 : kind == XINIT_PER_CAND ? gc : grow;
+    return q_sample4(sa, sb, *reinterpret_cast<const f32x4 *>(x_init + (size_t)row * D0 + qd * 4), z);
+}
 
 // |v| as an ordered integer: max over these bits is max |v| and propagates a NaN (its magnitude bits
 // exceed +inf's), which is what the chain clip test needs (mpcd_sample_args.chain_absmax).

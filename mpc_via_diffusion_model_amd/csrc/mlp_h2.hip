@@ -613,6 +613,7 @@ struct MlpH2 {
             if (gc < p.batch) {
                 z = p.noise ? *reinterpret_cast<const f32x4 *>(p.noise + (size_t)gc * D0 + qd * 4)
                             : philox_normal4(p.seed, (uint64_t)(p.global_offset + gc), 0u, (uint32_t)qd);
+                if (IS_DDPM && p.x_init) z = warm_x<D0>(p.x_init, p.x_init_kind, p.x_sa, p.x_sb, gc, 0, qd, z);  // warm start
                 if (p.chain && SMODE != MODE_EPS) *reinterpret_cast<f32x4 *>(p.chain + (size_t)gc * D0 + qd * 4) = z;
             }
             store_x(lds, c, qd * 4, z);

@@ -364,6 +364,9 @@ struct MlpKernel {
             if (gc < p.batch) {
                 z = p.noise ? *reinterpret_cast<const f32x4 *>(p.noise + (size_t)gc * D0 + qd * 4)
                             : philox_normal4(p.seed, (uint64_t)(p.global_offset + gc), 0u, (uint32_t)qd);
+                // warm start; a grouped call's per-group prior row is gc / group, as its projection row above
+                if (IS_DDPM && p.x_init)
+                    z = warm_x<D0>(p.x_init, p.x_init_kind, p.x_sa, p.x_sb, gc, p.x_init_kind == XINIT_PER_GROUP ? gc / p.group : 0, qd, z);
                 if (p.chain && SMODE != MODE_EPS) *reinterpret_cast<f32x4 *>(p.chain + (size_t)gc * D0 + qd * 4) = z;
             }
             *reinterpret_cast<f32x4 *>(lds + L::XB + c * L::SX + qd * 4) = z;

@@ -37,6 +37,8 @@ hipError_t launch_control_step(const mpcd_system_desc &d, double *x_dev, int64_t
                                const int *flags_dev, int select_first, int decimals, double *u_applied,
                                int64_t *best_idx, double *best_cost, hipStream_t stream);
 hipError_t launch_argmin(const double *cost, int64_t n, int64_t offset, mpcd_best *best, hipStream_t stream);
+hipError_t launch_shift_plans(const float *rows, int64_t batch, int H, int d, const int64_t *index, int64_t offset,
+                              int64_t n_states, float *out, hipStream_t stream);
 hipError_t launch_winner_row(const mpcd_best *best, int64_t lo, int64_t n_local, const float *rows, int row_len,
                              float *out, hipStream_t stream);
 
@@ -313,13 +315,15 @@ enum {
 float tab(const mpcd_ctx *c, int which, int t) { return c->tables[(size_t)which * c->n_steps + t]; }
 
 // Build the per-step plan (sample_functions.py:28-44 for DDPM; diffusion_model_base.py:251-290 for DDIM).
-int build_plan(mpcd_ctx *c, const mpcd_sample_args *a, std::vector<StepPlan> &plan)
+// t_start = K > 0 (DDPM, warm start): the chain's last K steps t = K - 1 ... 0 and the n_wo_noise extra ones, the cold
+// plan's entries unchanged; 0: the whole chain.
+int build_plan(mpcd_ctx *c, const mpcd_sample_args *a, std::vector<StepPlan> &plan, int t_start = 0)
 {
     plan.clear();
     const int N = c->n_steps;
     if (a->sampler == MPCD_DDPM_CFG) {
         if (a->n_wo_noise < 0) return fail(MPCD_EINVAL, "n_wo_noise < 0");
-        for (int i = N - 1; i >= -a->n_wo_noise; --i) {
+        for (int i = (t_start > 0 ? t_start : N) - 1; i >= -a->n_wo_noise; --i) {
             const int t = i < 0 ? 0 : i;
             StepPlan s{};
             s.t = t;
@@ -370,6 +374,40 @@ int build_plan(mpcd_ctx *c, const mpcd_sample_args *a, std::vector<StepPlan> &pl
         s.cn = sqrtf(1.0f - an - 0.0f);  // sigma = eta * (...) = 0 (eta = 0, :253)
         plan.push_back(s);
     }
+    return MPCD_OK;
+}
+
+// A call's warm start, checked and resolved (mpcd_warm_start -> what the kernels take). t_start == 0: cold.
+struct WarmArgs {
+    const float *x_init = nullptr;
+    int32_t kind = XINIT_SHARED;
+    int32_t t_start = 0;
+    float sa = 0.f, sb = 0.f;  // sqrt_alphas_cumprod[K - 1], sqrt_one_minus_alphas_cumprod[K - 1]
+};
+int resolve_warm(const mpcd_ctx *c, const mpcd_sample_args *a, int64_t group, const mpcd_warm_start *w, WarmArgs &out)
+{
+    out = WarmArgs{};
+    if (!c || !a || !w) return fail(MPCD_EINVAL, "null argument (warm start)");
+    if (!c->n_steps) return fail(MPCD_ESTATE, "no schedule set");
+    if (w->t_start < 0 || w->t_start > c->n_steps)
+        return fail(MPCD_EINVAL, "warm start: t_start %d outside [0, %d]", w->t_start, c->n_steps);
+    if (w->t_start == 0) return MPCD_OK;
+    if (a->sampler != MPCD_DDPM_CFG)
+        return fail(MPCD_EUNSUP, "warm start (t_start > 0) is implemented for the CFG-DDPM sampler only");
+    if (!w->x_init) return fail(MPCD_EINVAL, "warm start: t_start %d without x_init", w->t_start);
+    if (w->rows == 1)
+        out.kind = XINIT_SHARED;
+    else if (w->rows == a->batch)
+        out.kind = XINIT_PER_CAND;
+    else if (group > 0 && a->batch % group == 0 && w->rows == a->batch / group)
+        out.kind = XINIT_PER_GROUP;
+    else
+        return fail(MPCD_EINVAL, "warm start: x_init rows %lld is none of 1, batch %lld%s", (long long)w->rows,
+                    (long long)a->batch, group > 0 ? ", batch / group" : "");
+    out.x_init = w->x_init;
+    out.t_start = w->t_start;
+    out.sa = tab(c, T_SQAC, w->t_start - 1);
+    out.sb = tab(c, T_SQ1MAC, w->t_start - 1);
     return MPCD_OK;
 }
 
@@ -634,15 +672,16 @@ int mpcd_sample_steps(mpcd_ctx *c, const mpcd_sample_args *a, int32_t *n)
 // ctx_row: mpcd_mpc_step's one shared context row by value (the ctx prologue reads it from its kernel
 // arguments: no host-to-device copy); nullptr: a->context on the device (the C-ABI mpcd_sample)
 // group: mpcd_sample_grouped's candidates per context row (a->context is [batch / group][C]); 0: mpcd_sample
+// warm: the call's resolved warm start (resolve_warm), nullptr or t_start == 0: the cold chain from slice 0
 static int sample_impl(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr, const CtxRowArg *ctx_row,
-                       int64_t group = 0);
+                       int64_t group = 0, const WarmArgs *warm = nullptr);
 
 int mpcd_sample(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr)
 {
     return sample_impl(c, a, stream_ptr, nullptr);
 }
 
-int mpcd_sample_grouped(mpcd_ctx *c, const mpcd_sample_args *a, int64_t group, void *stream_ptr)
+static int check_grouped(const mpcd_ctx *c, const mpcd_sample_args *a, int64_t group)
 {
     if (!c || !a) return fail(MPCD_EINVAL, "null argument");
     if (group < 1) return fail(MPCD_EINVAL, "mpcd_sample_grouped: group %lld < 1", (long long)group);
@@ -652,10 +691,57 @@ int mpcd_sample_grouped(mpcd_ctx *c, const mpcd_sample_args *a, int64_t group, v
     if (c->net_loaded && c->desc.context_dim == 0)
         return fail(MPCD_EINVAL, "mpcd_sample_grouped: the net has no context (context_dim == 0)");
     if (!a->context) return fail(MPCD_EINVAL, "mpcd_sample_grouped: no context given");
+    return MPCD_OK;
+}
+
+int mpcd_sample_grouped(mpcd_ctx *c, const mpcd_sample_args *a, int64_t group, void *stream_ptr)
+{
+    if (int rc = check_grouped(c, a, group)) return rc;
     return sample_impl(c, a, stream_ptr, nullptr, group);
 }
 
-static int sample_impl(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr, const CtxRowArg *ctx_row, int64_t group)
+int mpcd_sample_warm(mpcd_ctx *c, const mpcd_sample_args *a, int64_t group, const mpcd_warm_start *warm, void *stream_ptr)
+{
+    if (!c || !a || !warm) return fail(MPCD_EINVAL, "null argument");
+    if (group != 0)
+        if (int rc = check_grouped(c, a, group)) return rc;
+    WarmArgs w;
+    if (int rc = resolve_warm(c, a, group, warm, w)) return rc;
+    return sample_impl(c, a, stream_ptr, nullptr, group, &w);
+}
+
+int mpcd_sample_steps_warm(mpcd_ctx *c, const mpcd_sample_args *a, const mpcd_warm_start *warm, int32_t *n)
+{
+    if (!c || !a || !warm || !n) return fail(MPCD_EINVAL, "null argument");
+    if (!c->n_steps) return fail(MPCD_ESTATE, "no schedule set");
+    if (warm->t_start < 0 || warm->t_start > c->n_steps)
+        return fail(MPCD_EINVAL, "warm start: t_start %d outside [0, %d]", warm->t_start, c->n_steps);
+    if (warm->t_start > 0 && a->sampler != MPCD_DDPM_CFG)
+        return fail(MPCD_EUNSUP, "warm start (t_start > 0) is implemented for the CFG-DDPM sampler only");
+    std::vector<StepPlan> plan;
+    int rc = build_plan(c, a, plan, warm->t_start);
+    if (rc) return rc;
+    *n = (int32_t)plan.size();
+    return MPCD_OK;
+}
+
+int mpcd_shift_plans(mpcd_ctx *c, const float *u_norm, int64_t batch, int32_t horizon, const int64_t *index_dev,
+                     int64_t index_offset, int64_t n_states, float *out, void *stream_ptr)
+{
+    if (!c || !u_norm || !out) return fail(MPCD_EINVAL, "null argument");
+    if (!c->net_loaded) return fail(MPCD_ESTATE, "no net loaded");
+    if (batch < 1 || n_states < 1 || n_states > INT32_MAX)
+        return fail(MPCD_EINVAL, "mpcd_shift_plans: batch %lld / n_states %lld", (long long)batch, (long long)n_states);
+    if (horizon != c->desc.horizon)
+        return fail(MPCD_EINVAL, "mpcd_shift_plans: horizon %d != the net's %d", horizon, c->desc.horizon);
+    DEVICE_GUARD(c->device);
+    HIP_TRY(launch_shift_plans(u_norm, batch, horizon, c->desc.state_dim, index_dev, index_offset, n_states, out,
+                               static_cast<hipStream_t>(stream_ptr)));
+    return MPCD_OK;
+}
+
+static int sample_impl(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr, const CtxRowArg *ctx_row, int64_t group,
+                       const WarmArgs *warm)
 {
     if (!c || !a) return fail(MPCD_EINVAL, "null argument");
     if (!c->net_loaded) return fail(MPCD_ESTATE, "no net loaded");
@@ -669,7 +755,8 @@ static int sample_impl(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr,
     hipStream_t st = static_cast<hipStream_t>(stream_ptr);
     DEVICE_GUARD(c->device);
 
-    int rc = build_plan(c, a, c->plan_host);
+    if (warm && warm->t_start == 0) warm = nullptr;
+    int rc = build_plan(c, a, c->plan_host, warm ? warm->t_start : 0);
     if (rc) return rc;
     const int S = (int)c->plan_host.size();
     const CondLayer *cl = c->cond_layers.as<CondLayer>();
@@ -749,6 +836,12 @@ static int sample_impl(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr,
         m.wp1 = wp1;
         m.wf = wf;
         m.group = group;
+        if (warm) {
+            m.x_init = warm->x_init;
+            m.x_init_kind = warm->kind;
+            m.x_sa = warm->sa;
+            m.x_sb = warm->sb;
+        }
         if (fuse_ctx) {
             m.ctx_fused = 1;
             m.ctx_row = *ctx_row;
@@ -781,6 +874,13 @@ static int sample_impl(mpcd_ctx *c, const mpcd_sample_args *a, void *stream_ptr,
         u.clamp_x0 = a->clamp_x0;
         u.wp1 = wp1;
         u.wf = wf;
+        if (warm) {
+            u.x_init = warm->x_init;
+            u.x_init_kind = warm->kind;
+            u.x_group = group;
+            u.x_sa = warm->sa;
+            u.x_sb = warm->sb;
+        }
         u.fused = unet_use_fused(c->unet, u.mode);  // once: sizes the workspace and picks the kernels
         size_t ws = unet_workspace_bytes(d, c->unet, u.fused, a->batch, cfg ? 2 : 1);
         if ((rc = c->unet_ws.ensure(ws))) return rc;
@@ -1217,26 +1317,58 @@ int mpcd_select(mpcd_ctx *c, const double *cost_local, int64_t n_local, const fl
     return comm_reduce(c, row_out, (size_t)row_len, COMM_SUM_F32, st);
 }
 
-static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream);
+// WARM (mpcd_mpc_step_warm): the sampler call takes the resolved warm start and, next_init_out non-null, one
+// shift_plan launch on the winner follows the selection. A template flag: mpcd_mpc_step's instantiation compiles the
+// code it had, with no branch on either.
+extern "C++" {  // templates cannot have C linkage
+template <bool WARM>
+static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream,
+                         const WarmArgs *warm = nullptr, float *next_init_out = nullptr);
 
 // An MPCD_F16X2 net computes in the fp16 range: a step whose sampled trajectories came back with a NaN (an
 // activation beyond 65504 turns into one: hi = inf, lo = inf - inf) or with no finite cost is re-run with the net's
 // split-bf16 (MPCD_F32X3) programs and flagged MPCD_STEP_F32X3_RERUN. Single rank only: with a communicator every
 // rank would have to agree to re-run (the flag and the ENONFINITE return report it there).
-int mpcd_mpc_step(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream)
+template <bool WARM>
+static int mpc_step_rerun(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream,
+                          const WarmArgs *warm = nullptr, float *next_init_out = nullptr)
 {
-    int rc = mpc_step_impl(c, a, best_host, u_best_host, stream);
+    int rc = mpc_step_impl<WARM>(c, a, best_host, u_best_host, stream, warm, next_init_out);
     const bool f16x2 = c && c->net_loaded && c->desc.dtype == MPCD_F16X2 && !c->force_x3;
     if (f16x2 && !c->comm && (rc == MPCD_ENONFINITE || (rc == MPCD_OK && (c->step_flags & MPCD_STEP_NAN_SAMPLES)))) {
         c->force_x3 = c->unet.force3 = true;
-        rc = mpc_step_impl(c, a, best_host, u_best_host, stream);
+        rc = mpc_step_impl<WARM>(c, a, best_host, u_best_host, stream, warm, next_init_out);
         c->force_x3 = c->unet.force3 = false;
         c->step_flags |= MPCD_STEP_F32X3_RERUN;
     }
     return rc;
 }
+}  // extern "C++"
 
-static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream)
+int mpcd_mpc_step(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream)
+{
+    return mpc_step_rerun<false>(c, a, best_host, u_best_host, stream);
+}
+
+int mpcd_mpc_step_warm(mpcd_ctx *c, const mpcd_step_args *a, const mpcd_warm_start *warm, float *next_init_out,
+                       mpcd_best *best_host, float *u_best_host, void *stream)
+{
+    if (!c || !a || !warm) return fail(MPCD_EINVAL, "null argument");
+    if (warm->t_start > 0 && warm->rows != 1)
+        return fail(MPCD_EINVAL, "mpcd_mpc_step_warm: one prior for every candidate (rows == 1), not %lld rows",
+                    (long long)warm->rows);
+    // the re-run of an MPCD_F16X2 step reads the prior again: the next prior must not have replaced it
+    if (next_init_out && warm->t_start > 0 && next_init_out == warm->x_init)
+        return fail(MPCD_EINVAL, "mpcd_mpc_step_warm: next_init_out aliases warm->x_init");
+    WarmArgs w;
+    if (int rc = resolve_warm(c, &a->sample, 0, warm, w)) return rc;
+    return mpc_step_rerun<true>(c, a, best_host, u_best_host, stream, &w, next_init_out);
+}
+
+extern "C++" {
+template <bool WARM>
+static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream,
+                         const WarmArgs *warm, float *next_init_out)
 {
     if (!c || !a || !a->sys || !a->x0 || !a->act_min || !a->act_max || !a->cost_local || !best_host || !u_best_host)
         return fail(MPCD_EINVAL, "null argument");
@@ -1300,7 +1432,11 @@ static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_h
         if ((rc = c->step_amax.ensure(sizeof(float) * (size_t)B))) return rc;
         sa.chain_absmax = c->step_amax.as<float>();
     }
-    if ((rc = sample_impl(c, &sa, stream, by_value ? &ctx_row : nullptr))) return rc;
+    if constexpr (WARM) {
+        if ((rc = sample_impl(c, &sa, stream, by_value ? &ctx_row : nullptr, 0, warm))) return rc;
+    } else {
+        if ((rc = sample_impl(c, &sa, stream, by_value ? &ctx_row : nullptr))) return rc;
+    }
 
     // LimitsNormalizer's global clip flag over the chain (the reference's unnormalize_states of run_CFG's
     // whole chain), over the final samples, or proven 0; max-reduced over ranks (see mpcd_clip_flag)
@@ -1347,6 +1483,18 @@ static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_h
         HIP_TRY(launch_unnormalize(row_norm, row, d.state_dim, flag, a->act_min, a->act_max, u_dev, st));
         HIP_TRY(hipMemcpyAsync(code_dev, flag, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     }
+    if constexpr (WARM) {
+        // the next step's prior: the winner's normalised plan moved one horizon point ahead. One rank: the row of
+        // x_out that the device-resident best.index names; ranks: the all-reduced winner row (the same on each)
+        if (next_init_out) {
+            if (!c->comm)
+                HIP_TRY(launch_shift_plans(sa.x_out, B, H, d.state_dim, &best_dev->index, sa.global_offset, 1,
+                                           next_init_out, st));
+            else
+                HIP_TRY(launch_shift_plans(reinterpret_cast<float *>(part_idx + n_part), 1, H, d.state_dim, nullptr, 0, 1,
+                                           next_init_out, st));
+        }
+    }
     if (c->comm) {
         HIP_TRY(hipMemcpyAsync(host_out, c->step_out.p, out_bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -1382,6 +1530,7 @@ static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_h
     }
     return MPCD_OK;
 }
+}  // extern "C++"
 
 
 // ---- native training step: MLP noise-net, fp32, csrc/train.hip

@@ -514,7 +514,42 @@ __global__ void winner_row_kernel(const mpcd_best *best, int64_t lo, int64_t n_l
     for (int i = threadIdx.x; i < row_len; i += blockDim.x) out[i] = own ? rows[idx * row_len + i] : 0.f;
 }
 
+// The next warm-start priors (mpcd_shift_plans): workgroup m gathers state m's plan, row index[m] - offset of rows
+// [batch][H][d] (index null: row m), and writes it moved one horizon point ahead with the last point repeated,
+// out[m][h] = row[min(h + 1, H - 1)]. V floats per access (V divides d, so a vector never straddles two points and
+// both sides are V-aligned). An index outside the rows writes nothing.
+template <int V>
+__global__ __launch_bounds__(256) void shift_plan_kernel(const float *rows, int64_t batch, int H, int d,
+                                                         const int64_t *index, int64_t offset, float *out)
+{
+    typedef float vec_t __attribute__((ext_vector_type(V)));
+    const int64_t m = blockIdx.x;
+    const int64_t idx = index ? index[m] - offset : m;
+    if (idx < 0 || idx >= batch) return;
+    const int dv = d / V, n = H * dv;
+    const vec_t *src = reinterpret_cast<const vec_t *>(rows + (size_t)idx * H * d);
+    vec_t *dst = reinterpret_cast<vec_t *>(out + (size_t)m * H * d);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int h = i / dv, e = i - h * dv;
+        dst[i] = src[min(h + 1, H - 1) * dv + e];
+    }
+}
+
 }  // namespace
+
+hipError_t launch_shift_plans(const float *rows, int64_t batch, int H, int d, const int64_t *index, int64_t offset,
+                              int64_t n_states, float *out, hipStream_t stream)
+{
+    const dim3 grid((unsigned)n_states), block(256);
+    const uintptr_t al = reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(out);  // a caller's sub-view
+    if (d % 4 == 0 && al % 16 == 0)
+        hipLaunchKernelGGL(shift_plan_kernel<4>, grid, block, 0, stream, rows, batch, H, d, index, offset, out);
+    else if (d % 2 == 0 && al % 8 == 0)
+        hipLaunchKernelGGL(shift_plan_kernel<2>, grid, block, 0, stream, rows, batch, H, d, index, offset, out);
+    else
+        hipLaunchKernelGGL(shift_plan_kernel<1>, grid, block, 0, stream, rows, batch, H, d, index, offset, out);
+    return hipGetLastError();
+}
 
 hipError_t launch_winner_row(const mpcd_best *best, int64_t lo, int64_t n_local, const float *rows, int row_len,
                              float *out, hipStream_t stream)

@@ -110,6 +110,12 @@ struct UnetSampleArgs {
     float *eps_cond, *eps_uncond;  // MODE_EPS / MODE_EPS1 outputs
     const float *x_in;             // MODE_EPS / MODE_EPS1 input
     int32_t fused;                 // the form, decided once per call by unet_use_fused (it also sized workspace)
+    // warm start (mpcd_sample_warm): null = the chain starts at noise slice 0; else at q_sample4(x_sa, x_sb,
+    // x_init[row(b)], slice 0), row by x_init_kind (XINIT_*; per group: b / x_group)
+    const float *x_init;
+    int32_t x_init_kind;
+    int64_t x_group;
+    float x_sa, x_sb;
 };
 
 // epilogue kinds shared by both conv families

@@ -270,17 +270,28 @@ __global__ __launch_bounds__(CT) void conv_kernel(const ConvK a)
     conv_body<KIND, EPI>(a);
 }
 
-// x_T into the state (and chain[0])
+// x_T into the state (and chain[0]); warm start (x_init non-null): the noised prior, q_sample of row b's prior
+// (shared: row 0; per candidate: b; per group: b / x_group) with slice 0 as its noise
+struct WarmInit {
+    const float *x_init;
+    int32_t kind;
+    int64_t group;
+    float sa, sb;
+};
 __global__ void init_x_kernel(float *x, int64_t batch, int flat, const float *noise, uint64_t seed, int64_t goff,
-                              float *chain)
+                              float *chain, const WarmInit w)
 {
     const int quads = flat / 4;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= batch * quads) return;
     const int64_t b = i / quads;
     const int qd = (int)(i - b * quads);
-    const f32x4 z = noise ? *reinterpret_cast<const f32x4 *>(noise + (size_t)b * flat + 4 * qd)
-                          : philox_normal4(seed, (uint64_t)(goff + b), 0u, (uint32_t)qd);
+    f32x4 z = noise ? *reinterpret_cast<const f32x4 *>(noise + (size_t)b * flat + 4 * qd)
+                    : philox_normal4(seed, (uint64_t)(goff + b), 0u, (uint32_t)qd);
+    if (w.x_init) {
+        const int64_t row = w.kind == XINIT_SHARED ? 0 : w.kind == XINIT_PER_CAND ? b : b / w.group;
+        z = q_sample4(w.sa, w.sb, *reinterpret_cast<const f32x4 *>(w.x_init + (size_t)row * flat + 4 * qd), z);
+    }
     *reinterpret_cast<f32x4 *>(x + (size_t)b * flat + 4 * qd) = z;
     if (chain) *reinterpret_cast<f32x4 *>(chain + (size_t)b * flat + 4 * qd) = z;
 }
@@ -916,7 +927,7 @@ int sample_fused(const mpcd_net_desc &d, const UnetWeights &W, const UnetSampleA
     const int threads = 256;
     const unsigned g1 = (unsigned)((a.batch * (flat / 4) + threads - 1) / threads);
     hipLaunchKernelGGL(init_x_kernel, dim3(g1), dim3(threads), 0, st, xs, a.batch, flat, a.noise, a.seed,
-                       a.global_offset, a.chain);
+                       a.global_offset, a.chain, WarmInit{a.x_init, a.x_init_kind, a.x_group, a.x_sa, a.x_sb});
     f.x = xs;
     // diagnostics: MPCD_FUSED_PROF=<file> writes the per-op s_memtime stamps of the third step's first workgroups
     static const char *prof_path = getenv("MPCD_FUSED_PROF");
@@ -1012,7 +1023,7 @@ int unet_sample(const mpcd_net_desc &d, const UnetWeights &W, const UnetSampleAr
     }
     uint32_t *amq = a.chain_absmax ? reinterpret_cast<uint32_t *>(xs + (size_t)a.batch * flat) : nullptr;
     hipLaunchKernelGGL(init_x_kernel, dim3(g1), dim3(threads), 0, st, xs, a.batch, flat, a.noise, a.seed,
-                       a.global_offset, a.chain);
+                       a.global_offset, a.chain, WarmInit{a.x_init, a.x_init_kind, a.x_group, a.x_sa, a.x_sb});
     for (int s = 0; s < a.n_steps; ++s) {
         c.tp = a.tproj + (size_t)s * a.cond_total;
         int rc = forward(c, m, B, xs, a.batch);

@@ -271,7 +271,50 @@ class DiffusionMPC:
         a.chain_absmax = absmax.data_ptr() if absmax is not None else None
         return a
 
-    def n_denoise_steps(self, sample_fn="ddpm_cfg", n_wo_noise=0, ddim_steps=None):
+    def _warm(self, x_init, t_start, batch, group=None):
+        """(mpcd_warm_start, the prior tensor it points to) of a sample call, checked; t_start 0: a cold start."""
+        K = int(t_start)
+        if K < 0 or K > self.n_steps:
+            raise ValueError(f"t_start={K} must be in [0, {self.n_steps}]")
+        w = N.WarmStart()
+        w.t_start = K
+        if K == 0:
+            return w, None
+        if x_init is None:
+            raise ValueError("t_start > 0 needs x_init (the normalised prior plan)")
+        H, d = self.spec.horizon, self.spec.state_dim
+        x_init = torch.as_tensor(x_init, dtype=torch.float32)
+        if x_init.dim() == 2:
+            x_init = x_init[None]
+        allowed = [1, batch] + ([batch // group] if group else [])
+        if x_init.dim() != 3 or tuple(x_init.shape[1:]) != (H, d) or x_init.shape[0] not in allowed:
+            raise ValueError(f"x_init must be [rows, {H}, {d}] with rows one of {sorted(set(allowed))} "
+                             f"(1, n_samples{', n_samples / context_group' if group else ''}), got {tuple(x_init.shape)}")
+        x_init = x_init.to(self.device).contiguous()
+        w.x_init = x_init.data_ptr()
+        w.rows = x_init.shape[0]
+        return w, x_init
+
+    def shift_plans(self, u_norm, index=None, index_offset=0, out=None):
+        """The next warm-start priors (mpcd_shift_plans): out[m, h] = u_norm[index[m] - index_offset, min(h + 1, H - 1)],
+        each chosen candidate's normalised plan moved one horizon point ahead with its last point repeated.
+        u_norm [B, H, d] device fp32; index: device int64 [M] global candidate indices (closed_loop's / mpc_step's
+        winners), None = every row of u_norm. Returns out [M, H, d]."""
+        B, H, d = u_norm.shape
+        u_norm = u_norm.contiguous()
+        M = B if index is None else int(index.numel())
+        if index is not None and (index.dtype != torch.int64 or index.device != self.device or not index.is_contiguous()):
+            raise ValueError(f"index must be a contiguous int64 tensor on {self.device}")
+        if out is None:
+            out = torch.empty((M, H, d), dtype=torch.float32, device=self.device)
+        N.check(self._lib.mpcd_shift_plans(self._ctx, ctypes.c_void_p(u_norm.data_ptr()), B, H,
+                                           ctypes.c_void_p(index.data_ptr()) if index is not None else None,
+                                           int(index_offset), M, ctypes.c_void_p(out.data_ptr()), self._stream()),
+                "mpcd_shift_plans")
+        return out
+
+    def n_denoise_steps(self, sample_fn="ddpm_cfg", n_wo_noise=0, ddim_steps=None, t_start=None):
+        """Denoise steps S of a sample call; t_start=K (warm start, CFG-DDPM): K + n_wo_noise."""
         a = N.SampleArgs()
         a.sampler = self._sampler_id(sample_fn)
         a.n_wo_noise = n_wo_noise
@@ -282,12 +325,21 @@ class DiffusionMPC:
             a.ddim_times = ctypes.cast(self._times, ctypes.POINTER(ctypes.c_int32))
             a.n_ddim_times = len(times)
         n = ctypes.c_int32()
-        N.check(self._lib.mpcd_sample_steps(self._ctx, ctypes.byref(a), ctypes.byref(n)), "mpcd_sample_steps")
+        if t_start is None:
+            N.check(self._lib.mpcd_sample_steps(self._ctx, ctypes.byref(a), ctypes.byref(n)), "mpcd_sample_steps")
+        else:
+            if int(t_start) < 0 or int(t_start) > self.n_steps:
+                raise ValueError(f"t_start={int(t_start)} must be in [0, {self.n_steps}]")
+            w = N.WarmStart()
+            w.t_start = int(t_start)
+            N.check(self._lib.mpcd_sample_steps_warm(self._ctx, ctypes.byref(a), ctypes.byref(w), ctypes.byref(n)),
+                    "mpcd_sample_steps_warm")
         return n.value
 
     def sample_trajectories(self, context=None, n_samples=1, horizon=None, w=0.01, sample_fn="ddpm_cfg",
                             n_wo_noise=0, ddim_steps=None, clamp_x0=False, seed=0, global_offset=0, noise=None,
-                            return_chain=False, out=None, absmax_out=None, context_group=None):
+                            return_chain=False, out=None, absmax_out=None, context_group=None, x_init=None,
+                            t_start=None):
         """Normalised candidate trajectories [B, H, d] (or the chain [S+1, B, H, d]).
         context: [1, C] (shared) or [B, C] normalised fp32; noise: optional injected [S+1, B, H, d].
         context_group=g: context is [B / g, C], candidate b uses row b // g (mpcd_sample_grouped: a closed-loop
@@ -295,7 +347,14 @@ class DiffusionMPC:
         [B, C] context runs the exact-f32 one). Anything but B / g rows raises ValueError.
         absmax_out: optional fp32 [B] device tensor <- per candidate max |x| over the whole chain
         (x_T .. x_0; NaN if any NaN): the input of the reference's chain-wide clip test without
-        materialising the chain."""
+        materialising the chain.
+        t_start=K with x_init (warm start, CFG-DDPM only; mpcd_sample_warm): the chain starts at the prior plan
+        x_init noised to level K, x = sqrt_alphas_cumprod[K-1] x_init + sqrt_one_minus_alphas_cumprod[K-1] z0 (the
+        reference's q_sample at t = K - 1, z0 = noise slice 0), and runs the last K steps only: S = K + n_wo_noise,
+        noise / chain are [S+1, B, H, d] with chain[0] the noised prior. x_init: normalised [1, H, d] (or [H, d]; one
+        prior for all), [B, H, d] (one per candidate) or, with context_group=g, [B / g, H, d] (one per context row);
+        other shapes raise ValueError. t_start=0 is a cold start through the same entry point; None (default) is
+        today's call."""
         H = horizon or self.spec.horizon
         if H != self.spec.horizon:
             raise ValueError(f"net was built for horizon {self.spec.horizon}")
@@ -307,7 +366,7 @@ class DiffusionMPC:
             if context.dim() == 1:
                 context = context[None]
             context = context.to(self.device).contiguous()
-        steps = self.n_denoise_steps(sample_fn, n_wo_noise, ddim_steps)
+        steps = self.n_denoise_steps(sample_fn, n_wo_noise, ddim_steps, t_start if t_start else None)
         if noise is not None:
             noise = noise.to(self.device, torch.float32).contiguous()
             if tuple(noise.shape) != (steps + 1, B, H, d):
@@ -326,9 +385,13 @@ class DiffusionMPC:
         group = None if context_group is None else int(context_group)
         a = self._args(sampler, B, context, w, n_wo_noise, ddim_steps, clamp_x0, seed, global_offset, noise, x, chain,
                        amax, group)
+        warm = None if t_start is None else self._warm(x_init, t_start, B, group)
 
         def run(what):
-            if group is None:
+            if warm is not None:
+                N.check(self._lib.mpcd_sample_warm(self._ctx, ctypes.byref(a), group or 0, ctypes.byref(warm[0]),
+                                                   self._stream()), what.replace("mpcd_sample", "mpcd_sample_warm"))
+            elif group is None:
                 N.check(self._lib.mpcd_sample(self._ctx, ctypes.byref(a), self._stream()), what)
             else:
                 N.check(self._lib.mpcd_sample_grouped(self._ctx, ctypes.byref(a), group, self._stream()),
@@ -465,7 +528,7 @@ class DiffusionMPC:
 
     def closed_loop(self, x0_states, system: System, iterations, n_samples=1, w=0.01, sample_fn="ddpm_cfg",
                     n_wo_noise=0, ddim_steps=None, clamp_x0=False, select="argmin", decimals=4, seed=0, noise=None,
-                    clip_rule="chain", grouped=False):
+                    clip_rule="chain", grouped=False, warm_start=None):
         """Closed-loop diffusion MPC for M plant states at once, resident on the device.
         The reference runs one initial state at a time on the host (Cart_Diffusion_inference.py:405-512:
         normalize_condition -> run_CFG -> unnormalize -> u0 = round(u[0], 4) -> x = f(x, u0), repeated
@@ -484,7 +547,16 @@ class DiffusionMPC:
         where grouped_pays() says so. noise: optional callable it -> injected sampler
         noise [S+1, M*n_samples, H, d] (parity tests); default in-kernel Philox keyed by (seed + it).
         clip_rule: "chain" (the reference: run_CFG(return_chain=True) then unnormalize_states of the whole
-        chain, so each state's clip test also sees its x_T) or "final" (the final samples only)."""
+        chain, so each state's clip test also sees its x_T) or "final" (the final samples only).
+        warm_start=K (CFG-DDPM, 1 <= K <= N): iteration 0 samples cold; after every control step each state's
+        selected plan, moved one horizon point ahead (mpcd_shift_plans on the step's winners), becomes its prior, and
+        the later iterations sample from it with t_start=K (see sample_trajectories): K + n_wo_noise denoise steps
+        instead of N + n_wo_noise. grouped=True where grouped_pays(): the [M, H, d] priors go in as they are; else
+        they are repeated per candidate like the contexts. noise(it) must then return K + n_wo_noise + 1 slices for
+        it >= 1. Under clip_rule="chain" a warm iteration's clip test sees the noised prior, not x_T."""
+        K = None if warm_start is None else int(warm_start)
+        if K is not None and (K < 1 or K > self.n_steps or self._sampler_id(sample_fn) != N.MPCD_DDPM_CFG):
+            raise ValueError(f"warm_start={K} needs 1 <= K <= {self.n_steps} and the CFG-DDPM sampler")
         if select not in ("argmin", "first"):
             raise ValueError("select must be 'argmin' or 'first'")
         if clip_rule not in _CLIP_RULES:
@@ -511,13 +583,17 @@ class DiffusionMPC:
         absmax = torch.empty(B, dtype=torch.float32, device=dev) if clip_rule == "chain" else None
         ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         grouped = bool(grouped) and self.grouped_pays(M, n, sample_fn)
+        priors = torch.empty((M, H, d), dtype=torch.float32, device=dev) if K is not None else None
         xs[0] = x
         for it in range(T):
+            warm = {}
+            if K is not None and it > 0:
+                warm = dict(x_init=priors if grouped else priors.repeat_interleave(n, dim=0), t_start=K)
             N.check(self._lib.mpcd_normalize_states(self._ctx, ptr(x), M, nx, self.ctx_min.ctypes.data,
                                                     self.ctx_max.ctypes.data, ptr(ctx), st), "mpcd_normalize_states")
             self.sample_trajectories(ctx if grouped else ctx.repeat_interleave(n, dim=0), B, H, w, sample_fn, n_wo_noise,
                                      ddim_steps, clamp_x0, seed + it, 0, None if noise is None else noise(it), False,
-                                     out=u_norm, absmax_out=absmax, context_group=n if grouped else None)
+                                     out=u_norm, absmax_out=absmax, context_group=n if grouped else None, **warm)
             if absmax is not None:  # each state's flag over its candidates' chains
                 N.check(self._lib.mpcd_clip_flags(self._ctx, ptr(absmax), M, n, ptr(flags), st), "mpcd_clip_flags")
             else:
@@ -529,12 +605,15 @@ class DiffusionMPC:
                                                 self.act_min.ctypes.data, self.act_max.ctypes.data, ptr(flags),
                                                 1 if select == "first" else 0, -1 if decimals is None else int(decimals),
                                                 ptr(us[it]), ptr(ix[it]), ptr(cs[it]), st), "mpcd_control_step")
+            if K is not None:
+                self.shift_plans(u_norm, ix[it], 0, out=priors)
             xs[it + 1] = x
         return ClosedLoopResult(x=xs.transpose(0, 1).cpu().numpy(), u=us.transpose(0, 1).cpu().numpy(),
                                 cost=cs.t().cpu().numpy(), index=ix.t().cpu().numpy())
 
     def mpc_step(self, x0, system: System, n_samples, w=0.01, sample_fn="ddpm_cfg", n_wo_noise=0, ddim_steps=None,
-                 clamp_x0=False, seed=0, noise=None, group=None, comm=None, native=None, clip_rule="chain"):
+                 clamp_x0=False, seed=0, noise=None, group=None, comm=None, native=None, clip_rule="chain",
+                 warm_start=None, prior=None):
         """One control step: sample n_samples candidates on this rank (weak scaling: every rank adds
         n_samples), roll out + cost them, all-gather costs, pick the global argmin, broadcast it.
         comm: a distributed.NativeComm (the exchange inside libmpcd.so over RCCL) or None
@@ -546,7 +625,14 @@ class DiffusionMPC:
         reference scripts, which call run_CFG(return_chain=True) and unnormalise the whole chain
         (Cart_Diffusion_inference.py:450-463, Diffusion_MPC_Inference.py:232-247), so x_T ~ N(0, 1) is in
         the test; "final" = the final samples only (proven 0 for DDPM when the last posterior mean cannot
-        leave [-1, 1], then no reduction is run)."""
+        leave [-1, 1], then no reduction is run).
+        warm_start=K (native step, CFG-DDPM, 1 <= K <= N; mpcd_mpc_step_warm): receding-horizon warm start. The
+        planner keeps the winner's normalised plan, moved one horizon point ahead, on the device as the next call's
+        prior: the first warm-enabled call (no prior yet) runs the full chain and fills it, later calls denoise only
+        K steps from the prior noised to level K (noise then has K + n_wo_noise + 1 slices) and refresh it.
+        reset_warm_start() drops the prior (a new episode); prior= (normalised [H, d]) overrides it for this call.
+        Under clip_rule="chain" a warm step's test sees the noised prior instead of x_T, so the clip is no longer
+        practically certain. What K costs in control quality depends on the model: measure it."""
         if clip_rule not in _CLIP_RULES:
             raise ValueError(f"clip_rule must be one of {sorted(_CLIP_RULES)}")
         if comm is not None:
@@ -559,7 +645,9 @@ class DiffusionMPC:
             if size > 1 and comm is None:
                 raise ValueError("native mpc_step on several ranks needs a NativeComm")
             return self._mpc_step_native(x0, system, n_samples, w, sample_fn, n_wo_noise, ddim_steps, clamp_x0, seed,
-                                         noise, comm, clip_rule)
+                                         noise, comm, clip_rule, warm_start, prior)
+        if warm_start is not None or prior is not None:
+            raise ValueError("warm_start / prior need the native step (native=True)")
         offset = rank * n_samples
         ctx = torch.from_numpy(self.normalize_condition(x0)[None]) if self.spec.context_dim > 0 else None
         absmax = torch.empty(n_samples, dtype=torch.float32, device=self.device) if clip_rule == "chain" else None
@@ -585,8 +673,17 @@ class DiffusionMPC:
         return MPCResult(u0=u_host[0].copy(), u_best=u_host, best_cost=best, best_index=idx, costs=costs,
                          u_norm=u_norm)
 
+    def reset_warm_start(self):
+        """Drop the prior plan mpc_step(warm_start=K) keeps: the next warm-enabled call starts cold."""
+        self._prior = self._prior_spare = None
+
+    def warm_prior(self):
+        """The normalised prior plan [H, d] the next mpc_step(warm_start=K) starts from (device), or None."""
+        p = getattr(self, "_prior", None)
+        return None if p is None else p[0]
+
     def _mpc_step_native(self, x0, system, n_samples, w, sample_fn, n_wo_noise, ddim_steps, clamp_x0, seed, noise,
-                         comm, clip_rule="chain"):
+                         comm, clip_rule="chain", warm_start=None, prior=None):
         """mpc_step as one libmpcd call (mpcd_mpc_step): one H2D copy of the context row, the kernels,
         the result block {best, u_best} written to pinned host memory by the selecting workgroup (one rank) or one
         D2H copy + stream synchronisation (with a communicator)."""
@@ -595,8 +692,22 @@ class DiffusionMPC:
         if d != system.n_u:
             raise ValueError(f"system {system.name} has {system.n_u} inputs, samples have {d}")
         sampler = self._sampler_id(sample_fn)
+        warm = None
+        if warm_start is not None or prior is not None:
+            K = int(warm_start) if warm_start is not None else 0
+            if K < 1 or K > self.n_steps or sampler != N.MPCD_DDPM_CFG:
+                raise ValueError(f"warm_start={warm_start} needs 1 <= K <= {self.n_steps} and the CFG-DDPM sampler")
+            if prior is None:
+                prior = getattr(self, "_prior", None)
+            # no prior yet: a cold step (t_start 0) that fills it
+            warm, prior = self._warm(prior, K if prior is not None else 0, B)
+            if prior is not None and prior.shape[0] != 1:
+                raise ValueError(f"prior must be one plan [{H}, {d}], got {tuple(prior.shape)}")
+            nxt = getattr(self, "_prior_spare", None)
+            if nxt is None or (prior is not None and nxt.data_ptr() == prior.data_ptr()):
+                nxt = torch.empty((1, H, d), dtype=torch.float32, device=self.device)
         if noise is not None:
-            steps = self.n_denoise_steps(sample_fn, n_wo_noise, ddim_steps)
+            steps = self.n_denoise_steps(sample_fn, n_wo_noise, ddim_steps, warm.t_start or None if warm else None)
             noise = noise.to(self.device, torch.float32).contiguous()
             if tuple(noise.shape) != (steps + 1, B, H, d):
                 raise ValueError(f"noise must be [{steps + 1}, {B}, {H}, {d}], got {tuple(noise.shape)}")
@@ -633,8 +744,15 @@ class DiffusionMPC:
         a.costs_all = costs.data_ptr()
         u_best = np.empty((H, d), dtype=np.float32)
         # MPCD_ENONFINITE (no candidate with a finite cost: NaN / Inf samples) raises MpcdError here
-        N.check(self._lib.mpcd_mpc_step(self._ctx, a_ref, ctypes.byref(best), u_best.__array_interface__["data"][0],
-                                        self._stream()), "mpcd_mpc_step")
+        if warm is None:
+            N.check(self._lib.mpcd_mpc_step(self._ctx, a_ref, ctypes.byref(best), u_best.__array_interface__["data"][0],
+                                            self._stream()), "mpcd_mpc_step")
+        else:
+            N.check(self._lib.mpcd_mpc_step_warm(self._ctx, a_ref, ctypes.byref(warm), ctypes.c_void_p(nxt.data_ptr()),
+                                                 ctypes.byref(best), u_best.__array_interface__["data"][0],
+                                                 self._stream()), "mpcd_mpc_step_warm")
+            # the refreshed prior becomes the next call's; this call's buffer is the next one's output
+            self._prior, self._prior_spare = nxt, getattr(self, "_prior", None)
         N.check(self._lib.mpcd_last_step_flags(self._ctx, ctypes.byref(fl)), "mpcd_last_step_flags")
         return MPCResult(u0=u_best[0].copy(), u_best=u_best, best_cost=best.cost, best_index=best.index, costs=costs,
                          u_norm=u_norm, flags=fl.value)
