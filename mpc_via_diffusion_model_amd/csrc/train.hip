@@ -39,66 +39,10 @@ MPCD_DEV float rowsum_step(const float (&As)[GK][GT + 1], float acc)
 }
 
 // C[m][n] (ldc) = beta * C + sum_k A(m,k) B(k,n) (+ bias[n]); A(m,k) = a[m*sam + k*sak], B(k,n) = b[k*sbk + n*sbn].
-// 256 threads, each a 4x4 block of C; the k-sum runs in k order per output (fp32 FMA off: -ffp-contract=off).
+// On the fp32 matrix cores: v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulate), the k-sum in k order per
+// output. 256 threads = 4 waves, each a 32x32 quarter of the 64x64 tile as 2x2 MFMA tiles, operands staged in LDS.
 // Split K (gridDim.z > 1): slice z sums k in [z*kchunk, (z+1)*kchunk) into c + z*zstride (beta 0, no bias);
 // splitk_reduce_kernel then adds the slices in z order (deterministic).
-__global__ __launch_bounds__(256) void gemm_kernel(int M, int N, int K, const float *__restrict__ a, int64_t sam,
-                                                   int64_t sak, const float *__restrict__ b, int64_t sbk, int64_t sbn,
-                                                   float *__restrict__ c, int64_t ldc, float beta,
-                                                   const float *__restrict__ bias, int kchunk, int64_t zstride,
-                                                   float *__restrict__ rs)
-{
-    __shared__ float As[GK][GT + 1], Bs[GK][GT + 1];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int m0 = blockIdx.y * GT, n0 = blockIdx.x * GT;
-    const int kb = blockIdx.z * kchunk, ke = min(K, kb + kchunk);
-    c += blockIdx.z * zstride;
-    float acc[4][4] = {};
-    const bool rsum = rs && blockIdx.x == 0 && threadIdx.x < GT;
-    float rsacc = 0.f;
-    for (int k0 = kb; k0 < ke; k0 += GK) {
-        for (int i = threadIdx.x; i < GK * GT; i += 256) {
-            const int kk = i / GT, r = i % GT;
-            const int m = m0 + r, n = n0 + r, k = k0 + kk;
-            As[kk][r] = (m < M && k < ke) ? a[m * sam + k * sak] : 0.f;
-            Bs[kk][r] = (n < N && k < ke) ? b[k * sbk + n * sbn] : 0.f;
-        }
-        __syncthreads();
-        if (rsum) rsacc = rowsum_step(As, rsacc);
-#pragma unroll
-        for (int kk = 0; kk < GK; ++kk) {
-            float av[4], bv[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                av[i] = As[kk][ty + 16 * i];
-                bv[i] = Bs[kk][tx + 16 * i];
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] += av[i] * bv[j];
-        }
-        __syncthreads();
-    }
-    if (rsum && m0 + (int)threadIdx.x < M) rs[blockIdx.z * (int64_t)M + m0 + threadIdx.x] = rsacc;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m0 + ty + 16 * i;
-        if (m >= M) continue;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = n0 + tx + 16 * j;
-            if (n >= N) continue;
-            float v = acc[i][j];
-            if (bias) v += bias[n];
-            float *p = c + m * ldc + n;
-            *p = beta != 0.f ? *p + v : v;
-        }
-    }
-}
-
-// The same contract on the fp32 matrix cores: v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulate).
-// 4 waves, each a 32x32 quarter of the 64x64 tile as 2x2 MFMA tiles; the LDS staging is gemm_kernel's.
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void gemm_mfma_kernel(int M, int N, int K, const float *__restrict__ a, int64_t sam,
                                                         int64_t sak, const float *__restrict__ b, int64_t sbk,
@@ -599,15 +543,6 @@ struct Trainer {
         }
         return ws;
     }
-    // the fp32 MFMA GEMM (default) or the VALU one (MPCD_TRAIN_GEMM=valu)
-    static decltype(&gemm_kernel) gemm_fn()
-    {
-        static const bool valu = [] {
-            const char *e = getenv("MPCD_TRAIN_GEMM");
-            return e && !strcmp(e, "valu");
-        }();
-        return valu ? &gemm_kernel : &gemm_mfma_kernel;
-    }
     hipError_t gemm(int M, int N, int K, const float *a, int64_t sam, int64_t sak, const float *b, int64_t sbk,
                     int64_t sbn, float *c, int64_t ldc, float beta, const float *bias, float *db = nullptr)
     {
@@ -625,8 +560,8 @@ struct Trainer {
             if (!part) return hipErrorOutOfMemory;
             float *rs = db ? part + mn * z : nullptr;
             g.z = z;
-            hipLaunchKernelGGL(gemm_fn(), g, dim3(256), 0, st, M, N, K, a, sam, sak, b, sbk, sbn, part, (int64_t)N, 0.f,
-                               (const float *)nullptr, kchunk, mn, rs);
+            hipLaunchKernelGGL(gemm_mfma_kernel, g, dim3(256), 0, st, M, N, K, a, sam, sak, b, sbk, sbn, part, (int64_t)N,
+                               0.f, (const float *)nullptr, kchunk, mn, rs);
             hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid_for(mn)), dim3(256), 0, st, M, N, z, (const float *)part, c,
                                ldc, beta, bias);
             if (db)
@@ -636,8 +571,8 @@ struct Trainer {
         }
         float *rs = nullptr;
         if (db && !(rs = workspace(M))) return hipErrorOutOfMemory;
-        hipLaunchKernelGGL(gemm_fn(), g, dim3(256), 0, st, M, N, K, a, sam, sak, b, sbk, sbn, c, ldc, beta, bias, K,
-                           (int64_t)0, rs);
+        hipLaunchKernelGGL(gemm_mfma_kernel, g, dim3(256), 0, st, M, N, K, a, sam, sak, b, sbk, sbn, c, ldc, beta, bias,
+                           K, (int64_t)0, rs);
         if (db) hipLaunchKernelGGL(colsum_reduce_kernel, dim3((M + 255) / 256), dim3(256), 0, st, M, 1, (const float *)rs, db);
         return hipGetLastError();
     }

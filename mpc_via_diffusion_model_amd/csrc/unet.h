@@ -54,7 +54,6 @@ struct ConvMK {
     int alias;              // 1: the fp32 output tile reuses the staged-input LDS
     int stat_off;           // LDS byte offset of the GroupNorm statistics (then the per-channel table)
     int cpg_shift;          // log2(cout / groups)
-    int skip;               // experiment only (MPCD_UNET_SKIP): bit 0 staging, 1 GEMM, 2 statistics, 3 epilogue
     // LDS placement (set by unet_launch_mx / unet_launch_mx_rtb): staged input planes and fp32 tile
     int in_off, out_off;
     // fused ResidualTemporalBlock, first conv only: the epilogue writes its result as the second
@@ -63,12 +62,6 @@ struct ConvMK {
     int lds_out, nx_off, nx_cs, nx_win, nx_halo_l;
     // fp16 activation buffers (f16 net): input (xa / xb), residual, output hold halves, not floats
     int in_h, res_h, out_h;
-    int layer;              // index of the conv in UnetWeights::layers (diagnostics)
-    // first-generation stagger (non-persistent grids): workgroup b < stag_ncu * stag_slots sleeps
-    // (b / stag_ncu) * stag_units x s_sleep(32), so the co-resident workgroups of a CU run their
-    // staging / GEMM / epilogue phases out of step instead of all at once
-    int stag_units, stag_ncu, stag_slots;
-    uint32_t *wgtrace;      // diagnostics (MPCD_UNET_WGTRACE): per workgroup {start, end, HW_ID, XCC_ID}
 };
 
 // Whole-network-per-workgroup form (unet_fused.hip): the op program and its LDS placement.
@@ -155,8 +148,7 @@ struct UnetFusedStep {
 };
 // planes: the program's numerics (0: the net's own - W.fused_planes, else W.planes; 3: the split-bf16 program of an
 // MPCD_F16X2 net)
-UnetFusedPlan *unet_fused_prepare(const mpcd_net_desc &d, const UnetWeights &W, int rows_per_wg, std::string *why,
-                                  int planes = 0);
+UnetFusedPlan *unet_fused_prepare(const mpcd_net_desc &d, const UnetWeights &W, std::string *why, int planes = 0);
 size_t unet_fused_scratch_bytes(const UnetFusedPlan &pl, int64_t batch);
 // true: the fused launch writes each branch's eps (one row per workgroup) and the CFG update runs as its own launch
 bool unet_fused_split_update(const UnetFusedPlan &pl);

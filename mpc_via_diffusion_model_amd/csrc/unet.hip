@@ -529,13 +529,10 @@ int unet_prepare(const mpcd_net_desc &d, size_t, const TensorLookup &dev, const 
     W.fused.reset();
     W.fused3.reset();
     W.fused_why.clear();
-    // MPCD_FUSED_ROWS=<R>: the fused program with R rows per workgroup (tuning experiments; default: the first
-    // instantiated configuration of the net's numerics and horizon)
-    static const int fused_rows = getenv("MPCD_FUSED_ROWS") ? atoi(getenv("MPCD_FUSED_ROWS")) : 0;
-    if (UnetFusedPlan *fp = unet_fused_prepare(d, W, fused_rows, &W.fused_why)) W.fused.reset(fp, unet_fused_free);
+    if (UnetFusedPlan *fp = unet_fused_prepare(d, W, &W.fused_why)) W.fused.reset(fp, unet_fused_free);
     std::string why3;
     if (h2)
-        if (UnetFusedPlan *fp = unet_fused_prepare(d, W, 0, &why3, 3)) W.fused3.reset(fp, unet_fused_free);
+        if (UnetFusedPlan *fp = unet_fused_prepare(d, W, &why3, 3)) W.fused3.reset(fp, unet_fused_free);
     return MPCD_OK;
 }
 
@@ -595,14 +592,10 @@ struct Ctx {
     // (first conv's input) and eps (last conv's output) stay fp32
     bool act_h;
     const float *x_in, *eps_out;
-    int act_mask;             // experiment knob (MPCD_UNET_F16_ACT): which buffers are fp16
     const float *hbuf[8];
     bool is_h(const float *p) const
     {
-        if (!act_h || !p) return false;
-        for (int i = 0; i < 8; ++i)
-            if (p == hbuf[i]) return (act_mask >> i) & 1;
-        return false;
+        return act_h && p && std::find(hbuf, hbuf + 8, p) != hbuf + 8;
     }
 };
 
@@ -673,7 +666,6 @@ ConvMK make_mk(const Ctx &c, const ConvLayer &L, int epi, const float *xa, int c
     k.in_h = c.is_h(xa);
     k.res_h = c.is_h(res);
     k.out_h = c.is_h(out);
-    k.layer = (int)(&L - c.W->layers.data());
     return k;
 }
 
@@ -1002,11 +994,7 @@ int unet_sample(const mpcd_net_desc &d, const UnetWeights &W, const UnetSampleAr
     c.cp = a.cproj;
     c.cp_stride = a.cproj_stride;
     c.st = st;
-    {
-        const char *e = getenv("MPCD_UNET_F16_ACT");  // experiment knob: 0 keeps fp32 activations
-        c.act_mask = e && e[0] ? atoi(e) : 255;
-        c.act_h = W.planes == 1 && c.act_mask != 0;
-    }
+    c.act_h = W.planes == 1;
     const int threads = 256;
     const int64_t nq = a.batch * (flat / 4);
     const unsigned g1 = (unsigned)((nq + threads - 1) / threads);

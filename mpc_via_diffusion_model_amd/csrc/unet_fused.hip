@@ -67,11 +67,6 @@ struct COp {
     int spill;             // also write the output to the skip scratch (RESTORE: read it back)
     CView in, res, out;
 };
-// MPCD_FUSED_GN1 = 1: GroupNorm statistics in one pass (sums and sums of squares reduced together,
-// var = E[x^2] - mean^2) instead of the exact two-pass; experiment switch
-#ifndef MPCD_FUSED_GN1
-#define MPCD_FUSED_GN1 0
-#endif
 constexpr int kMaxOps = 40;
 struct Prog {
     COp ops[kMaxOps];
@@ -272,7 +267,6 @@ struct FArgs {
     uint32_t *amq;
     float *eps_c, *eps_u;  // MODE_EPS outputs
     char *scratch;         // skip spill: [row][L][C], fp16 (P = 1) or fp32 (P = 3)
-    int64_t nblk;          // row blocks of R rows; workgroup b runs blocks b, b + gridDim.x, ... (persistent grid)
     uint64_t *prof;        // diagnostics (MPCD_FUSED_PROF) or null: per workgroup < kProfWgs and op, wave 0's
                            // s_memtime at op start / GEMM done / statistics done / op done
 };
@@ -656,38 +650,6 @@ MPCD_DEV void conv_op(const FArgs &a, int64_t cand0, int64_t row0, int brn, APre
         };
         int slot[NTW];
         float m[NTW];
-#if MPCD_FUSED_GN1
-        // one pass, one barrier: both partial sums of each part of the row through LDS together
-#pragma unroll
-        for (int j = 0; j < NTW; ++j) {
-            slot[j] = (row * kGroups + (n0[j] >> op.cpg_sh)) * kWprMax;
-            f32x2 p1 = lo2(acc[j][0]) + hi2(acc[j][0]);
-            f32x2 p2 = fma2(hi2(acc[j][0]), hi2(acc[j][0]), lo2(acc[j][0]) * lo2(acc[j][0]));
-#pragma unroll
-            for (int cc = 1; cc < NCW; ++cc) {
-                const f32x2 a0 = lo2(acc[j][cc]), a1 = hi2(acc[j][cc]);
-                p1 += a0 + a1;
-                p2 = fma2(a1, a1, fma2(a0, a0, p2));
-            }
-            float ss[2] = {p1[0] + p1[1], p2[0] + p2[1]};
-            group_sum_n<16, QMASK, 2>(ss);
-            if (leader) {
-                st[slot[j] + part] = ss[0];
-                st[S2 + slot[j] + part] = ss[1];
-            }
-        }
-        lds_barrier();
-#pragma unroll
-        for (int j = 0; j < NTW; ++j) {
-            m[j] = sum_parts(st + slot[j]) * inv_n;
-            const float rs = rsqrt_nr(fmaxf(sum_parts(st + S2 + slot[j]) * inv_n - m[j] * m[j], 0.f) + 1e-5f);
-#pragma unroll
-            for (int cc = 0; cc < NCW; ++cc) {
-                mean[j][cc] = m[j];
-                rstd[j][cc] = rs;
-            }
-        }
-#else
 #pragma unroll
         for (int j = 0; j < NTW; ++j) {
             slot[j] = (row * kGroups + (n0[j] >> op.cpg_sh)) * kWprMax;
@@ -721,46 +683,11 @@ MPCD_DEV void conv_op(const FArgs &a, int64_t cand0, int64_t row0, int brn, APre
                 rstd[j][cc] = rs;
             }
         }
-#endif
     } else if constexpr (GN) {  // every (row, group) inside the wave
         constexpr int L = op.lout, SEG = L < 16 ? L : 16, TPR = L > 16 ? L / 16 : 1;  // column tiles per row
         constexpr float inv_n = 1.0f / (float)(L << op.cpg_sh);
         static_assert(NCW % TPR == 0, "a wave's column tiles are whole rows");
         constexpr int NR = NCW / TPR, NS = NTW * NR;  // (n-tile, row) sums of the wave, reduced side by side
-#if MPCD_FUSED_GN1
-        // one pass: the sums and the sums of squares reduced side by side (one DPP chain's latency),
-        // var = E[x^2] - mean^2 (clamped at 0)
-        float ss[2 * NS];
-#pragma unroll
-        for (int j = 0; j < NTW; ++j)
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                f32x2 p1 = lo2(acc[j][r * TPR]) + hi2(acc[j][r * TPR]);
-                f32x2 p2 = fma2(hi2(acc[j][r * TPR]), hi2(acc[j][r * TPR]), lo2(acc[j][r * TPR]) * lo2(acc[j][r * TPR]));
-#pragma unroll
-                for (int t = 1; t < TPR; ++t) {
-                    const f32x2 a0 = lo2(acc[j][r * TPR + t]), a1 = hi2(acc[j][r * TPR + t]);
-                    p1 += a0 + a1;
-                    p2 = fma2(a1, a1, fma2(a0, a0, p2));
-                }
-                ss[j * NR + r] = p1[0] + p1[1];
-                ss[NS + j * NR + r] = p2[0] + p2[1];
-            }
-        group_sum_n<SEG, QMASK, 2 * NS>(ss);
-#pragma unroll
-        for (int j = 0; j < NTW; ++j)
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                const float m = ss[j * NR + r] * inv_n;
-                const float var = fmaxf(ss[NS + j * NR + r] * inv_n - m * m, 0.f);
-                const float rs = rsqrt_nr(var + 1e-5f);
-#pragma unroll
-                for (int t = 0; t < TPR; ++t) {
-                    mean[j][r * TPR + t] = m;
-                    rstd[j][r * TPR + t] = rs;
-                }
-            }
-#else
         float s1[NS], s2[NS];
 #pragma unroll
         for (int j = 0; j < NTW; ++j)
@@ -798,7 +725,6 @@ MPCD_DEV void conv_op(const FArgs &a, int64_t cand0, int64_t row0, int brn, APre
                     rstd[j][r * TPR + t] = rs;
                 }
             }
-#endif
     } else if constexpr (op.alias_in) {
         lds_barrier();
     }
@@ -938,7 +864,7 @@ MPCD_DEV void run_ops(const FArgs &a, int64_t cand0, int64_t row0, int brn, APre
     }
 }
 
-template <int P, int R, int H, int W, bool PERS>
+template <int P, int R, int H, int W>
 __global__ __launch_bounds__(64 * W) void unet_fused_kernel(const FArgs a)
 {
     constexpr int FT = 64 * W;
@@ -949,10 +875,7 @@ __global__ __launch_bounds__(64 * W) void unet_fused_kernel(const FArgs a)
     const int tid = threadIdx.x;
     const int d = a.d;
     APre<P> pre;
-    // Row blocks blockIdx.x, + gridDim.x, ...: a grid of one block per row block runs one iteration; a persistent
-    // grid (MPCD_FUSED_PERSIST) keeps each CU's workgroups walking the net together, block after block, so the
-    // weights of the ops in flight stay in the XCD's L2 instead of every late-starting workgroup re-fetching them.
-    for (int64_t blk = blockIdx.x; blk < a.nblk; blk += gridDim.x) {
+    const int64_t blk = blockIdx.x;  // one row block of R rows per workgroup
     // R = 1 (the fp32-accurate H = 128 net, whose three-plane activations fit the LDS only one row at a time):
     // workgroup blk runs branch blk & 1 of candidate blk >> 1 and writes that branch's eps; the CFG update of the
     // two branches runs as its own launch (unet.hip update_kernel)
@@ -990,9 +913,7 @@ __global__ __launch_bounds__(64 * W) void unet_fused_kernel(const FArgs a)
         if (cand0 < a.batch)
             for (int i = tid; i < quads; i += FT)
                 *reinterpret_cast<f32x4 *>(out + (size_t)cand0 * flat + 4 * i) = *reinterpret_cast<const f32x4 *>(E + 4 * i);
-        if constexpr (!PERS) break;
-        lds_barrier();
-        continue;
+        return;
     }
     const StepPlan sp = a.plan ? a.plan[a.s] : StepPlan{};
     for (int i = tid; i < RC * quads; i += FT) {
@@ -1021,9 +942,6 @@ __global__ __launch_bounds__(64 * W) void unet_fused_kernel(const FArgs a)
         if (a.chain) *reinterpret_cast<f32x4 *>(a.chain + (size_t)(a.s + 1) * a.batch * flat + off) = o;
         if (a.last && a.x_out != a.x) *reinterpret_cast<f32x4 *>(a.x_out + off) = o;
     }
-    if constexpr (!PERS) break;  // one block per workgroup: no loop-carried state (the registers of round 3)
-    lds_barrier();  // E (region Z) is read above; the next block stages x into region Z
-    }
 }
 
 // ---- host
@@ -1032,19 +950,27 @@ struct Cfg {
     int P, R, H, W;  // numerics planes, rows per workgroup, horizon, waves per workgroup
 };
 // the instantiated configurations (the LDS of R rows fits one CU: static_assert in the kernel)
-// the first match of (P, H) is the default; MPCD_FUSED_ROWS / MPCD_FUSED_WAVES pick another (experiments)
+// exactly one per (P, H): unet_fused_prepare takes the match
 // (1, 2, 64, 4): two or three 4-wave workgroups per CU, their barriers independent (cfg5 14.7 ms per CFG evaluation
 // vs 15.3 for one 8-wave workgroup of 4 rows); the split-bf16 nets keep 4-row blocks (their weights, three planes,
 // miss the L2 per block: cfg3 3.98 ms with 2-row blocks vs 3.58)
 // (3, 1, 128, 8): the fp32-accurate Panda net (H = 128), one row per workgroup, the CFG update as its own launch;
 // (2, R, H, 8): the two-term fp16 numerics (MPCD_F16X2) at the f32x3 row counts
 #define MPCD_FUSED_CFGS C_(1, 2, 64, 4) C_(3, 4, 32, 8) C_(1, 8, 32, 8) C_(3, 2, 64, 8) C_(1, 2, 128, 8) C_(3, 1, 128, 8) \
-    C_(2, 4, 32, 8) C_(2, 2, 64, 8) C_(2, 1, 128, 8) C_(1, 4, 64, 8) C_(1, 2, 64, 8) C_(3, 2, 32, 4)
+    C_(2, 4, 32, 8) C_(2, 2, 64, 8) C_(2, 1, 128, 8)
 constexpr Cfg kCfgs[] = {
 #define C_(p, r, h, w) {p, r, h, w},
     MPCD_FUSED_CFGS
 #undef C_
 };
+constexpr bool one_cfg_per_numerics_and_horizon()
+{
+    for (const Cfg &x : kCfgs)
+        for (const Cfg &y : kCfgs)
+            if (&x != &y && x.P == y.P && x.H == y.H) return false;
+    return true;
+}
+static_assert(one_cfg_per_numerics_and_horizon(), "kCfgs: one configuration per (P, H)");
 
 const Prog *prog_of(int P, int R, int H, int W)
 {
@@ -1055,39 +981,14 @@ const Prog *prog_of(int P, int R, int H, int W)
     return nullptr;
 }
 
-// MPCD_FUSED_PERSIST=1: a grid of (resident workgroups per CU) x CUs walking the row blocks (experiment switch)
-bool fused_persistent()
-{
-    static const bool on = [] {
-        const char *e = getenv("MPCD_FUSED_PERSIST");
-        return e && e[0] == '1';
-    }();
-    return on;
-}
-
 template <int P, int R, int H, int W>
 hipError_t launch_cfg(const FArgs &fa, unsigned grid, hipStream_t st)
 {
     constexpr size_t lds = ProgOf<P, R, H, W>::v.lds;
-    if (P == 1 || !fused_persistent()) {  // (f16 weights, 2 MB, stay L2-resident: no persistent form)
-        constexpr auto kfn = &unet_fused_kernel<P, R, H, W, false>;
-        if (hipError_t e = allow_max_lds<kfn>(); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * W), lds, st, fa);
-        return hipGetLastError();
-    }
-    if constexpr (P != 1) {
-        constexpr auto kfn = &unet_fused_kernel<P, R, H, W, true>;
-        if (hipError_t e = allow_max_lds<kfn>(); e != hipSuccess) return e;
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kfn), 64 * W, lds) !=
-                hipSuccess || per_cu < 1)
-            per_cu = 1;
-        const int64_t cap = (int64_t)per_cu * device_cu_count();
-        if (cap > 0 && cap < (int64_t)grid) grid = (unsigned)cap;
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * W), lds, st, fa);
-        return hipGetLastError();
-    }
-    return hipErrorInvalidValue;
+    constexpr auto kfn = &unet_fused_kernel<P, R, H, W>;
+    if (hipError_t e = allow_max_lds<kfn>(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * W), lds, st, fa);
+    return hipGetLastError();
 }
 
 hipError_t launch_any(int P, int R, int H, int W, const FArgs &fa, unsigned grid, hipStream_t st)
@@ -1115,8 +1016,7 @@ void unet_fused_free(UnetFusedPlan *p) { delete p; }
 
 // Check the compile-time program against the loaded net and build the weight-pointer table; nullptr (and *why)
 // when the net or the numerics are not covered (the layer-by-layer path runs it instead).
-UnetFusedPlan *unet_fused_prepare(const mpcd_net_desc &d, const UnetWeights &W, int rows_per_wg, std::string *why,
-                                  int planes)
+UnetFusedPlan *unet_fused_prepare(const mpcd_net_desc &d, const UnetWeights &W, std::string *why, int planes)
 {
     auto no = [&](const std::string &m) -> UnetFusedPlan * {
         if (why) *why = m;
@@ -1134,15 +1034,14 @@ UnetFusedPlan *unet_fused_prepare(const mpcd_net_desc &d, const UnetWeights &W, 
     if (W.n_layers != 35) return no("fused U-Net: unexpected layer count");
     const Prog *pg = nullptr;
     int R = 0, Wv = 0;
-    static const int waves = getenv("MPCD_FUSED_WAVES") ? atoi(getenv("MPCD_FUSED_WAVES")) : 0;  // experiments
     for (const Cfg &c : kCfgs)
-        if (c.P == P && c.H == H && (rows_per_wg <= 0 || rows_per_wg == c.R) && (waves <= 0 || waves == c.W)) {
+        if (c.P == P && c.H == H) {
             R = c.R;
             Wv = c.W;
             pg = prog_of(c.P, c.R, c.H, c.W);
             break;
         }
-    if (!pg) return no("fused U-Net: no instantiation for this horizon / numerics / rows per workgroup");
+    if (!pg) return no("fused U-Net: no instantiation for this horizon / numerics");
     std::vector<FPtr> ptrs(pg->n);
     for (int i = 0; i < pg->n; ++i) {
         const COp &o = pg->ops[i];
@@ -1222,6 +1121,5 @@ hipError_t unet_fused_step(const UnetFusedPlan &pl, const UnetFusedStep &s, hipS
     fa.prof = s.prof;
     const int64_t grid = fused_blocks(pl, s.batch);
     if (grid <= 0 || grid > 0x7fffffff) return hipErrorInvalidValue;
-    fa.nblk = grid;
     return launch_any(pl.P, pl.R, pl.H, pl.W, fa, (unsigned)grid, st);
 }

@@ -50,19 +50,10 @@ using namespace mx;
 constexpr int MT = 256;  // threads per workgroup
 // weight chunks in flight for the small f16 tiles (NN x NC <= 8): the GEMM phase of a 4-row block
 // streams the whole layer's weights from L2 for 64 columns, so its A loads are latency-bound
+constexpr int DA_SMALL = 4;
 // 16-byte staging loads / epilogue items each thread keeps in flight
-#ifndef MPCD_MX_SU
-#define MPCD_MX_SU 4
-#endif
-#ifndef MPCD_MX_EU
-#define MPCD_MX_EU 4
-#endif
-#ifndef MPCD_MX_TILE_H
-#define MPCD_MX_TILE_H 0
-#endif
-#ifndef MPCD_MX_DA_SMALL
-#define MPCD_MX_DA_SMALL 4
-#endif
+constexpr int SU = 4, EU = 4;
+constexpr size_t LDS_CAP = (size_t)160 * 1024;  // dynamic LDS a workgroup may ask for (allow_max_lds): one per CU
 
 // n / d and n % d for small non-negative n (< 2^20) via a float reciprocal + one correction step:
 // a handful of VALU ops instead of the ~20-op integer division sequence.
@@ -128,14 +119,6 @@ __device__ __forceinline__ void conv_mx_body(const ConvMK2 &as)
     extern __shared__ __attribute__((aligned(16))) char sm[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t t_start = as.ph[0].wgtrace ? (uint32_t)__builtin_amdgcn_s_memrealtime() : 0u;
-    if constexpr (!PERS) {
-        const ConvMK &a0 = as.ph[0];
-        if (a0.stag_units > 0 && (int64_t)blockIdx.x < (int64_t)a0.stag_ncu * a0.stag_slots) {
-            const int n = (int)(blockIdx.x / (unsigned)a0.stag_ncu) * a0.stag_units;
-            for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(32);
-        }
-    }
     static_assert(NPH == 1 || (!PERS && KIND == UCONV_SAME5), "fused pairs: 5-tap convs, one row block per workgroup");
     if constexpr (NPH == 2) {  // zero the halo positions of the second conv's staging window (rows rb)
         const ConvMK &a = as.ph[0];
@@ -219,7 +202,7 @@ __device__ __forceinline__ void conv_mx_body(const ConvMK2 &as)
     };
     auto stage_direct = [&](int64_t r0, int nrow) {
         if ((a.ca & 7) == 0 && (a.cb & 7) == 0) {
-            constexpr int SU = MPCD_MX_SU;  // items per thread in flight before any conversion or LDS store
+            // SU items per thread in flight before any conversion or LDS store
             for (int i0 = tid; i0 < n_items; i0 += SU * MT) {
                 f32x4 lo[SU], hi[SU];
                 int dst[SU];
@@ -282,16 +265,11 @@ __device__ __forceinline__ void conv_mx_body(const ConvMK2 &as)
     const int npj = (NT + NN - 1) / NN, ncg = (ctp + NC - 1) / NC;
     const int jobs = npj * ncg * npar;
     const int col = lane & 15, q = lane >> 4;
-    // pre-norm output tile in LDS: fp32, or fp16 for the fp16-operand net when MPCD_MX_TILE_H (half the LDS,
-    // so more workgroups share a CU; the conv's fp32 accumulators are rounded once to fp16 there)
-    using tile_t = typename std::conditional<P == 1 && MPCD_MX_TILE_H, _Float16, float>::type;
-    constexpr int TPAD = sizeof(tile_t) == 2 ? 8 : 4;
-    const int sout = a.coutp + TPAD;
+    // pre-norm output tile in LDS, fp32
+    using tile_t = float;
+    const int sout = a.coutp + 4;
     tile_t *s_out = reinterpret_cast<tile_t *>(sm + a.out_off);
-    auto tile_ld4 = [&](const tile_t *p) -> f32x4 {
-        if constexpr (sizeof(tile_t) == 2) return __builtin_convertvector(*reinterpret_cast<const f16x4 *>(p), f32x4);
-        else return *reinterpret_cast<const f32x4 *>(p);
-    };
+    auto tile_ld4 = [&](const tile_t *p) -> f32x4 { return *reinterpret_cast<const f32x4 *>(p); };
 
     const uint64_t wa = (uint64_t)a.w;
     const uint32_t wlo = __builtin_amdgcn_readfirstlane((uint32_t)wa), whi = __builtin_amdgcn_readfirstlane((uint32_t)(wa >> 32));
@@ -361,7 +339,7 @@ __device__ __forceinline__ void conv_mx_body(const ConvMK2 &as)
         // A (weights, L2) runs DA chunks ahead in a register ring; B (LDS) one chunk ahead. The
         // prefetches are unconditional (clamped to the last chunk) so the waits before each chunk's
         // MFMAs leave the younger loads in flight.
-        constexpr int DA = P == 1 ? (NN * NC >= 32 ? 2 : NN * NC >= 16 ? 4 : MPCD_MX_DA_SMALL) : 2;
+        constexpr int DA = P == 1 ? (NN * NC >= 32 ? 2 : NN * NC >= 16 ? 4 : DA_SMALL) : 2;
         u32x4 A[DA][NN][P];
 #pragma unroll
         for (int s = 0; s < DA; ++s) load_a(A[s], min(s, KC - 1));
@@ -413,8 +391,7 @@ __device__ __forceinline__ void conv_mx_body(const ConvMK2 &as)
                 const int ct = cg * NC + cc;
                 if (ct >= ctp) continue;
                 tile_t *dst = s_out + (size_t)(par * cpar16 + ct * 16 + col) * sout + nt * 16 + 4 * q;
-                if constexpr (sizeof(tile_t) == 2) *reinterpret_cast<f16x4 *>(dst) = __builtin_convertvector(acc[j][cc], f16x4);
-                else *reinterpret_cast<f32x4 *>(dst) = acc[j][cc];
+                *reinterpret_cast<f32x4 *>(dst) = acc[j][cc];
             }
         }
     };
@@ -481,7 +458,7 @@ __device__ __forceinline__ void conv_mx_body(const ConvMK2 &as)
     };
     auto epilogue = [&](int64_t r0, int nrow) {
         const int n_ro = nrow * a.lout;
-        constexpr int EU = MPCD_MX_EU;  // items per thread with their residual loads in flight together
+        // EU items per thread with their residual loads in flight together
         for (int i0 = tid < tps * cq ? tid / cq : n_ro; i0 < n_ro; i0 += EU * tps) {
             f32x4 rv[EU];
             int rr[EU], oo_[EU];
@@ -517,11 +494,7 @@ __device__ __forceinline__ void conv_mx_body(const ConvMK2 &as)
                         // Each element's Mish in scalar VALU ops (common.h mish_scalar: packed by hipcc's SLP
                         // vectorizer, this epilogue read v_rcp_f32 results with v_pk_fma_f32 one wait state later
                         // and gave wrong conv outputs on the GPU, profiles/r3_hazard_ab.txt). ~2 % of the kernel.
-#ifndef MPCD_MX_NO_FENCE
                         v[e] = mish_scalar(raw[e] * scale + shift);
-#else
-                        v[e] = mish(raw[e] * scale + shift);
-#endif
                     }
                     if (epi == UEPI_GN_MISH_COND) {  // row < b_cand: context branch; else the masked (CFG) branch
                         int64_t cand = grow, br = 0;  // branch = row / b_cand (0: context, 1: masked)
@@ -560,27 +533,25 @@ __device__ __forceinline__ void conv_mx_body(const ConvMK2 &as)
     if constexpr (!PERS) {
         const int64_t r0 = (int64_t)blockIdx.x * a.rb;
         const int nrow = (int)min((int64_t)a.rb, a.rows - r0);
-        if (ph == 0 && !(a.skip & 1)) stage_direct(r0, nrow);
+        if (ph == 0) stage_direct(r0, nrow);
         __syncthreads();
         epi_setup();
-        if (!(a.skip & 2)) {
-            if (a.alias) {  // one job per wave (host-checked): finish every read of the staged input first
-                if (wave < jobs) compute(wave);
-                __syncthreads();
-                if (wave < jobs) store(wave);
-            } else {
-                for (int job = wave; job < jobs; job += MT / 64) {
-                    compute(job);
-                    store(job);
-                }
+        if (a.alias) {  // one job per wave (host-checked): finish every read of the staged input first
+            if (wave < jobs) compute(wave);
+            __syncthreads();
+            if (wave < jobs) store(wave);
+        } else {
+            for (int job = wave; job < jobs; job += MT / 64) {
+                compute(job);
+                store(job);
             }
         }
         __syncthreads();
-        if (epi != UEPI_BIAS && !(a.skip & 4)) {
+        if (epi != UEPI_BIAS) {
             stats(nrow);
             __syncthreads();
         }
-        if (!(a.skip & 8)) epilogue(r0, nrow);
+        epilogue(r0, nrow);
     } else {  // host: no alias, 16-byte staging, items per thread <= SUP
         int64_t blk = blockIdx.x;
         {
@@ -609,45 +580,12 @@ __device__ __forceinline__ void conv_mx_body(const ConvMK2 &as)
     }
     if (ph + 1 < NPH) __syncthreads();  // the second conv's planes complete; tile / statistics free
     }
-    if (as.ph[0].wgtrace && tid == 0) {  // diagnostics: workgroup residency (vector stores from lane 0)
-        const uint32_t t_end = (uint32_t)__builtin_amdgcn_s_memrealtime();
-        uint32_t *tr = as.ph[0].wgtrace + 4 * (size_t)blockIdx.x;
-        tr[0] = t_start;
-        tr[1] = t_end;
-        tr[2] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID: wave, SIMD, CU, SH, SE
-        tr[3] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
-    }
 }
 
 template <int KIND, int P, int NN, int NC, bool PERS, int NPH>
 __global__ __launch_bounds__(MT) void conv_mx_kernel(const ConvMK2 as)
 {
     conv_mx_body<KIND, P, NN, NC, PERS, NPH>(as);
-}
-
-// MPCD_MX_WAVES_EU = w > 0: the fp16-operand net's convs are compiled for w waves per SIMD (w workgroups per
-// CU, register budget 512 / w): a workgroup is latency-bound and throughput grows with co-resident ones
-#ifndef MPCD_MX_WAVES_EU
-#define MPCD_MX_WAVES_EU 0
-#endif
-#if MPCD_MX_WAVES_EU > 0
-template <int KIND, int P, int NN, int NC, bool PERS, int NPH>
-__global__ __launch_bounds__(MT) __attribute__((amdgpu_waves_per_eu(MPCD_MX_WAVES_EU, 8))) void conv_mx_kernel_w(
-    const ConvMK2 as)
-{
-    conv_mx_body<KIND, P, NN, NC, PERS, NPH>(as);
-}
-#endif
-
-template <int KIND, int P, int NN, int NC, bool PERS, int NPH>
-constexpr auto conv_kernel_ptr()
-{
-#if MPCD_MX_WAVES_EU > 0
-    if constexpr (P == 1 && !PERS && NN * NC <= 8) return &conv_mx_kernel_w<KIND, P, NN, NC, PERS, NPH>;
-    else return &conv_mx_kernel<KIND, P, NN, NC, PERS, NPH>;
-#else
-    return &conv_mx_kernel<KIND, P, NN, NC, PERS, NPH>;
-#endif
 }
 
 // ---- host side
@@ -708,46 +646,22 @@ hipError_t resident_per_cu(const void *fn, size_t lds, int &out)
 }
 
 // LDS bytes of the pre-norm output tile (rows x (coutp + pad)), as the kernel lays it out
-size_t tile_bytes(int planes, size_t rows, int coutp)
-{
-    return (planes == 1 && MPCD_MX_TILE_H) ? rows * (size_t)(coutp + 8) * 2 : rows * (size_t)(coutp + 4) * 4;
-}
+size_t tile_bytes(size_t rows, int coutp) { return rows * (size_t)(coutp + 4) * 4; }
 
 template <int KIND, int P, int NN, int NC, bool PERS, int NPH = 1>
 hipError_t launch_one(const ConvMK2 &k2, size_t lds, hipStream_t st)
 {
     const ConvMK &k = k2.ph[0];
-    constexpr auto kfn = conv_kernel_ptr<KIND, P, NN, NC, PERS, NPH>();
+    constexpr auto kfn = &conv_mx_kernel<KIND, P, NN, NC, PERS, NPH>;
     auto *fn = reinterpret_cast<const void *>(kfn);
     if (hipError_t e = allow_max_lds<kfn>(); e != hipSuccess) return e;
     int64_t blocks = (k.rows + k.rb - 1) / k.rb;
-    int resident = 1;  // workgroups per CU at this kernel's registers and this launch's LDS
-    const int n_cu = device_cu_count();
-    if (PERS) {
+    if (PERS) {  // a resident grid: workgroups per CU at this kernel's registers and this launch's LDS
+        int resident = 1;
         if (hipError_t e = resident_per_cu(fn, lds, resident); e != hipSuccess) return e;
-        blocks = std::min<int64_t>(blocks, (int64_t)resident * n_cu);
+        blocks = std::min<int64_t>(blocks, (int64_t)resident * device_cu_count());
     }
-    static const int stag = [] {  // experiment knob: first-generation stagger units per resident slot
-        const char *e = getenv("MPCD_UNET_STAGGER");
-        return e ? atoi(e) : 0;
-    }();
-    if (!PERS && stag > 0) {
-        if (hipError_t e = resident_per_cu(fn, lds, resident); e != hipSuccess) return e;
-        if (resident > 1 && blocks > (int64_t)resident * n_cu) {
-            ConvMK2 k3 = k2;
-            k3.ph[0].stag_units = stag;
-            k3.ph[0].stag_ncu = n_cu;
-            k3.ph[0].stag_slots = resident;
-            hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(MT), lds, st, k3);
-            return hipGetLastError();
-        }
-    }
-    static const size_t lds_pad = [] {  // experiment knob: extra LDS per workgroup (fewer co-resident workgroups)
-        const char *e = getenv("MPCD_UNET_LDS_PAD");
-        return e ? (size_t)atol(e) : (size_t)0;
-    }();
-    hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(MT),
-                       std::min(lds + lds_pad, (size_t)160 * 1024), st, k2);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(MT), lds, st, k2);
     return hipGetLastError();
 }
 
@@ -957,10 +871,6 @@ hipError_t unet_launch_mx(int kind, int planes, ConvMK &k, hipStream_t st, std::
     const int nprod = planes == 1 ? 1 : 6;
     const Tile *tiles = planes == 1 ? kTiles1 : kTiles3;
     const int ntiles = planes == 1 ? 5 : 3;
-    static const size_t cap = [] {  // experiment knob: LDS bytes per workgroup (160 KiB = one per CU)
-        const char *e = getenv("MPCD_UNET_LDS_CAP");
-        return e ? (size_t)atol(e) : (size_t)160 * 1024;
-    }();
     // Candidates: for each rows-per-workgroup rb, the tile an issue model likes best (MFMA slots of
     // the busiest wave, padding included, + fragment loads + staging). The model does not see
     // occupancy - the LDS of a workgroup decides how many share a CU and hide each other's staging
@@ -972,7 +882,7 @@ hipError_t unet_launch_mx(int kind, int planes, ConvMK &k, hipStream_t st, std::
         const int nval = kind == UCONV_UP4 ? rb * k.lin : rb * k.lout;
         const int ctp = (nval + 15) / 16;
         const size_t in_b = (size_t)planes * rb * win * cs;
-        const size_t out_b = tile_bytes(planes, (size_t)npar * ctp * 16, k.coutp);
+        const size_t out_b = tile_bytes((size_t)npar * ctp * 16, k.coutp);
         const size_t stat_b = (size_t)(2 * rb * 32 + 4) * 4 + (size_t)4 * k.coutp * 4;
         MxChoice best{};
         for (int ti = 0; ti < ntiles; ++ti) {
@@ -981,7 +891,7 @@ hipError_t unet_launch_mx(int kind, int planes, ConvMK &k, hipStream_t st, std::
             const int alias = jobs <= MT / 64;
             const size_t body = alias ? std::max(in_b, out_b) : in_b + out_b;
             const size_t lds = body + stat_b;
-            if (lds > cap) continue;
+            if (lds > LDS_CAP) continue;
             const int per_wave = (jobs + 3) / 4;
             const double cyc = (double)per_wave * KC *
                                    (t.nn * t.nc * nprod * 16.0 + t.nn * planes * 24.0 + t.nc * planes * 8.0) +
@@ -995,7 +905,7 @@ hipError_t unet_launch_mx(int kind, int planes, ConvMK &k, hipStream_t st, std::
         if (best.rb && (k.ca & 7) == 0 && (k.cb & 7) == 0 && (int64_t)rb * 4 < k.rows) {
             const int items = rb * win * (cinp / 8);
             const size_t lds = in_b + out_b + stat_b;
-            if ((items + MT - 1) / MT <= SUP && lds <= cap)
+            if ((items + MT - 1) / MT <= SUP && lds <= LDS_CAP)
                 cands.push_back(MxChoice{rb, best.t, 1, 0, lds, (int)(in_b + out_b), best.model * 1.0001});
         }
     }
@@ -1009,17 +919,7 @@ hipError_t unet_launch_mx(int kind, int planes, ConvMK &k, hipStream_t st, std::
     MxChoice pick = cands[0];
     bool have = false;
     if (int f = g_force_conv.load(); f >= 0) {  // forced candidate (tests: every tiling gives the same bits)
-        // diagnostics: MPCD_UNET_FORCE_LAYER=l applies the forced index to conv l only, the others take
-        // MPCD_UNET_FORCE_BASE (default 0)
-        const char *ol = getenv("MPCD_UNET_FORCE_LAYER"), *ob = getenv("MPCD_UNET_FORCE_BASE");
-        const int only = ol && ol[0] ? atoi(ol) : -1, base = ob && ob[0] ? atoi(ob) : 0;
-        if (only >= 0 && k.layer != only) f = base;
         const MxChoice &ch = cands[f % cands.size()];
-        if (tune_log() && only >= 0 && k.layer == only)
-            fprintf(stderr, "[mx force] layer %d kind %d P%d cin %d+%d cout %d L %d->%d epi %d rows %lld: rb %d tile %dx%d %s lds %zu\n",
-                    k.layer, kind, planes, k.ca, k.cb, k.cout, k.lin, k.lout, k.epi, (long long)k.rows, ch.rb, ch.t.nn,
-                    ch.t.nc, ch.pers ? "pers" : ch.alias ? "alias" : "tile", ch.lds);
-        k.skip = 0;
         return launch_choice(kind, planes, k, ch, st);
     }
     {
@@ -1069,47 +969,6 @@ hipError_t unet_launch_mx(int kind, int planes, ConvMK &k, hipStream_t st, std::
            << pick.lds << ' ' << pick.stat_off;
         tune_cache_append(os.str());
     }
-    // diagnostics: MPCD_UNET_WGTRACE=<layer>[:<nth call>] records one launch's workgroup residency into
-    // gpurun_out/wgtrace_L<layer>.bin ({start, end, HW_ID, XCC_ID} per workgroup, s_memrealtime at 100 MHz)
-    static int tr_layer = -2, tr_call = 0;
-    if (tr_layer == -2) {
-        const char *e = getenv("MPCD_UNET_WGTRACE");
-        tr_layer = e && e[0] ? atoi(e) : -1;
-        const char *c = e ? strchr(e, ':') : nullptr;
-        tr_call = c ? atoi(c + 1) : 3;
-    }
-    if (tr_layer >= 0 && k.layer == tr_layer && --tr_call == 0) {
-        const int64_t nb = (k.rows + pick.rb - 1) / pick.rb;
-        uint32_t *dbuf = nullptr;
-        if (hipMalloc(&dbuf, (size_t)nb * 16) == hipSuccess) {
-            (void)hipMemsetAsync(dbuf, 0, (size_t)nb * 16, st);
-            ConvMK kk = k;
-            kk.skip = 0;
-            kk.wgtrace = dbuf;
-            hipError_t e = launch_choice(kind, planes, kk, pick, st);
-            std::vector<uint32_t> h((size_t)nb * 4);
-            if (e == hipSuccess && hipStreamSynchronize(st) == hipSuccess &&
-                hipMemcpy(h.data(), dbuf, (size_t)nb * 16, hipMemcpyDeviceToHost) == hipSuccess) {
-                char fn[128];
-                snprintf(fn, sizeof fn, "gpurun_out/wgtrace_L%d.bin", tr_layer);
-                if (FILE *f = fopen(fn, "wb")) {
-                    const int32_t hdr[4] = {(int32_t)nb, pick.rb, pick.t.nn * 16 + pick.t.nc, (int32_t)pick.lds};
-                    fwrite(hdr, 4, 4, f);
-                    fwrite(h.data(), 4, h.size(), f);
-                    fclose(f);
-                }
-            }
-            (void)hipFree(dbuf);
-            if (e != hipSuccess) return e;
-        }
-    }
-    static const int skip = [] {  // experiment knob: skip kernel phases (results are garbage)
-        const char *e = getenv("MPCD_UNET_SKIP");
-        return e ? atoi(e) : 0;
-    }();
-    k.skip = skip;
-    static const bool keep = getenv("MPCD_UNET_SKIP_KEEP") != nullptr;  // keep the tuned / cached pick
-    if (skip && (!keep || pick.pers)) pick = cands[0].pers ? cands[1] : cands[0];
     return launch_choice(kind, planes, k, pick, st);
 }
 
@@ -1268,11 +1127,11 @@ hipError_t unet_launch_mx_rtb(int planes, ConvMK &k1, ConvMK &k2, hipStream_t st
         if (rb > 1 && (int64_t)rb > k1.rows) continue;
         const int ctp = (rb * k1.lout + 15) / 16;
         const size_t in1 = (size_t)planes * rb * win1 * k1.cs, in2 = (size_t)planes * rb * win2 * k2.cs;
-        const size_t out_b = tile_bytes(planes, (size_t)ctp * 16, k1.coutp);
+        const size_t out_b = tile_bytes((size_t)ctp * 16, k1.coutp);
         const size_t stat_b = (size_t)(2 * rb * 32 + 4) * 4 + (size_t)4 * k1.coutp * 4;
         const size_t x_off = in1 + out_b;  // >= out_b: the second tile fits in front of x_off
         const size_t lds = x_off + in2 + stat_b;
-        if (lds > (size_t)160 * 1024) continue;
+        if (lds > LDS_CAP) continue;
         RtbChoice best{};
         for (int ti = 0; ti < ntiles; ++ti) {
             const Tile t = tiles[ti];

@@ -38,6 +38,20 @@ def _eps_err(got, ref):
     return float((got.cpu() - ref).abs().max()) / max(float(ref.abs().max()), 1.0)
 
 
+@pytest.mark.parametrize("dtype,H,rows,waves", [
+    ("f16", 32, 8, 8), ("f16", 64, 2, 4), ("f16", 128, 2, 8),
+    ("f32x3", 32, 4, 8), ("f32x3", 64, 2, 8), ("f32x3", 128, 1, 8),
+    ("f16x2", 32, 4, 8), ("f16x2", 64, 2, 8), ("f16x2", 128, 1, 8)])
+def test_fused_default_configuration(dtype, H, rows, waves, fused):
+    """The one fused program instantiated per (numerics, horizon): rows and waves per workgroup of the nine shipped
+    pairs (csrc/unet_fused.hip kCfgs). No sample call: the form is decided when the net is loaded."""
+    d, C = 1, 2
+    form = _planner(make_unet(d, C, seed=H), d, H, C, dtype=dtype).unet_form()
+    assert form["fused"]
+    assert (form["rows_per_workgroup"], form["waves_per_workgroup"]) == (rows, waves)
+    assert form["planes"] == {"f16": 1, "f32x3": 3, "f16x2": 2}[dtype]
+
+
 @pytest.mark.parametrize("dtype", ["f16", "f32x3", "f16x2"])
 def test_fused_h128_panda_shape(dtype, fused):
     """H = 128 (the Panda net's horizon: d = 7, C = 20): fp16 operands with two rows (both CFG branches) per workgroup,

@@ -3,7 +3,8 @@
 1. Packed-math reads of transcendental results ("Codegen hazards"). With the GroupNorm+Mish
    epilogue of csrc/unet_mx.hip SLP-packed by hipcc, the conv kernels gave wrong outputs on the GPU
    (tests/test_gpu_unet_bench_sizes.py, bit-identity across tilings, failed with -DMPCD_MX_NO_FENCE and passed
-   with the fence or with -fno-slp-vectorize: tools/hazard_ab.sh, profiles/r3_hazard_ab.txt). The only code
+   with the fence or with -fno-slp-vectorize: profiles/r3_hazard_ab.txt; that switch and its A/B recipe were
+   since removed and are in git history). The only code
    difference: 432 sites where a v_pk_fma_f32 reads a v_rcp_f32 result one wait state after it. The U-Net
    same pattern sat in the MLP samplers' Mish epilogues (626 sites in round 3); every kernel of the library must
    keep every packed reader of a transcendental result at >= 2 wait states.

@@ -89,7 +89,7 @@ run_job() {
       local c=${arg:-cfg5}
       timeout -k 10 600 python -u tools/unet_perf.py ${UARGS[$c]} $UNET_ARGS > "gpurun_out/unet_$c.log" 2>&1 ;;
     upmc)
-      # $UPMC_TAG: suffix of the output names (A/B of an environment switch, e.g. MPCD_FUSED_PERSIST=1)
+      # $UPMC_TAG: suffix of the output names (A/B of an environment switch, e.g. MPCD_UNET_FUSE=0)
       local c=${arg:-cfg5} i=0 ctr
       local a="${UARGS[$c]} --steps 1 --reps 1 $UNET_ARGS" n=${arg:-cfg5}$UPMC_TAG
       export MPCD_UNET_TUNE_CACHE=gpurun_out/uroof/${n}_tune.txt

@@ -2,7 +2,7 @@
 """Is the device code of a refactor the parent's, instruction for instruction? (CPU only, no GPU.)
 
     git archive <parent> mpc_via_diffusion_model_amd/csrc include | tar -x -C /tmp/parent
-    python tools/isa_identity.py /tmp/parent --work /tmp/isa [-o profiles/<name>.txt] [files.hip ...]
+    python tools/isa_identity.py /tmp/parent --work /tmp/isa [-o profiles/<name>.txt] [--rename REGEX=REPL] [files.hip ...]
 
 Compiles each translation unit of both trees device-only to assembly with build.py's FLAGS and SOURCE_FLAGS, once as
 the product and once with -DMPCD_PROF_LAYERS, splits the text per function symbol (instantiation order may differ:
@@ -24,7 +24,7 @@ from mpc_via_diffusion_model_amd import build as B  # noqa: E402
 
 DEFAULT = ["mlp_rw.hip", "mlp_x3.hip", "mlp_h2.hip", "mlp_sampler.hip", "mpcd_api.hip"]
 LABEL = re.compile(r"(\.L)?(BB|func_begin|func_end|tmp)\d+(_?)")
-BEGIN = re.compile(r"^\t\.globl\t(\S+)\s*; -- Begin function")
+BEGIN = re.compile(r"^\t\.(?:globl|protected)\t(\S+)\s*; -- Begin function")  # .protected: kernels with external linkage
 STOP = re.compile(r"^\t(\.section\t\.text|\.text|\.type\t\S+,@object|\.amdgpu_metadata)")
 
 
@@ -35,10 +35,14 @@ def assemble(csrc, src, out, defines):
         raise RuntimeError(f"{' '.join(cmd)}\n{r.stderr}")
 
 
-def functions(path):
-    """symbol -> normalised text: the function, its kernel descriptor directives, its metadata entry"""
+def functions(path, rename=()):
+    """symbol -> normalised text: the function, its kernel descriptor directives, its metadata entry.
+    rename: (regex, replacement) pairs applied to the whole text first (a symbol whose mangled name changed)"""
     fn, cur = {}, None
-    lines = open(path).read().split("\n")
+    text = open(path).read()
+    for pat, repl in rename:
+        text = re.sub(pat, repl, text)
+    lines = text.split("\n")
     meta = lines.index("\t.amdgpu_metadata") if "\t.amdgpu_metadata" in lines else len(lines)
     for ln in lines[:meta]:
         m = BEGIN.match(ln)
@@ -75,6 +79,8 @@ def main():
     ap.add_argument("--reuse", action="store_true", help="do not recompile assembly files that exist")
     ap.add_argument("-o", "--out")
     ap.add_argument("-j", type=int, default=4)
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPL",
+                    help="rewrite the parent's assembly text before it is split (renamed symbols); repeatable")
     a = ap.parse_args()
     sides = {"parent": os.path.join(a.parent, "mpc_via_diffusion_model_amd", "csrc"), "new": B.CSRC}
     variants = {"product": [], "MPCD_PROF_LAYERS": ["-DMPCD_PROF_LAYERS"]}
@@ -93,7 +99,8 @@ def main():
     for var in variants:
         rep.append(f"\n[{var}]")
         for f in a.files:
-            p, n = (functions(os.path.join(a.work, f"{s}_{var}", f.replace(".hip", ".s"))) for s in sides)
+            p, n = (functions(os.path.join(a.work, f"{s}_{var}", f.replace(".hip", ".s")),
+                              [r.split("=", 1) for r in a.rename] if s == "parent" else ()) for s in sides)
             same = sum(1 for k in p if k in n and p[k] == n[k])
             diff = sorted(k for k in set(p) | set(n) if p.get(k) != n.get(k))
             bad += len(diff)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Before / after table of the register, scratch, LDS and occupancy figures of the MLP sampler kernels.
+"""Before / after table of the register, scratch, LDS and occupancy figures of the kernels of two trees.
 
 Compile the kernels of two trees with the library's flags plus the resource remarks, device only (no GPU needed):
 
@@ -41,7 +41,8 @@ def short(mangled):
     m = re.search(r"(mlp_\w+?_kernel)I(.*?)EEv", mangled)
     if not m:
         try:
-            return subprocess.run(["c++filt", mangled], capture_output=True, text=True).stdout.strip() or mangled
+            full = subprocess.run(["c++filt", mangled], capture_output=True, text=True).stdout.strip() or mangled
+            return re.sub(r"\(\w+\)$", "", re.sub(r"^void |\(anonymous namespace\)::", "", full))  # kernel<arguments>
         except OSError:
             return mangled
     args = re.findall(r"L([ib])(\d+)E", m.group(2))
@@ -50,8 +51,9 @@ def short(mangled):
 
 def main():
     before, after = parse(sys.argv[1]), parse(sys.argv[2])
-    print("template arguments: mlp_rw_kernel / mlp_x3_kernel <H*d, sampler mode, context, rows, waves>; dynamic LDS is")
-    print("sized at launch (the static figure is 0); b = before, a = after\n")
+    if any("mlp_" in k for k in set(before) | set(after)):
+        print("template arguments: mlp_rw_kernel / mlp_x3_kernel <H*d, sampler mode, context, rows, waves>")
+    print("dynamic LDS is sized at launch (the static figure is 0); b = before, a = after\n")
     print(f"{'kernel':46s} " + " ".join(f"{h + ' b':>9s} {h + ' a':>9s}" for h, _ in FIELDS))
     changed = fresh = 0
     for k in sorted(set(before) | set(after), key=short):
