@@ -285,6 +285,51 @@ int mpcd_control_step(mpcd_ctx *ctx, const mpcd_system_desc *sys, double *x_dev,
                       const float *umax_host, const int32_t *flags_dev, int32_t select_first, int32_t decimals,
                       double *u_applied, int64_t *best_index, double *best_cost, void *hip_stream);
 
+/* ---- The whole closed loop in one call. mpcd_closed_loop enqueues, on hip_stream and without a host synchronisation,
+ * what DiffusionMPC.closed_loop composes from the entry points above: one mpcd_normalize_states launch for iteration
+ * 0, then per iteration the sampler and ONE launch (closed_loop_tail_kernel, csrc/rollout.hip) for everything else:
+ * each state's clip code, the fp64 rollout and cost of its candidates, the selection (NaN = +inf, lowest index on
+ * ties, or the group's first candidate), u0 unnormalised and rounded, the plant step, the history rows, the next
+ * iteration's context row and, with a warm start, its next prior. The results are bit for bit those of the composed
+ * calls (same fp64 operations in the same order per candidate).
+ * MPCD_EINVAL: a NULL required pointer, iterations / group / n_states < 1, sys->n_u != the net's state_dim,
+ * sys->n_x != its context_dim, clip_rule == MPCD_CLIP_NONE (or unknown), warm_t_start outside [0, n_steps].
+ * MPCD_EUNSUP: an MPCD_F16X2 net - its range guard needs a look at the chain maxima on the host in every iteration
+ * (the re-run with the split-bf16 programs), which is exactly the round trip this call removes; a context with a
+ * communicator (the loop is single-rank); warm_t_start > 0 with a sampler other than MPCD_DDPM_CFG. */
+typedef struct {
+    const mpcd_system_desc *sys;    /* n_u == the net's state_dim, n_x == its context_dim */
+    const float *ctx_min, *ctx_max; /* host [n_x] condition limits (mpcd_normalize_states) */
+    const float *act_min, *act_max; /* host [n_u] action limits */
+    mpcd_sample_args sample;        /* the sampler, w, n_wo_noise, the DDIM fields and clamp_x0; seed = iteration 0's
+                                       seed (iteration it: seed + it, global_offset 0). batch, context,
+                                       context_shared, global_offset, noise, x_out, chain_out and chain_absmax are
+                                       ignored: batch = n_states * group */
+    int64_t n_states;               /* M plant states */
+    int64_t group;                  /* n candidates per state */
+    int32_t iterations;             /* T */
+    int32_t group_contexts;         /* 1: the sampler runs as mpcd_sample_grouped on the [M][C] rows and [M][H][d] priors;
+                                       0: one row (and prior) per candidate, each state's repeated n times - an MLP
+                                       then runs the exact-f32 kernel, as with mpcd_sample and a [B][C] context */
+    const float *const *noise_iters; /* host [iterations] device pointers, entry it = that iteration's injected noise
+                                       [S_it + 1][B][H][d] (S_0 = the cold step count; S_it = warm_t_start + n_wo_noise
+                                       for it >= 1 of a warm loop); NULL = Philox */
+    int32_t clip_rule;              /* MPCD_CLIP_CHAIN or MPCD_CLIP_FINAL, per state over its own candidates */
+    int32_t select_first;           /* mpcd_control_step's */
+    int32_t decimals;               /* mpcd_control_step's (< 0: no rounding) */
+    int32_t warm_t_start;           /* 0: every iteration samples cold; K >= 1: iteration 0 cold, the later ones
+                                       t_start = K from the shifted winners (mpcd_shift_plans' rule) */
+    double *x_dev;                  /* dev [M][n_x] fp64 plant states, in and out */
+    double *x_hist;                 /* dev [T + 1][M][n_x]; slice 0 = the initial states (written by the call) */
+    double *u_hist;                 /* dev [T][M][n_u] applied actions */
+    double *cost_hist;              /* dev [T][M] cost of the selected candidate */
+    int64_t *index_hist;            /* dev [T][M] global index of the selected candidate in that iteration's batch */
+    float *u_norm;                  /* dev [B][H][d] or NULL: the last iteration's normalised samples */
+} mpcd_closed_loop_args;
+/* The context owns the loop's workspace (context rows, per-state counters, partials, samples, chain maxima, priors),
+ * reused and grown across calls: like every context workspace it is ordered on ONE stream. */
+int mpcd_closed_loop(mpcd_ctx *ctx, const mpcd_closed_loop_args *args, void *hip_stream);
+
 /* ---- Candidate-batch data parallelism over RCCL / xGMI. One process per GPU, one
  * communicator per context; rank r owns global candidates [r*B_local, (r+1)*B_local). The reference has
  * no distributed code: these entry points are new design, not replacements. */

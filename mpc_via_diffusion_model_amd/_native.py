@@ -62,6 +62,17 @@ class WarmStart(ctypes.Structure):
     _fields_ = [("x_init", ctypes.c_void_p), ("rows", ctypes.c_int64), ("t_start", ctypes.c_int32)]
 
 
+class ClosedLoopArgs(ctypes.Structure):
+    _fields_ = [("sys", ctypes.POINTER(SystemDesc)), ("ctx_min", ctypes.c_void_p), ("ctx_max", ctypes.c_void_p),
+                ("act_min", ctypes.c_void_p), ("act_max", ctypes.c_void_p), ("sample", SampleArgs),
+                ("n_states", ctypes.c_int64), ("group", ctypes.c_int64), ("iterations", ctypes.c_int32),
+                ("group_contexts", ctypes.c_int32), ("noise_iters", ctypes.POINTER(ctypes.c_void_p)),
+                ("clip_rule", ctypes.c_int32), ("select_first", ctypes.c_int32), ("decimals", ctypes.c_int32),
+                ("warm_t_start", ctypes.c_int32), ("x_dev", ctypes.c_void_p), ("x_hist", ctypes.c_void_p),
+                ("u_hist", ctypes.c_void_p), ("cost_hist", ctypes.c_void_p), ("index_hist", ctypes.c_void_p),
+                ("u_norm", ctypes.c_void_p)]
+
+
 class TrainCfg(ctypes.Structure):
     _fields_ = [("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
                 ("ema_decay", ctypes.c_float), ("step_start_ema", ctypes.c_int32), ("update_ema_every", ctypes.c_int32)]
@@ -112,6 +123,7 @@ EXPORTS = {
                            ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                            ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                            ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "mpcd_closed_loop": ([ctypes.c_void_p, ctypes.POINTER(ClosedLoopArgs), ctypes.c_void_p], ctypes.c_int),
     "mpcd_comm_unique_id": ([ctypes.c_void_p], ctypes.c_int),
     "mpcd_comm_init": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p], ctypes.c_int),
     "mpcd_philox_noise": ([ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,

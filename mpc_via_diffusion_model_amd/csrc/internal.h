@@ -168,3 +168,32 @@ struct RolloutSelect {
     uint32_t host_seq;
 };
 constexpr int kRolloutBlock = 64;  // candidates per rollout workgroup
+
+// One closed-loop iteration's control tail (rollout.hip closed_loop_tail_kernel, mpcd_closed_loop): everything
+// after the sampler in one launch of n_states * ceil(group / kRolloutBlock) workgroups. Device pointers.
+struct ClosedLoopTail {
+    const float *u_norm;   // [n_states * group][H][n_u] this iteration's samples
+    const float *clip_src; // chain rule: chain_absmax [n_states * group]; final rule: u_norm
+    int64_t clip_per_state;  // floats of clip_src per state: group, or group * H * n_u
+    double *x_dev;         // [n_states][n_x], in and out
+    int64_t n_states, group;
+    int32_t H, select_first, decimals;
+    // per-workgroup partials [n_states * ceil(group / kRolloutBlock)] and one zero-initialised, self-resetting
+    // counter per state
+    double *part_cost, *part_raw;
+    int64_t *part_idx;
+    unsigned *counters;
+    // this iteration's history rows
+    double *x_next, *u_applied, *best_cost;  // x_hist[it + 1], u_hist[it], cost_hist[it]
+    int64_t *best_idx;                       // index_hist[it]
+    // the next iteration's sampler inputs: one row per state, or (repeat_rows) each state's row repeated `group`
+    // times, one per candidate; prior_out null: no warm start
+    float *ctx_out;
+    float *prior_out;
+    int32_t repeat_rows;
+};
+hipError_t launch_closed_loop_tail(const mpcd_system_desc &d, const float *umin_host, const float *umax_host,
+                                   const float *cmin_host, const float *cmax_host, const ClosedLoopTail &t,
+                                   hipStream_t stream);
+// out[r * n + j][:] = rows[r][:] for j < n (the per-candidate rows of iteration 0 when the loop is not grouped)
+hipError_t launch_repeat_rows(const float *rows, int64_t n_rows, int64_t n, int row_len, float *out, hipStream_t stream);

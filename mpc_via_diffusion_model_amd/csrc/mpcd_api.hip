@@ -299,6 +299,8 @@ struct mpcd_ctx {
     // mpcd_mpc_step: device context row, per-block argmin partials, {best, winner row} result block
     // and its pinned host mirror (one D2H copy per control step)
     DevBuf step_ctx, step_part, step_out, step_amax;
+    // mpcd_closed_loop: partials, samples, chain maxima, context rows and priors; one self-resetting counter per state
+    DevBuf loop_ws, loop_cnt;
     void *step_host = nullptr;
     void *step_host_dev = nullptr;  // step_host's device address (mapped pinned memory)
     size_t step_host_bytes = 0;
@@ -624,7 +626,7 @@ void mpcd_destroy(mpcd_ctx *c)
     if (!c) return;
     DeviceGuard device_guard_(c->device);
     for (DevBuf *b : {&c->params, &c->wpack, &c->wpack3, &c->wpackh, &c->cond_layers, &c->unet_pack, &c->plan, &c->tproj, &c->cproj, &c->flag,
-                      &c->unet_ws, &c->step_ctx, &c->step_part, &c->step_out, &c->step_amax})
+                      &c->unet_ws, &c->step_ctx, &c->step_part, &c->step_out, &c->step_amax, &c->loop_ws, &c->loop_cnt})
         b->release();
     for (int i = 0; i < mpcd_ctx::kEvRing; ++i)
         for (int j = 0; j < 2; ++j)
@@ -1183,6 +1185,126 @@ int mpcd_control_step(mpcd_ctx *c, const mpcd_system_desc *sys, double *x, int64
     DEVICE_GUARD(c->device);
     HIP_TRY(launch_control_step(*sys, x, n_states, group, u_norm, horizon, cost, umin, umax, flags, select_first,
                                 decimals, u_applied, best_index, best_cost, static_cast<hipStream_t>(stream_ptr)));
+    return MPCD_OK;
+}
+
+int mpcd_closed_loop(mpcd_ctx *c, const mpcd_closed_loop_args *a, void *stream_ptr)
+{
+    if (!c || !a) return fail(MPCD_EINVAL, "null argument");
+    if (!a->sys || !a->ctx_min || !a->ctx_max || !a->act_min || !a->act_max || !a->x_dev || !a->x_hist || !a->u_hist ||
+        !a->cost_hist || !a->index_hist)
+        return fail(MPCD_EINVAL, "mpcd_closed_loop: null argument");
+    if (a->iterations < 1 || a->group < 1 || a->n_states < 1)
+        return fail(MPCD_EINVAL, "mpcd_closed_loop: iterations %d / group %lld / n_states %lld < 1", a->iterations,
+                    (long long)a->group, (long long)a->n_states);
+    if (a->clip_rule != MPCD_CLIP_CHAIN && a->clip_rule != MPCD_CLIP_FINAL)
+        return fail(MPCD_EINVAL, "mpcd_closed_loop: clip_rule %d (MPCD_CLIP_CHAIN or MPCD_CLIP_FINAL)", a->clip_rule);
+    if (a->decimals > 15) return fail(MPCD_EINVAL, "decimals > 15");
+    if (!c->net_loaded) return fail(MPCD_ESTATE, "no net loaded");
+    if (!c->n_steps) return fail(MPCD_ESTATE, "no schedule set");
+    const mpcd_net_desc &d = c->desc;
+    const mpcd_system_desc &sys = *a->sys;
+    if (sys.n_u != d.state_dim) return fail(MPCD_EINVAL, "system n_u %d != net state_dim %d", sys.n_u, d.state_dim);
+    if (sys.n_x != d.context_dim)
+        return fail(MPCD_EINVAL, "the loop conditions on the plant state: n_x %d != net context_dim %d", sys.n_x,
+                    d.context_dim);
+    if (d.dtype == MPCD_F16X2)
+        return fail(MPCD_EUNSUP, "mpcd_closed_loop: an MPCD_F16X2 net's range guard reads the chain maxima on the host in "
+                                 "every iteration, the round trip this call removes");
+    if (c->comm) return fail(MPCD_EUNSUP, "mpcd_closed_loop is single-rank: the context has a communicator");
+    const int H = d.horizon, nu = sys.n_u, nx = sys.n_x;
+    int rc = check_system(&sys, H);
+    if (rc) return rc;
+    if ((size_t)(H * nu + 1) * 64 * sizeof(float) > 64 * 1024) return fail(MPCD_EUNSUP, "H*n_u too large");
+    const int64_t M = a->n_states, n = a->group;
+    if (M > INT32_MAX || n > ((int64_t)1 << 40) / M) return fail(MPCD_EINVAL, "n_states * group too large");
+    const int64_t B = M * n, wps = (n + kRolloutBlock - 1) / kRolloutBlock;
+    if (M * wps > INT32_MAX) return fail(MPCD_EINVAL, "n_states * ceil(group / 64) workgroups exceed a grid");
+    const bool grouped = a->group_contexts != 0, chain_rule = a->clip_rule == MPCD_CLIP_CHAIN;
+    const int64_t rows = grouped ? M : B;  // context rows / priors the sampler takes
+
+    mpcd_sample_args s = a->sample;
+    s.batch = B;
+    s.context_shared = 0;
+    s.global_offset = 0;
+    s.chain_out = nullptr;
+    if (a->warm_t_start < 0 || a->warm_t_start > c->n_steps)
+        return fail(MPCD_EINVAL, "warm_t_start %d outside [0, %d]", a->warm_t_start, c->n_steps);
+    if (a->warm_t_start > 0 && s.sampler != MPCD_DDPM_CFG)
+        return fail(MPCD_EUNSUP, "warm start (warm_t_start > 0) is implemented for the CFG-DDPM sampler only");
+    hipStream_t st = static_cast<hipStream_t>(stream_ptr);
+    DEVICE_GUARD(c->device);
+
+    // workspace, every part 256-byte aligned: fp64 partials first
+    size_t off = 0;
+    auto carve = [&off](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return at;
+    };
+    const size_t o_pc = carve(sizeof(double) * M * wps), o_pr = carve(sizeof(double) * M * wps),
+                 o_pi = carve(sizeof(int64_t) * M * wps), o_u = carve(sizeof(float) * B * H * nu),
+                 o_amax = carve(chain_rule ? sizeof(float) * B : 0), o_ctx = carve(sizeof(float) * rows * nx),
+                 o_ctx0 = carve(grouped ? 0 : sizeof(float) * M * nx),
+                 o_prior = carve(a->warm_t_start ? sizeof(float) * rows * H * nu : 0);
+    if ((rc = c->loop_ws.ensure(off))) return rc;
+    if (sizeof(unsigned) * M > c->loop_cnt.bytes) {  // new counters start at zero; the kernel leaves them there
+        if ((rc = c->loop_cnt.ensure(sizeof(unsigned) * M))) return rc;
+        HIP_TRY(hipMemsetAsync(c->loop_cnt.p, 0, c->loop_cnt.bytes, st));
+    }
+    char *w = c->loop_ws.as<char>();
+    float *u_norm = reinterpret_cast<float *>(w + o_u);
+    float *amax = chain_rule ? reinterpret_cast<float *>(w + o_amax) : nullptr;
+    float *ctx = reinterpret_cast<float *>(w + o_ctx);
+    float *prior = a->warm_t_start ? reinterpret_cast<float *>(w + o_prior) : nullptr;
+
+    HIP_TRY(hipMemcpyAsync(a->x_hist, a->x_dev, sizeof(double) * M * nx, hipMemcpyDeviceToDevice, st));
+    if (grouped) {
+        HIP_TRY(launch_normalize_states(a->x_dev, M, nx, a->ctx_min, a->ctx_max, ctx, st));
+    } else {  // iteration 0's per-candidate rows; the later ones are written by the tail
+        float *ctx0 = reinterpret_cast<float *>(w + o_ctx0);
+        HIP_TRY(launch_normalize_states(a->x_dev, M, nx, a->ctx_min, a->ctx_max, ctx0, st));
+        HIP_TRY(launch_repeat_rows(ctx0, M, n, nx, ctx, st));
+    }
+    s.context = ctx;
+    s.x_out = u_norm;
+    s.chain_absmax = amax;
+
+    ClosedLoopTail t{};
+    t.u_norm = u_norm;
+    t.clip_src = chain_rule ? amax : u_norm;
+    t.clip_per_state = chain_rule ? n : n * H * nu;
+    t.x_dev = a->x_dev;
+    t.n_states = M;
+    t.group = n;
+    t.H = H;
+    t.select_first = a->select_first;
+    t.decimals = a->decimals;
+    t.part_cost = reinterpret_cast<double *>(w + o_pc);
+    t.part_raw = reinterpret_cast<double *>(w + o_pr);
+    t.part_idx = reinterpret_cast<int64_t *>(w + o_pi);
+    t.counters = c->loop_cnt.as<unsigned>();
+    t.ctx_out = ctx;
+    t.prior_out = prior;
+    t.repeat_rows = grouped ? 0 : 1;
+    WarmArgs warm;
+    if (a->warm_t_start) {
+        const mpcd_warm_start ws{prior, rows, a->warm_t_start};
+        if ((rc = resolve_warm(c, &s, grouped ? n : 0, &ws, warm))) return rc;
+    }
+    for (int32_t it = 0; it < a->iterations; ++it) {
+        s.seed = a->sample.seed + (uint64_t)it;
+        s.noise = a->noise_iters ? a->noise_iters[it] : nullptr;
+        rc = sample_impl(c, &s, stream_ptr, nullptr, grouped ? n : 0, a->warm_t_start && it > 0 ? &warm : nullptr);
+        if (rc) return rc;
+        t.x_next = a->x_hist + (size_t)(it + 1) * M * nx;
+        t.u_applied = a->u_hist + (size_t)it * M * nu;
+        t.best_cost = a->cost_hist + (size_t)it * M;
+        t.best_idx = a->index_hist + (size_t)it * M;
+        HIP_TRY(launch_closed_loop_tail(sys, a->act_min, a->act_max, a->ctx_min, a->ctx_max, t, st));
+    }
+    if (a->u_norm)
+        HIP_TRY(hipMemcpyAsync(a->u_norm, u_norm, sizeof(float) * B * H * nu, hipMemcpyDeviceToDevice, st));
     return MPCD_OK;
 }
 

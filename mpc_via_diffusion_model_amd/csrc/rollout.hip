@@ -535,7 +535,264 @@ __global__ __launch_bounds__(256) void shift_plan_kernel(const float *rows, int6
     }
 }
 
+// ---- The closed loop's control tail (mpcd_closed_loop): per iteration, everything after the sampler in one launch.
+// The two helpers restate rollout_cost_kernel's staging and per-candidate cost expression by expression (same fp64
+// operations in the same order, -ffp-contract=off), so a candidate's cost is bit for bit that kernel's.
+
+// nvalid candidates' contiguous [row] floats at src -> su[c][row + 1]
+__device__ __forceinline__ void stage_rows(const float *src, int64_t nvalid, int row, float *su)
+{
+    const int stride = row + 1;
+    if ((row & 3) == 0) {  // 16-byte loads, UNR per lane in flight before the first LDS store (as rollout_cost_kernel)
+        constexpr int UNR = 8;
+        const int nq = (int)(nvalid * row / 4);
+        for (int base = 0; base < nq; base += UNR * RT_THREADS) {
+            f32x4 v[UNR];
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+                const int i = base + u * RT_THREADS + (int)threadIdx.x;
+                v[u] = i < nq ? ldg4(src + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+                const int i = base + u * RT_THREADS + (int)threadIdx.x;
+                if (i < nq) {
+                    const int c = 4 * i / row, k = 4 * i - c * row;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) su[c * stride + k + e] = v[u][e];
+                }
+            }
+        }
+    } else {
+        for (int i = threadIdx.x; i < nvalid * row; i += RT_THREADS) {
+            const int c = i / row, k = i - c * row;
+            su[c * stride + k] = src[i];
+        }
+    }
+}
+
+// The MPC cost of the normalised plan ur[H][nu] from the state x (overwritten), both cost kinds
+template <int SYS>
+__device__ __forceinline__ double candidate_cost(const SysK &S, const float *ur, bool clip, double *x, int H)
+{
+    constexpr int nx = SysDim<SYS>::NX, nu = SysDim<SYS>::NU;
+    float mn[nu], mx[nu];
+#pragma unroll
+    for (int i = 0; i < nu; ++i) { mn[i] = S.umin[i]; mx[i] = S.umax[i]; }
+    double xn[nx], u[nu];
+    double J;
+    if (S.cost_kind == MPCD_COST_CALMPC) {
+        J = 0.0;
+        for (int i = 0; i < nx; ++i) J = J + S.Q[i] * (x[i] * x[i]);
+        u[0] = (double)unnorm1(ur[0], clip, mn[0], mx[0]);
+        J = J + S.R[0] * (u[0] * u[0]);
+        for (int i = 0; i < nx; ++i) xn[i] = x[i];
+        double ucur = u[0];
+        for (int i = 1; i < H - 1; ++i) {
+            dyn_step<SYS>(S, x, &ucur, xn);
+            const double un = (double)unnorm1(ur[i * nu], clip, mn[0], mx[0]);
+            for (int j = 1; j < nx; ++j) J = J + S.Q[j] * (xn[j] * xn[j]);
+            J = J + S.R[0] * (un * un);
+            ucur = un;
+            for (int j = 0; j < nx; ++j) x[j] = xn[j];
+        }
+        for (int i = 0; i < nx; ++i) J = J + S.P[i] * (xn[i] * xn[i]);
+    } else {
+        const double zero[4] = {0.0, 0.0, 0.0, 0.0};
+        J = quadform<nx>(S.Q, x, S.xr);
+        for (int k = 0; k < H; ++k) {
+            for (int i = 0; i < nu; ++i) u[i] = (double)unnorm1(ur[k * nu + i], clip, mn[i], mx[i]);
+            dyn_step<SYS>(S, x, u, xn);
+            const double sx = k < H - 1 ? quadform<nx>(S.Q, xn, S.xr) : quadform<nx>(S.P, xn, S.xr);
+            const double sv = quadform<nu>(S.R, u, zero);
+            J = J + (sx + sv);
+            for (int j = 0; j < nx; ++j) x[j] = xn[j];
+        }
+    }
+    return J;
+}
+
+// NormK's constants before their (exact) promotion to fp64: half the kernel-argument registers
+struct NormF {
+    float mn[12], den[12];
+};
+
+// Grid: n_states * wps workgroups, wps = ceil(group / RT_THREADS); workgroup (m, j) owns candidates
+// [m * group + j * RT_THREADS, ...) of plant state m. Per state:
+//  - every workgroup recomputes the state's clip code (clip_flags_kernel's test over the state's slice of clip_src),
+//    rolls out and costs its candidates from x_dev[m] (rollout_cost_kernel's expressions) and leaves its argmin
+//    partial; select_first: the only entrant is the group's first candidate;
+//  - the last workgroup to arrive (counters[m], reset by it; rollout_cost_kernel<SYS, true>'s counter / fence /
+//    better() protocol) reduces the state's partials, takes control_step_kernel's plant step x_dev[m] <- f(x_dev[m],
+//    u0) - every other workgroup of the state has read x_dev[m] by then: its partial depends on it - and writes the
+//    history rows, the next context row (normalize_states_kernel's formula) and the next prior (shift_plan_kernel's
+//    rule on the winner's normalised plan), one row per state or one per candidate (repeat_rows).
+template <int SYS>
+__global__ __launch_bounds__(RT_THREADS) void closed_loop_tail_kernel(const SysK S, const NormF nk, const ClosedLoopTail T)
+{
+    constexpr int nx = SysDim<SYS>::NX, nu = SysDim<SYS>::NU;
+    extern __shared__ float su[];  // [RT_THREADS][H*nu + 1]
+    const int H = T.H, row = H * nu, stride = row + 1;
+    const int wps = (int)((T.group + RT_THREADS - 1) / RT_THREADS);
+    const int64_t m = blockIdx.x / wps;
+    const int j = (int)(blockIdx.x - m * wps);
+    const int64_t base = m * T.group, end = base + T.group;
+    const int64_t c0 = base + (int64_t)j * RT_THREADS;
+    stage_rows(T.u_norm + (size_t)c0 * row, min((int64_t)RT_THREADS, end - c0), row, su);
+    int code;
+    {
+        const float hi = (float)(1.0 + 1e-4), lo = (float)(-1.0 - 1e-4);
+        const float *cs = T.clip_src + (size_t)m * T.clip_per_state;
+        unsigned any = 0;
+        const int64_t n4 = ((uintptr_t)cs & 15) ? 0 : T.clip_per_state >> 2;
+#pragma unroll 8
+        for (int64_t i = threadIdx.x; i < n4; i += RT_THREADS) {
+            const f32x4 v = ldg4(cs + 4 * i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) any |= clip_bits(v[e], hi, lo);
+        }
+        for (int64_t i = 4 * n4 + threadIdx.x; i < T.clip_per_state; i += RT_THREADS) any |= clip_bits(cs[i], hi, lo);
+        __shared__ unsigned blk;
+        if (threadIdx.x == 0) blk = 0;
+        __syncthreads();
+        if (any) atomicOr(&blk, any);
+        __syncthreads();
+        code = clip_code(blk);
+    }
+    __syncthreads();
+    const bool clip = code == 1;
+    const int64_t b = min(c0 + threadIdx.x, end - 1);  // lanes past the group recompute its last candidate
+    double x[nx];
+#pragma unroll
+    for (int i = 0; i < nx; ++i) x[i] = T.x_dev[m * nx + i];
+    const double J = candidate_cost<SYS>(S, su + (b - c0) * stride, clip, x, H);
+    double v = isnan(J) ? INFINITY : J;
+    int64_t i = c0 + threadIdx.x < end && (!T.select_first || b == base) ? b : -1;
+    wave_argmin(v, i);  // RT_THREADS == one wave; every lane holds the result
+    const double raw = __shfl(J, i >= 0 ? (int)(i - c0) : 0);  // the entrant's cost as computed (a NaN stays one)
+    __shared__ bool last;
+    if (threadIdx.x == 0) {
+        T.part_cost[blockIdx.x] = v;
+        T.part_idx[blockIdx.x] = i;
+        T.part_raw[blockIdx.x] = raw;
+        __threadfence();
+        last = atomicAdd(T.counters + m, 1u) == (unsigned)wps - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    v = INFINITY;
+    i = -1;
+    for (int k = threadIdx.x; k < wps; k += RT_THREADS) {
+        const double pv = __builtin_nontemporal_load(T.part_cost + m * wps + k);
+        const int64_t pi = __builtin_nontemporal_load(T.part_idx + m * wps + k);
+        if (better(pv, pi, v, i)) { v = pv; i = pi; }
+    }
+    wave_argmin(v, i);
+    __shared__ float ctx_row[16];
+    if (threadIdx.x == 0) T.counters[m] = 0u;
+    if (i >= 0) {
+        // every lane computes the (wave-uniform) plant step and lane 0 stores it: with the fp64 pow and the dynamics
+        // inside a one-lane branch the quadrotor kernel reserved a 36-byte private segment
+        double xc[nx], xn[nx], u[nu];
+#pragma unroll
+        for (int e = 0; e < nx; ++e) xc[e] = T.x_dev[m * nx + e];
+#pragma unroll
+        for (int e = 0; e < nu; ++e) {
+            double o = (double)unnorm1(T.u_norm[(size_t)i * row + e], clip, S.umin[e], S.umax[e]);
+            if (T.decimals >= 0) {
+                const double sc = pow(10.0, (double)T.decimals);
+                o = rint(o * sc) / sc;
+            }
+            u[e] = o;
+        }
+        dyn_step<SYS>(S, xc, u, xn);
+        const double raw_best = __builtin_nontemporal_load(T.part_raw + m * wps + (i - base) / RT_THREADS);
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int e = 0; e < nx; ++e) {
+                T.x_dev[m * nx + e] = xn[e];
+                T.x_next[m * nx + e] = xn[e];
+                ctx_row[e] = (float)(2.0 * ((xn[e] - (double)nk.mn[e]) / (double)nk.den[e]) - 1.0);
+            }
+#pragma unroll
+            for (int e = 0; e < nu; ++e) T.u_applied[m * nu + e] = u[e];
+            T.best_idx[m] = i;
+            T.best_cost[m] = raw_best;
+        }
+    }
+    __syncthreads();
+    if (i < 0) return;
+    const int64_t reps = T.repeat_rows ? T.group : 1;
+    float *co = T.ctx_out + (size_t)m * reps * nx;
+    for (int64_t e = threadIdx.x; e < reps * nx; e += RT_THREADS) co[e] = ctx_row[e % nx];
+    if (T.prior_out) {
+        const float *wr = T.u_norm + (size_t)i * row;
+        float *po = T.prior_out + (size_t)m * reps * row;
+        for (int64_t e = threadIdx.x; e < reps * row; e += RT_THREADS) {
+            const int k = (int)(e % row), h = k / nu;
+            po[e] = wr[min(h + 1, H - 1) * nu + (k - h * nu)];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void repeat_rows_kernel(const float *rows, int64_t total, int64_t n, int row_len, float *out)
+{
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = e / row_len;
+        out[e] = rows[(r / n) * row_len + (e - r * row_len)];
+    }
+}
+
 }  // namespace
+
+hipError_t launch_repeat_rows(const float *rows, int64_t n_rows, int64_t n, int row_len, float *out, hipStream_t stream)
+{
+    const int64_t total = n_rows * n * row_len;
+    const int64_t blocks = std::min<int64_t>(4096, (total + 255) / 256);
+    hipLaunchKernelGGL(repeat_rows_kernel, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, stream, rows, total,
+                       n, row_len, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_closed_loop_tail(const mpcd_system_desc &d, const float *umin_host, const float *umax_host,
+                                   const float *cmin_host, const float *cmax_host, const ClosedLoopTail &t,
+                                   hipStream_t stream)
+{
+    SysK S = {};
+    S.system = d.system;
+    S.cost_kind = d.cost_kind;
+    S.nx = d.n_x;
+    S.nu = d.n_u;
+    for (int i = 0; i < 24; ++i) S.params[i] = d.params[i];
+    for (int i = 0; i < 12; ++i) { S.Q[i] = d.Q[i]; S.P[i] = d.P[i]; S.xr[i] = d.x_ref[i]; }
+    for (int i = 0; i < 4; ++i) S.R[i] = d.R[i];
+    for (int i = 0; i < d.n_u; ++i) { S.umin[i] = umin_host[i]; S.umax[i] = umax_host[i]; }
+    NormF nk;
+    for (int i = 0; i < 12; ++i) {
+        nk.mn[i] = i < d.n_x ? cmin_host[i] : 0.f;
+        nk.den[i] = i < d.n_x ? cmax_host[i] - cmin_host[i] : 1.f;  // fp32 subtraction; promoted in the kernel
+    }
+    const int64_t wgs = t.n_states * ((t.group + RT_THREADS - 1) / RT_THREADS);
+    if (t.n_states < 1 || t.group < 1 || wgs > 0x7fffffff) return hipErrorInvalidValue;
+    const size_t lds = sizeof(float) * RT_THREADS * (t.H * d.n_u + 1);
+#define MPCD_TAIL(SYS_)                                                                                            \
+    case SYS_:                                                                                                     \
+        if (d.n_x != SysDim<SYS_>::NX || d.n_u != SysDim<SYS_>::NU) return hipErrorInvalidValue;                   \
+        hipLaunchKernelGGL(closed_loop_tail_kernel<SYS_>, dim3((unsigned)wgs), dim3(RT_THREADS), lds, stream, S, nk, t); \
+        break;
+    switch (d.system) {
+        MPCD_TAIL(MPCD_SYS_CARTPOLE_LIN5)
+        MPCD_TAIL(MPCD_SYS_CARTPOLE_NL5)
+        MPCD_TAIL(MPCD_SYS_CARTPOLE_ZOH4)
+        MPCD_TAIL(MPCD_SYS_DOUBLE_INT2D)
+        MPCD_TAIL(MPCD_SYS_PENDULUM)
+        MPCD_TAIL(MPCD_SYS_QUADROTOR12)
+    default: return hipErrorInvalidValue;
+    }
+#undef MPCD_TAIL
+    return hipGetLastError();
+}
 
 hipError_t launch_shift_plans(const float *rows, int64_t batch, int H, int d, const int64_t *index, int64_t offset,
                               int64_t n_states, float *out, hipStream_t stream)

@@ -120,6 +120,7 @@ class ClosedLoopResult:
     u: np.ndarray           # [M, T, n_u] applied actions (unnormalised, rounded as requested)
     cost: np.ndarray        # [M, T] cost of the selected candidate at each step
     index: np.ndarray       # [M, T] global index of the selected candidate in that step's batch
+    u_norm: torch.Tensor = None  # [M * n, H, d] the last iteration's normalised samples (native=True only)
 
 
 class DiffusionMPC:
@@ -528,7 +529,7 @@ class DiffusionMPC:
 
     def closed_loop(self, x0_states, system: System, iterations, n_samples=1, w=0.01, sample_fn="ddpm_cfg",
                     n_wo_noise=0, ddim_steps=None, clamp_x0=False, select="argmin", decimals=4, seed=0, noise=None,
-                    clip_rule="chain", grouped=False, warm_start=None):
+                    clip_rule="chain", grouped=False, warm_start=None, native=False):
         """Closed-loop diffusion MPC for M plant states at once, resident on the device.
         The reference runs one initial state at a time on the host (Cart_Diffusion_inference.py:405-512:
         normalize_condition -> run_CFG -> unnormalize -> u0 = round(u[0], 4) -> x = f(x, u0), repeated
@@ -553,7 +554,13 @@ class DiffusionMPC:
         the later iterations sample from it with t_start=K (see sample_trajectories): K + n_wo_noise denoise steps
         instead of N + n_wo_noise. grouped=True where grouped_pays(): the [M, H, d] priors go in as they are; else
         they are repeated per candidate like the contexts. noise(it) must then return K + n_wo_noise + 1 slices for
-        it >= 1. Under clip_rule="chain" a warm iteration's clip test sees the noised prior, not x_T."""
+        it >= 1. Under clip_rule="chain" a warm iteration's clip test sees the noised prior, not x_T.
+        native=True: the whole loop is ONE library call (mpcd_closed_loop) - per iteration the sampler and one fused
+        launch for the clip code, rollout, cost, selection, plant step, history rows and the next context row / prior -
+        with results bit for bit those of native=False (the default, the composed calls above). noise(it) is then
+        evaluated for every iteration up front, and the result's u_norm holds the last iteration's samples. An f16x2
+        spec raises ValueError: its range guard reads the chain maxima on the host in every iteration, the round trip
+        the native loop removes."""
         K = None if warm_start is None else int(warm_start)
         if K is not None and (K < 1 or K > self.n_steps or self._sampler_id(sample_fn) != N.MPCD_DDPM_CFG):
             raise ValueError(f"warm_start={K} needs 1 <= K <= {self.n_steps} and the CFG-DDPM sampler")
@@ -570,6 +577,9 @@ class DiffusionMPC:
             raise ValueError(f"closed loop conditions on the plant state: context_dim {self.spec.context_dim} != n_x {nx}")
         T, n, H, d = int(iterations), int(n_samples), self.spec.horizon, self.spec.state_dim
         B, dev, st = M * n, self.device, self._stream()
+        if native:
+            return self._closed_loop_native(x0, system, T, n, w, sample_fn, n_wo_noise, ddim_steps, clamp_x0, select,
+                                            decimals, seed, noise, clip_rule, grouped, K)
         desc = system.desc()
         x = torch.from_numpy(x0).to(dev)
         xs = torch.empty((T + 1, M, nx), dtype=torch.float64, device=dev)
@@ -610,6 +620,58 @@ class DiffusionMPC:
             xs[it + 1] = x
         return ClosedLoopResult(x=xs.transpose(0, 1).cpu().numpy(), u=us.transpose(0, 1).cpu().numpy(),
                                 cost=cs.t().cpu().numpy(), index=ix.t().cpu().numpy())
+
+    def _closed_loop_native(self, x0, system, T, n, w, sample_fn, n_wo_noise, ddim_steps, clamp_x0, select, decimals,
+                            seed, noise, clip_rule, grouped, K):
+        """closed_loop(native=True): one mpcd_closed_loop call; the arguments are closed_loop's, already checked."""
+        if self.spec.dtype == "f16x2":
+            raise ValueError("closed_loop(native=True) does not take an f16x2 spec: its range guard reads the chain "
+                             "maxima on the host in every iteration, the round trip the native loop removes")
+        M, nx = x0.shape
+        H, d, B, dev = self.spec.horizon, self.spec.state_dim, M * n, self.device
+        noises = None
+        if noise is not None:  # evaluated up front and kept alive until the results are on the host
+            cold = self.n_denoise_steps(sample_fn, n_wo_noise, ddim_steps)
+            later = cold if K is None else self.n_denoise_steps(sample_fn, n_wo_noise, ddim_steps, K)
+            noises = []
+            for it in range(T):
+                z = noise(it).to(dev, torch.float32).contiguous()
+                steps = cold if it == 0 else later
+                if tuple(z.shape) != (steps + 1, B, H, d):
+                    raise ValueError(f"noise must be [{steps + 1}, {B}, {H}, {d}], got {tuple(z.shape)}")
+                noises.append(z)
+        grouped = bool(grouped) and self.grouped_pays(M, n, sample_fn)
+        x = torch.from_numpy(x0).to(dev)
+        xs = torch.empty((T + 1, M, nx), dtype=torch.float64, device=dev)
+        us = torch.empty((T, M, d), dtype=torch.float64, device=dev)
+        cs = torch.empty((T, M), dtype=torch.float64, device=dev)
+        ix = torch.empty((T, M), dtype=torch.int64, device=dev)
+        desc = system.desc()
+        a = N.ClosedLoopArgs()
+        a.sys = ctypes.pointer(desc)
+        a.ctx_min, a.ctx_max = self.ctx_min.ctypes.data, self.ctx_max.ctypes.data
+        a.act_min, a.act_max = self.act_min.ctypes.data, self.act_max.ctypes.data
+        u_norm = torch.empty((B, H, d), dtype=torch.float32, device=dev)
+        a.sample = self._args(self._sampler_id(sample_fn), B, _STEP_CONTEXT, w, n_wo_noise, ddim_steps, clamp_x0, seed, 0,
+                              None, u_norm, None)
+        a.sample.x_out = None  # ignored by the call: it samples into its workspace and copies the last iteration out
+        a.u_norm = u_norm.data_ptr()
+        a.n_states, a.group, a.iterations = M, n, T
+        a.group_contexts = 1 if grouped else 0
+        if noises is not None:
+            ptrs = (ctypes.c_void_p * T)(*[z.data_ptr() for z in noises])
+            a.noise_iters = ctypes.cast(ptrs, ctypes.POINTER(ctypes.c_void_p))
+        a.clip_rule = _CLIP_RULES[clip_rule]
+        a.select_first = 1 if select == "first" else 0
+        a.decimals = -1 if decimals is None else int(decimals)
+        a.warm_t_start = 0 if K is None else K
+        a.x_dev, a.x_hist, a.u_hist = x.data_ptr(), xs.data_ptr(), us.data_ptr()
+        a.cost_hist, a.index_hist = cs.data_ptr(), ix.data_ptr()
+        N.check(self._lib.mpcd_closed_loop(self._ctx, ctypes.byref(a), self._stream()), "mpcd_closed_loop")
+        res = ClosedLoopResult(x=xs.transpose(0, 1).cpu().numpy(), u=us.transpose(0, 1).cpu().numpy(),
+                               cost=cs.t().cpu().numpy(), index=ix.t().cpu().numpy(), u_norm=u_norm)
+        del noises  # the copies above waited for the loop: its inputs may go now
+        return res
 
     def mpc_step(self, x0, system: System, n_samples, w=0.01, sample_fn="ddpm_cfg", n_wo_noise=0, ddim_steps=None,
                  clamp_x0=False, seed=0, noise=None, group=None, comm=None, native=None, clip_rule="chain",
