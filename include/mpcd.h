@@ -330,6 +330,67 @@ typedef struct {
  * reused and grown across calls: like every context workspace it is ordered on ONE stream. */
 int mpcd_closed_loop(mpcd_ctx *ctx, const mpcd_closed_loop_args *args, void *hip_stream);
 
+/* ---- One control step for many plant states that arrive from OUTSIDE (a vectorised simulator, a plant with model
+ * mismatch or disturbances, a fleet of devices). mpcd_closed_loop owns its plant; mpcd_mpc_step takes one state per
+ * call. mpcd_mpc_step_batch takes n_states fp64 states from the host and returns every state's applied action,
+ * selected plan, cost, index and flags to the host in ONE call: one host-to-device copy of the states through pinned
+ * staging, mpcd_normalize_states, the sampler over n_states * group candidates (grouped, or each state's row repeated
+ * per candidate), ONE launch (batch_step_tail_kernel, csrc/rollout.hip) for each state's clip code, the fp64 rollout
+ * and cost of its candidates, the selection (NaN = +inf, lowest index on ties, or the group's first candidate), u0
+ * unnormalised and rounded, the selected plan unnormalised and the next prior, then one device-to-host copy of the
+ * packed result block into pinned memory of the context and one stream synchronisation. The host outputs are complete
+ * when the call returns.
+ * Given states equal to a closed-loop iteration's x_dev (and that iteration's seed, noise and warm start) the call
+ * computes bit for bit what that iteration of mpcd_closed_loop computes up to and including the selection and u0, and
+ * the same next prior. It takes no plant step and writes no history rows and no next context row.
+ * Flags per state: MPCD_STEP_CLIPPED / MPCD_STEP_NAN_SAMPLES from the state's clip code (1 / 2) and
+ * MPCD_STEP_NONFINITE_WINNER when the selected cost is not finite.
+ * Returns MPCD_ENONFINITE when any state carries MPCD_STEP_NONFINITE_WINNER: all outputs are still written and the
+ * other states' results are valid.
+ * MPCD_EINVAL: a NULL required pointer, n_states / group < 1, sys->n_u != the net's state_dim, sys->n_x != its
+ * context_dim, clip_rule == MPCD_CLIP_NONE (or unknown), decimals > 15, warm_t_start outside [0, n_steps],
+ * warm_t_start > 0 without priors.
+ * MPCD_EUNSUP: an MPCD_F16X2 net (its range guard reads the chain maxima on the host and re-runs the sampler: a
+ * second round trip inside the step); a context with a communicator (the step is single-rank); warm_t_start > 0 with
+ * a sampler other than MPCD_DDPM_CFG; H * n_u too large for the tail's LDS. */
+typedef struct {
+    double cost;      /* the selected candidate's cost as computed (a NaN stays one) */
+    int64_t index;    /* its global index in this call's batch: m * group + j */
+    int32_t flags;    /* per state: MPCD_STEP_CLIPPED | MPCD_STEP_NAN_SAMPLES | MPCD_STEP_NONFINITE_WINNER */
+    int32_t reserved; /* 0 */
+} mpcd_state_result;
+
+typedef struct {
+    const mpcd_system_desc *sys;    /* the PLANNING model: n_u == the net's state_dim, n_x == its context_dim */
+    const float *ctx_min, *ctx_max; /* host [n_x] condition limits (mpcd_normalize_states) */
+    const float *act_min, *act_max; /* host [n_u] action limits */
+    mpcd_sample_args sample;        /* as in mpcd_closed_loop_args: the sampler, w, n_wo_noise, the DDIM fields and
+                                       clamp_x0; seed and noise are THIS step's (noise: injected [S + 1][B][H][d], S =
+                                       warm_t_start + n_wo_noise for a warm step, or NULL = Philox). batch, context,
+                                       context_shared, global_offset, x_out, chain_out and chain_absmax are ignored:
+                                       batch = n_states * group, global_offset 0 */
+    int64_t n_states;               /* M plant states */
+    int64_t group;                  /* n candidates per state */
+    int32_t group_contexts;         /* mpcd_closed_loop_args' meaning */
+    int32_t clip_rule;              /* MPCD_CLIP_CHAIN or MPCD_CLIP_FINAL, per state over its own candidates */
+    int32_t select_first;           /* mpcd_control_step's */
+    int32_t decimals;               /* mpcd_control_step's (< 0: no rounding) */
+    int32_t warm_t_start;           /* 0: a cold step; K >= 1: sample from `priors` with t_start = K (CFG-DDPM only) */
+    const double *x_host;           /* host [M][n_x] fp64 plant states, read during the call */
+    float *priors;                  /* dev [M][H][d] or NULL. Read when warm_t_start > 0 (then required); when non-NULL
+                                       it is overwritten, after the sampler has read it, with the NEXT priors: each
+                                       state's selected plan under mpcd_shift_plans' rule */
+    mpcd_state_result *result_host; /* host [M] */
+    double *u_host;                 /* host [M][n_u]: the applied action (unnormalised with the state's clip flag,
+                                       rounded to `decimals`) */
+    float *plan_host;               /* host [M][H][d] or NULL: the selected plan, unnormalised the same way */
+    float *u_norm;                  /* dev [B][H][d] or NULL: all normalised samples of this step */
+} mpcd_batch_step_args;
+/* The context owns the step's workspace (state and context rows, per-state counters, partials, samples, chain maxima,
+ * repeated priors, the packed result block) and its pinned host staging, reused and grown across calls like the closed
+ * loop's; the per-state counters reset themselves. Like every context workspace it is ordered on ONE stream. */
+int mpcd_mpc_step_batch(mpcd_ctx *ctx, const mpcd_batch_step_args *args, void *hip_stream);
+
 /* ---- Candidate-batch data parallelism over RCCL / xGMI. One process per GPU, one
  * communicator per context; rank r owns global candidates [r*B_local, (r+1)*B_local). The reference has
  * no distributed code: these entry points are new design, not replacements. */

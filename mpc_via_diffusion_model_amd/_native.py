@@ -73,6 +73,21 @@ class ClosedLoopArgs(ctypes.Structure):
                 ("u_norm", ctypes.c_void_p)]
 
 
+class StateResult(ctypes.Structure):
+    _fields_ = [("cost", ctypes.c_double), ("index", ctypes.c_int64), ("flags", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class BatchStepArgs(ctypes.Structure):
+    _fields_ = [("sys", ctypes.POINTER(SystemDesc)), ("ctx_min", ctypes.c_void_p), ("ctx_max", ctypes.c_void_p),
+                ("act_min", ctypes.c_void_p), ("act_max", ctypes.c_void_p), ("sample", SampleArgs),
+                ("n_states", ctypes.c_int64), ("group", ctypes.c_int64), ("group_contexts", ctypes.c_int32),
+                ("clip_rule", ctypes.c_int32), ("select_first", ctypes.c_int32), ("decimals", ctypes.c_int32),
+                ("warm_t_start", ctypes.c_int32), ("x_host", ctypes.c_void_p), ("priors", ctypes.c_void_p),
+                ("result_host", ctypes.c_void_p), ("u_host", ctypes.c_void_p), ("plan_host", ctypes.c_void_p),
+                ("u_norm", ctypes.c_void_p)]
+
+
 class TrainCfg(ctypes.Structure):
     _fields_ = [("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
                 ("ema_decay", ctypes.c_float), ("step_start_ema", ctypes.c_int32), ("update_ema_every", ctypes.c_int32)]
@@ -124,6 +139,7 @@ EXPORTS = {
                            ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                            ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "mpcd_closed_loop": ([ctypes.c_void_p, ctypes.POINTER(ClosedLoopArgs), ctypes.c_void_p], ctypes.c_int),
+    "mpcd_mpc_step_batch": ([ctypes.c_void_p, ctypes.POINTER(BatchStepArgs), ctypes.c_void_p], ctypes.c_int),
     "mpcd_comm_unique_id": ([ctypes.c_void_p], ctypes.c_int),
     "mpcd_comm_init": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p], ctypes.c_int),
     "mpcd_philox_noise": ([ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,

@@ -195,5 +195,27 @@ struct ClosedLoopTail {
 hipError_t launch_closed_loop_tail(const mpcd_system_desc &d, const float *umin_host, const float *umax_host,
                                    const float *cmin_host, const float *cmax_host, const ClosedLoopTail &t,
                                    hipStream_t stream);
+// One control step of externally supplied states (rollout.hip batch_step_tail_kernel, mpcd_mpc_step_batch):
+// everything after the sampler in one launch of closed_loop_tail_kernel's grid. Device pointers. The packed result
+// block `result` is what one device-to-host copy returns: n_states records of rec_stride bytes, each
+// {mpcd_state_result, double u[n_u]}, then at plan_off the selected plans, float [n_states][H * n_u].
+struct BatchStepTail {
+    const float *u_norm;   // [n_states * group][H][n_u] this step's samples
+    const float *clip_src; // chain rule: chain_absmax [n_states * group]; final rule: u_norm
+    int64_t clip_per_state;  // floats of clip_src per state: group, or group * H * n_u
+    const double *x_dev;   // [n_states][n_x], read only
+    int64_t n_states, group;
+    int32_t H, select_first, decimals;
+    // per-workgroup partials and self-resetting per-state counters, as ClosedLoopTail's
+    double *part_cost, *part_raw;
+    int64_t *part_idx;
+    unsigned *counters;
+    char *result;
+    int64_t rec_stride, plan_off;
+    float *prior_out;      // [n_states][H][n_u] the next priors, or null
+};
+constexpr int64_t batch_step_rec_stride(int n_u) { return (int64_t)sizeof(mpcd_state_result) + 8 * n_u; }
+hipError_t launch_batch_step_tail(const mpcd_system_desc &d, const float *umin_host, const float *umax_host,
+                                  const BatchStepTail &t, hipStream_t stream);
 // out[r * n + j][:] = rows[r][:] for j < n (the per-candidate rows of iteration 0 when the loop is not grouped)
 hipError_t launch_repeat_rows(const float *rows, int64_t n_rows, int64_t n, int row_len, float *out, hipStream_t stream);

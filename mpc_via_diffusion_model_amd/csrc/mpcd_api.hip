@@ -301,6 +301,11 @@ struct mpcd_ctx {
     DevBuf step_ctx, step_part, step_out, step_amax;
     // mpcd_closed_loop: partials, samples, chain maxima, context rows and priors; one self-resetting counter per state
     DevBuf loop_ws, loop_cnt;
+    // mpcd_mpc_step_batch: the same kinds of parts plus the states and the packed result block; its own self-resetting
+    // counters; pinned host staging [states | result block] (one H2D and one D2H copy per call)
+    DevBuf batch_ws, batch_cnt;
+    void *batch_host = nullptr;
+    size_t batch_host_bytes = 0;
     void *step_host = nullptr;
     void *step_host_dev = nullptr;  // step_host's device address (mapped pinned memory)
     size_t step_host_bytes = 0;
@@ -626,7 +631,8 @@ void mpcd_destroy(mpcd_ctx *c)
     if (!c) return;
     DeviceGuard device_guard_(c->device);
     for (DevBuf *b : {&c->params, &c->wpack, &c->wpack3, &c->wpackh, &c->cond_layers, &c->unet_pack, &c->plan, &c->tproj, &c->cproj, &c->flag,
-                      &c->unet_ws, &c->step_ctx, &c->step_part, &c->step_out, &c->step_amax, &c->loop_ws, &c->loop_cnt})
+                      &c->unet_ws, &c->step_ctx, &c->step_part, &c->step_out, &c->step_amax, &c->loop_ws, &c->loop_cnt,
+                      &c->batch_ws, &c->batch_cnt})
         b->release();
     for (int i = 0; i < mpcd_ctx::kEvRing; ++i)
         for (int j = 0; j < 2; ++j)
@@ -634,6 +640,7 @@ void mpcd_destroy(mpcd_ctx *c)
     if (c->plan_ev) (void)hipEventDestroy(c->plan_ev);
     delete c->comm;
     if (c->step_host) (void)hipHostFree(c->step_host);
+    if (c->batch_host) (void)hipHostFree(c->batch_host);
     delete c;
 }
 
@@ -1305,6 +1312,157 @@ int mpcd_closed_loop(mpcd_ctx *c, const mpcd_closed_loop_args *a, void *stream_p
     }
     if (a->u_norm)
         HIP_TRY(hipMemcpyAsync(a->u_norm, u_norm, sizeof(float) * B * H * nu, hipMemcpyDeviceToDevice, st));
+    return MPCD_OK;
+}
+
+int mpcd_mpc_step_batch(mpcd_ctx *c, const mpcd_batch_step_args *a, void *stream_ptr)
+{
+    if (!c || !a) return fail(MPCD_EINVAL, "null argument");
+    if (!a->sys || !a->ctx_min || !a->ctx_max || !a->act_min || !a->act_max || !a->x_host || !a->result_host || !a->u_host)
+        return fail(MPCD_EINVAL, "mpcd_mpc_step_batch: null argument");
+    if (a->n_states < 1 || a->group < 1)
+        return fail(MPCD_EINVAL, "mpcd_mpc_step_batch: n_states %lld / group %lld < 1", (long long)a->n_states,
+                    (long long)a->group);
+    if (a->clip_rule != MPCD_CLIP_CHAIN && a->clip_rule != MPCD_CLIP_FINAL)
+        return fail(MPCD_EINVAL, "mpcd_mpc_step_batch: clip_rule %d (MPCD_CLIP_CHAIN or MPCD_CLIP_FINAL)", a->clip_rule);
+    if (a->decimals > 15) return fail(MPCD_EINVAL, "decimals > 15");
+    if (!c->net_loaded) return fail(MPCD_ESTATE, "no net loaded");
+    if (!c->n_steps) return fail(MPCD_ESTATE, "no schedule set");
+    const mpcd_net_desc &d = c->desc;
+    const mpcd_system_desc &sys = *a->sys;
+    if (sys.n_u != d.state_dim) return fail(MPCD_EINVAL, "system n_u %d != net state_dim %d", sys.n_u, d.state_dim);
+    if (sys.n_x != d.context_dim)
+        return fail(MPCD_EINVAL, "the step conditions on the plant state: n_x %d != net context_dim %d", sys.n_x,
+                    d.context_dim);
+    if (d.dtype == MPCD_F16X2)
+        return fail(MPCD_EUNSUP, "mpcd_mpc_step_batch: an MPCD_F16X2 net's range guard reads the chain maxima on the host "
+                                 "and re-runs the sampler, a second round trip inside the step");
+    if (c->comm) return fail(MPCD_EUNSUP, "mpcd_mpc_step_batch is single-rank: the context has a communicator");
+    const int H = d.horizon, nu = sys.n_u, nx = sys.n_x;
+    int rc = check_system(&sys, H);
+    if (rc) return rc;
+    if ((size_t)(H * nu + 1) * 64 * sizeof(float) > 64 * 1024) return fail(MPCD_EUNSUP, "H*n_u too large");
+    const int64_t M = a->n_states, n = a->group;
+    if (M > INT32_MAX || n > ((int64_t)1 << 40) / M) return fail(MPCD_EINVAL, "n_states * group too large");
+    const int64_t B = M * n, wps = (n + kRolloutBlock - 1) / kRolloutBlock;
+    if (M * wps > INT32_MAX) return fail(MPCD_EINVAL, "n_states * ceil(group / 64) workgroups exceed a grid");
+    const bool grouped = a->group_contexts != 0, chain_rule = a->clip_rule == MPCD_CLIP_CHAIN;
+    const int64_t rows = grouped ? M : B;  // context rows / priors the sampler takes
+    const int row = H * nu;
+
+    mpcd_sample_args s = a->sample;
+    s.batch = B;
+    s.context_shared = 0;
+    s.global_offset = 0;
+    s.chain_out = nullptr;
+    if (a->warm_t_start < 0 || a->warm_t_start > c->n_steps)
+        return fail(MPCD_EINVAL, "warm_t_start %d outside [0, %d]", a->warm_t_start, c->n_steps);
+    if (a->warm_t_start > 0 && !a->priors)
+        return fail(MPCD_EINVAL, "mpcd_mpc_step_batch: warm_t_start %d without priors", a->warm_t_start);
+    if (a->warm_t_start > 0 && s.sampler != MPCD_DDPM_CFG)
+        return fail(MPCD_EUNSUP, "warm start (warm_t_start > 0) is implemented for the CFG-DDPM sampler only");
+    hipStream_t st = static_cast<hipStream_t>(stream_ptr);
+    DEVICE_GUARD(c->device);
+
+    // workspace, every part 256-byte aligned: fp64 parts first. The packed result block (BatchStepTail): M records
+    // {mpcd_state_result, u[n_u]}, then the selected plans
+    size_t off = 0;
+    auto carve = [&off](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return at;
+    };
+    const int64_t rec_stride = batch_step_rec_stride(nu);
+    const size_t plan_off = ((size_t)(M * rec_stride) + 255) & ~(size_t)255;
+    const size_t res_bytes = plan_off + sizeof(float) * M * row, x_bytes = sizeof(double) * M * nx;
+    const bool repeat_priors = a->warm_t_start > 0 && !grouped;
+    const size_t o_x = carve(x_bytes), o_pc = carve(sizeof(double) * M * wps), o_pr = carve(sizeof(double) * M * wps),
+                 o_pi = carve(sizeof(int64_t) * M * wps), o_res = carve(res_bytes), o_u = carve(sizeof(float) * B * row),
+                 o_amax = carve(chain_rule ? sizeof(float) * B : 0), o_ctx = carve(sizeof(float) * rows * nx),
+                 o_ctx0 = carve(grouped ? 0 : sizeof(float) * M * nx),
+                 o_prior = carve(repeat_priors ? sizeof(float) * B * row : 0);
+    if ((rc = c->batch_ws.ensure(off))) return rc;
+    if (sizeof(unsigned) * M > c->batch_cnt.bytes) {  // new counters start at zero; the kernel leaves them there
+        if ((rc = c->batch_cnt.ensure(sizeof(unsigned) * M))) return rc;
+        HIP_TRY(hipMemsetAsync(c->batch_cnt.p, 0, c->batch_cnt.bytes, st));
+    }
+    const size_t h_res = (x_bytes + 255) & ~(size_t)255, host_bytes = h_res + res_bytes;
+    if (c->batch_host_bytes < host_bytes) {  // the previous call ended in a stream synchronisation: nothing reads it
+        if (c->batch_host) (void)hipHostFree(c->batch_host);
+        c->batch_host = nullptr;
+        c->batch_host_bytes = 0;
+        HIP_TRY(hipHostMalloc(&c->batch_host, host_bytes, hipHostMallocDefault));
+        c->batch_host_bytes = host_bytes;
+    }
+    char *w = c->batch_ws.as<char>(), *hs = static_cast<char *>(c->batch_host);
+    double *x_dev = reinterpret_cast<double *>(w + o_x);
+    float *u_norm = reinterpret_cast<float *>(w + o_u);
+    float *amax = chain_rule ? reinterpret_cast<float *>(w + o_amax) : nullptr;
+    float *ctx = reinterpret_cast<float *>(w + o_ctx);
+
+    memcpy(hs, a->x_host, x_bytes);
+    HIP_TRY(hipMemcpyAsync(x_dev, hs, x_bytes, hipMemcpyHostToDevice, st));
+    if (grouped) {
+        HIP_TRY(launch_normalize_states(x_dev, M, nx, a->ctx_min, a->ctx_max, ctx, st));
+    } else {  // one row per candidate, each state's repeated
+        float *ctx0 = reinterpret_cast<float *>(w + o_ctx0);
+        HIP_TRY(launch_normalize_states(x_dev, M, nx, a->ctx_min, a->ctx_max, ctx0, st));
+        HIP_TRY(launch_repeat_rows(ctx0, M, n, nx, ctx, st));
+    }
+    s.context = ctx;
+    s.x_out = u_norm;
+    s.chain_absmax = amax;
+    WarmArgs warm;
+    if (a->warm_t_start) {  // resolved as mpcd_closed_loop resolves it: [M] priors grouped, else one per candidate
+        const float *prior = a->priors;
+        if (repeat_priors) {
+            float *rep = reinterpret_cast<float *>(w + o_prior);
+            HIP_TRY(launch_repeat_rows(a->priors, M, n, row, rep, st));
+            prior = rep;
+        }
+        const mpcd_warm_start ws{prior, rows, a->warm_t_start};
+        if ((rc = resolve_warm(c, &s, grouped ? n : 0, &ws, warm))) return rc;
+    }
+    rc = sample_impl(c, &s, stream_ptr, nullptr, grouped ? n : 0, a->warm_t_start ? &warm : nullptr);
+    if (rc) return rc;
+
+    BatchStepTail t{};
+    t.u_norm = u_norm;
+    t.clip_src = chain_rule ? amax : u_norm;
+    t.clip_per_state = chain_rule ? n : n * row;
+    t.x_dev = x_dev;
+    t.n_states = M;
+    t.group = n;
+    t.H = H;
+    t.select_first = a->select_first;
+    t.decimals = a->decimals;
+    t.part_cost = reinterpret_cast<double *>(w + o_pc);
+    t.part_raw = reinterpret_cast<double *>(w + o_pr);
+    t.part_idx = reinterpret_cast<int64_t *>(w + o_pi);
+    t.counters = c->batch_cnt.as<unsigned>();
+    t.result = w + o_res;
+    t.rec_stride = rec_stride;
+    t.plan_off = (int64_t)plan_off;
+    t.prior_out = a->priors;
+    HIP_TRY(launch_batch_step_tail(sys, a->act_min, a->act_max, t, st));
+    if (a->u_norm) HIP_TRY(hipMemcpyAsync(a->u_norm, u_norm, sizeof(float) * B * row, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(hs + h_res, w + o_res, res_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+
+    int64_t bad = 0, first_bad = -1;
+    for (int64_t m = 0; m < M; ++m) {
+        const char *rec = hs + h_res + m * rec_stride;
+        memcpy(&a->result_host[m], rec, sizeof(mpcd_state_result));
+        memcpy(a->u_host + m * nu, rec + sizeof(mpcd_state_result), sizeof(double) * nu);
+        if (a->result_host[m].flags & MPCD_STEP_NONFINITE_WINNER) {
+            if (!bad++) first_bad = m;
+        }
+    }
+    if (a->plan_host) memcpy(a->plan_host, hs + h_res + plan_off, sizeof(float) * M * row);
+    if (bad)
+        return fail(MPCD_ENONFINITE, "mpcd_mpc_step_batch: %lld of %lld states have no candidate with a finite cost "
+                                     "(first: state %lld); the other states' results are valid",
+                    (long long)bad, (long long)M, (long long)first_bad);
     return MPCD_OK;
 }
 

@@ -736,6 +736,118 @@ __global__ __launch_bounds__(RT_THREADS) void closed_loop_tail_kernel(const SysK
     }
 }
 
+// ---- The control tail of one step for externally supplied states (mpcd_mpc_step_batch): closed_loop_tail_kernel's
+// grid and, up to the cross-workgroup reduction, its pieces in its order; no plant step, no history, no context row.
+
+// clip_flags_kernel's test over one state's slice cs[0, n) by one wave, as closed_loop_tail_kernel restates it
+__device__ __forceinline__ int state_clip_code(const float *cs, int64_t n)
+{
+    const float hi = (float)(1.0 + 1e-4), lo = (float)(-1.0 - 1e-4);
+    unsigned any = 0;
+    const int64_t n4 = ((uintptr_t)cs & 15) ? 0 : n >> 2;
+#pragma unroll 8
+    for (int64_t i = threadIdx.x; i < n4; i += RT_THREADS) {
+        const f32x4 v = ldg4(cs + 4 * i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) any |= clip_bits(v[e], hi, lo);
+    }
+    for (int64_t i = 4 * n4 + threadIdx.x; i < n; i += RT_THREADS) any |= clip_bits(cs[i], hi, lo);
+    __shared__ unsigned blk;
+    if (threadIdx.x == 0) blk = 0;
+    __syncthreads();
+    if (any) atomicOr(&blk, any);
+    __syncthreads();
+    return clip_code(blk);
+}
+
+// Per state, the last workgroup to arrive (the closed-loop tail's counter / fence / better() protocol) writes into the
+// packed result block the state's record {cost as computed, index, flags, u[n_u] fp64: control_step_kernel's
+// unnormalise and rounding} and, cooperatively across the wave, the selected plan unnormalised under the state's clip
+// flag; with prior_out, the next prior (shift_plan_kernel's rule on the winner's normalised plan).
+template <int SYS>
+__global__ __launch_bounds__(RT_THREADS) void batch_step_tail_kernel(const SysK S, const BatchStepTail T)
+{
+    constexpr int nx = SysDim<SYS>::NX, nu = SysDim<SYS>::NU;
+    extern __shared__ float su[];  // [RT_THREADS][H*nu + 1]
+    const int H = T.H, row = H * nu, stride = row + 1;
+    const int wps = (int)((T.group + RT_THREADS - 1) / RT_THREADS);
+    const int64_t m = blockIdx.x / wps;
+    const int j = (int)(blockIdx.x - m * wps);
+    const int64_t base = m * T.group, end = base + T.group;
+    const int64_t c0 = base + (int64_t)j * RT_THREADS;
+    stage_rows(T.u_norm + (size_t)c0 * row, min((int64_t)RT_THREADS, end - c0), row, su);
+    const int code = state_clip_code(T.clip_src + (size_t)m * T.clip_per_state, T.clip_per_state);
+    __syncthreads();
+    const bool clip = code == 1;
+    const int64_t b = min(c0 + threadIdx.x, end - 1);  // lanes past the group recompute its last candidate
+    double x[nx];
+#pragma unroll
+    for (int i = 0; i < nx; ++i) x[i] = T.x_dev[m * nx + i];
+    const double J = candidate_cost<SYS>(S, su + (b - c0) * stride, clip, x, H);
+    double v = isnan(J) ? INFINITY : J;
+    int64_t i = c0 + threadIdx.x < end && (!T.select_first || b == base) ? b : -1;
+    wave_argmin(v, i);  // RT_THREADS == one wave; every lane holds the result
+    const double raw = __shfl(J, i >= 0 ? (int)(i - c0) : 0);  // the entrant's cost as computed (a NaN stays one)
+    __shared__ bool last;
+    if (threadIdx.x == 0) {
+        T.part_cost[blockIdx.x] = v;
+        T.part_idx[blockIdx.x] = i;
+        T.part_raw[blockIdx.x] = raw;
+        __threadfence();
+        last = atomicAdd(T.counters + m, 1u) == (unsigned)wps - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    v = INFINITY;
+    i = -1;
+    for (int k = threadIdx.x; k < wps; k += RT_THREADS) {
+        const double pv = __builtin_nontemporal_load(T.part_cost + m * wps + k);
+        const int64_t pi = __builtin_nontemporal_load(T.part_idx + m * wps + k);
+        if (better(pv, pi, v, i)) { v = pv; i = pi; }
+    }
+    wave_argmin(v, i);
+    if (threadIdx.x == 0) T.counters[m] = 0u;
+    if (i < 0) return;  // not reached: group >= 1 leaves an entrant in the state's first workgroup
+    // every lane computes the (wave-uniform) action and lane 0 stores it, as in closed_loop_tail_kernel
+    double u[nu];
+#pragma unroll
+    for (int e = 0; e < nu; ++e) {
+        double o = (double)unnorm1(T.u_norm[(size_t)i * row + e], clip, S.umin[e], S.umax[e]);
+        if (T.decimals >= 0) {
+            const double sc = pow(10.0, (double)T.decimals);
+            o = rint(o * sc) / sc;
+        }
+        u[e] = o;
+    }
+    const double raw_best = __builtin_nontemporal_load(T.part_raw + m * wps + (i - base) / RT_THREADS);
+    if (threadIdx.x == 0) {
+        char *rec = T.result + m * T.rec_stride;
+        mpcd_state_result r;
+        r.cost = raw_best;
+        r.index = i;
+        r.flags = (code == 1 ? MPCD_STEP_CLIPPED : 0) | (code == 2 ? MPCD_STEP_NAN_SAMPLES : 0) |
+                  (isfinite(raw_best) ? 0 : MPCD_STEP_NONFINITE_WINNER);
+        r.reserved = 0;
+        *reinterpret_cast<mpcd_state_result *>(rec) = r;
+        double *uo = reinterpret_cast<double *>(rec + sizeof(mpcd_state_result));
+#pragma unroll
+        for (int e = 0; e < nu; ++e) uo[e] = u[e];
+    }
+    const float *wr = T.u_norm + (size_t)i * row;
+    float *plan = reinterpret_cast<float *>(T.result + T.plan_off) + (size_t)m * row;
+    float *po = T.prior_out ? T.prior_out + (size_t)m * row : nullptr;
+    for (int k = threadIdx.x; k < row; k += RT_THREADS) {
+        const int h = k / nu, e = k - h * nu;
+        float mn = S.umin[0], mx = S.umax[0];
+#pragma unroll
+        for (int q = 1; q < nu; ++q)
+            if (e == q) { mn = S.umin[q]; mx = S.umax[q]; }
+        plan[k] = unnorm1(wr[k], clip, mn, mx);
+        if (po) po[k] = wr[min(h + 1, H - 1) * nu + e];
+    }
+}
+
 __global__ __launch_bounds__(256) void repeat_rows_kernel(const float *rows, int64_t total, int64_t n, int row_len, float *out)
 {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
@@ -791,6 +903,40 @@ hipError_t launch_closed_loop_tail(const mpcd_system_desc &d, const float *umin_
     default: return hipErrorInvalidValue;
     }
 #undef MPCD_TAIL
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_step_tail(const mpcd_system_desc &d, const float *umin_host, const float *umax_host,
+                                  const BatchStepTail &t, hipStream_t stream)
+{
+    SysK S = {};
+    S.system = d.system;
+    S.cost_kind = d.cost_kind;
+    S.nx = d.n_x;
+    S.nu = d.n_u;
+    for (int i = 0; i < 24; ++i) S.params[i] = d.params[i];
+    for (int i = 0; i < 12; ++i) { S.Q[i] = d.Q[i]; S.P[i] = d.P[i]; S.xr[i] = d.x_ref[i]; }
+    for (int i = 0; i < 4; ++i) S.R[i] = d.R[i];
+    for (int i = 0; i < d.n_u; ++i) { S.umin[i] = umin_host[i]; S.umax[i] = umax_host[i]; }
+    const int64_t wgs = t.n_states * ((t.group + RT_THREADS - 1) / RT_THREADS);
+    if (t.n_states < 1 || t.group < 1 || wgs > 0x7fffffff) return hipErrorInvalidValue;
+    if (t.rec_stride != batch_step_rec_stride(d.n_u) || t.plan_off < t.n_states * t.rec_stride) return hipErrorInvalidValue;
+    const size_t lds = sizeof(float) * RT_THREADS * (t.H * d.n_u + 1);
+#define MPCD_BTAIL(SYS_)                                                                                         \
+    case SYS_:                                                                                                   \
+        if (d.n_x != SysDim<SYS_>::NX || d.n_u != SysDim<SYS_>::NU) return hipErrorInvalidValue;                 \
+        hipLaunchKernelGGL(batch_step_tail_kernel<SYS_>, dim3((unsigned)wgs), dim3(RT_THREADS), lds, stream, S, t); \
+        break;
+    switch (d.system) {
+        MPCD_BTAIL(MPCD_SYS_CARTPOLE_LIN5)
+        MPCD_BTAIL(MPCD_SYS_CARTPOLE_NL5)
+        MPCD_BTAIL(MPCD_SYS_CARTPOLE_ZOH4)
+        MPCD_BTAIL(MPCD_SYS_DOUBLE_INT2D)
+        MPCD_BTAIL(MPCD_SYS_PENDULUM)
+        MPCD_BTAIL(MPCD_SYS_QUADROTOR12)
+    default: return hipErrorInvalidValue;
+    }
+#undef MPCD_BTAIL
     return hipGetLastError();
 }
 

@@ -123,6 +123,19 @@ class ClosedLoopResult:
     u_norm: torch.Tensor = None  # [M * n, H, d] the last iteration's normalised samples (native=True only)
 
 
+@dataclass
+class BatchStepResult:
+    u: np.ndarray           # [M, n_u] fp64 applied actions (unnormalised, rounded as requested)
+    plan: np.ndarray        # [M, H, d] fp32 selected plans, unnormalised with each state's clip flag
+    cost: np.ndarray        # [M] cost of the selected candidate as computed (a NaN stays one)
+    index: np.ndarray       # [M] global index m * n + j of the selected candidate in this step's batch
+    flags: np.ndarray       # [M] int32 MPCD_STEP_CLIPPED | MPCD_STEP_NAN_SAMPLES | MPCD_STEP_NONFINITE_WINNER
+    u_norm: torch.Tensor = None  # [M * n, H, d] this step's normalised samples (return_samples=True)
+
+
+_STATE_RESULT = np.dtype([("cost", "<f8"), ("index", "<i8"), ("flags", "<i4"), ("reserved", "<i4")])
+
+
 class DiffusionMPC:
     def __init__(self, spec, params, tables=None, variance_schedule="exponential", n_diffusion_steps=100,
                  device=None, context_limits=None, action_limits=None):
@@ -673,6 +686,159 @@ class DiffusionMPC:
         del noises  # the copies above waited for the loop: its inputs may go now
         return res
 
+    def mpc_step_batch(self, x_states, system: System, n_samples, w=0.01, sample_fn="ddpm_cfg", n_wo_noise=0,
+                       ddim_steps=None, clamp_x0=False, seed=0, noise=None, select="argmin", decimals=4,
+                       clip_rule="chain", grouped=False, warm_start=None, reset=None, return_samples=False,
+                       allow_nonfinite=False):
+        """One control step for M plant states that arrive from OUTSIDE (a vectorised simulator, a plant with model
+        mismatch, a fleet of devices): ONE library call (mpcd_mpc_step_batch) - one upload of the [M, n_x] fp64
+        states, the sampler over M * n_samples candidates, one fused launch (batch_step_tail_kernel) for each state's
+        clip code, rollout, cost, selection, u0, selected plan and next prior, and one download of the packed
+        results. `system` is the PLANNING model; no plant step is taken. Given a closed_loop iteration's states and
+        its seed (seed + it) the step returns that iteration's u, cost and index bit for bit.
+        select, decimals, clip_rule, noise ([S + 1, M * n_samples, H, d], this step's): closed_loop's.
+        grouped=True: mpcd_sample_grouped on the [M, C] context rows where grouped_pays() (closed_loop's rule).
+        warm_start=K (CFG-DDPM, 1 <= K <= N): the planner keeps one normalised prior per state on the device,
+        [M, H, d], separate from mpc_step's single prior. The first such call, and any call after M changed, samples
+        cold and fills the set; later calls sample with t_start=K from it and refresh it with each state's selected
+        plan moved one horizon point ahead (mpcd_shift_plans' rule). batch_priors() returns the set,
+        set_batch_priors() replaces it, reset_warm_start() drops it.
+        reset: bool [M], the states whose episode restarted (the normal case in a vectorised simulator). Those are
+        sampled cold in a library call of their own and the others warm in theirs; priors are gathered for the two
+        calls and scattered back, results merged in state order (index and u_norm as of one M * n_samples batch).
+        Philox numbering then follows each sub-call's own batch (candidate j of the k-th reset state draws what
+        candidate k * n_samples + j of a cold call of the reset states alone draws), and injected noise is a pair
+        (noise of the cold call, noise of the warm call).
+        A state without a finite cost carries MPCD_STEP_NONFINITE_WINNER and the call raises MpcdError
+        (MPCD_ENONFINITE) unless allow_nonfinite=True, which returns the result with its flags (the other states'
+        entries are valid); either way the kept priors are dropped, so the next step is cold."""
+        K = None if warm_start is None else int(warm_start)
+        if K is not None and (K < 1 or K > self.n_steps or self._sampler_id(sample_fn) != N.MPCD_DDPM_CFG):
+            raise ValueError(f"warm_start={K} needs 1 <= K <= {self.n_steps} and the CFG-DDPM sampler")
+        if select not in ("argmin", "first"):
+            raise ValueError("select must be 'argmin' or 'first'")
+        if clip_rule not in _CLIP_RULES:
+            raise ValueError(f"clip_rule must be one of {sorted(_CLIP_RULES)}")
+        if self.spec.dtype == "f16x2":
+            raise ValueError("mpc_step_batch does not take an f16x2 spec: its range guard reads the chain maxima on "
+                             "the host and re-runs the sampler, a second round trip inside the step")
+        x = np.asarray(x_states, dtype=np.float64)
+        if x.ndim == 1:
+            x = x[None]
+        if x.ndim != 2 or x.shape[0] < 1:
+            raise ValueError(f"x_states must be [M, n_x], got {x.shape}")
+        x = np.ascontiguousarray(x)
+        M, nx = x.shape
+        if nx != system.n_x or system.n_u != self.spec.state_dim:
+            raise ValueError(f"system {system.name}: n_x={system.n_x}, n_u={system.n_u}; states have {nx} columns, "
+                             f"the net samples {self.spec.state_dim} actions")
+        if self.spec.context_dim != nx:
+            raise ValueError(f"the step conditions on the plant state: context_dim {self.spec.context_dim} != n_x {nx}")
+        n = int(n_samples)
+        if n < 1:
+            raise ValueError(f"n_samples={n} must be >= 1")
+        mask = None
+        if reset is not None:
+            mask = np.asarray(reset)
+            if mask.dtype != np.bool_ or mask.shape != (M,):
+                raise ValueError(f"reset must be a bool mask [{M}], got {mask.dtype} {mask.shape}")
+        H, d = self.spec.horizon, self.spec.state_dim
+        kw = dict(system=system, n=n, w=w, sample_fn=sample_fn, n_wo_noise=n_wo_noise, ddim_steps=ddim_steps,
+                  clamp_x0=clamp_x0, seed=seed, select=select, decimals=decimals, clip_rule=clip_rule, grouped=grouped,
+                  return_samples=return_samples)
+        priors = getattr(self, "_batch_priors", None) if K is not None else None
+        if priors is not None and priors.shape[0] != M:
+            priors = None  # the fleet changed size: a cold start
+        split = K is not None and priors is not None and mask is not None and mask.any() and not mask.all()
+        if isinstance(noise, (tuple, list)) != split:
+            raise ValueError("noise is a pair (cold call's, warm call's) exactly when `reset` names some but not all "
+                             "states of a warm step")
+        if not split:
+            warm = K is not None and priors is not None and not (mask is not None and mask.all())
+            if K is not None and not warm:
+                priors = torch.empty((M, H, d), dtype=torch.float32, device=self.device)
+            res, bad = self._batch_step_call(x, K if warm else 0, priors, noise, **kw)
+        else:
+            ic, iw = np.flatnonzero(mask), np.flatnonzero(~mask)
+            tc, tw = torch.from_numpy(ic).to(self.device), torch.from_numpy(iw).to(self.device)
+            pc = torch.empty((len(ic), H, d), dtype=torch.float32, device=self.device)
+            pw = priors.index_select(0, tw)
+            rc_, bad_c = self._batch_step_call(x[ic], 0, pc, noise[0], **kw)
+            rw_, bad_w = self._batch_step_call(x[iw], K, pw, noise[1], **kw)
+            priors.index_copy_(0, tc, pc)
+            priors.index_copy_(0, tw, pw)
+            bad = bad_c or bad_w
+            res = BatchStepResult(u=np.empty((M, d)), plan=np.empty((M, H, d), dtype=np.float32), cost=np.empty(M),
+                                  index=np.empty(M, dtype=np.int64), flags=np.empty(M, dtype=np.int32))
+            if return_samples:
+                res.u_norm = torch.empty((M * n, H, d), dtype=torch.float32, device=self.device)
+            for idx, tidx, sub in ((ic, tc, rc_), (iw, tw, rw_)):
+                res.u[idx], res.plan[idx], res.cost[idx], res.flags[idx] = sub.u, sub.plan, sub.cost, sub.flags
+                res.index[idx] = idx * n + (sub.index - np.arange(len(idx)) * n)
+                if return_samples:
+                    res.u_norm.view(M, n, H, d).index_copy_(0, tidx, sub.u_norm.view(len(idx), n, H, d))
+        if K is not None:
+            self._batch_priors = None if bad else priors
+        if bad and not allow_nonfinite:
+            N.check(N.MPCD_ENONFINITE, "mpcd_mpc_step_batch")
+        return res
+
+    def batch_priors(self):
+        """The normalised priors [M, H, d] the next mpc_step_batch(warm_start=K) starts from (device), or None."""
+        return getattr(self, "_batch_priors", None)
+
+    def set_batch_priors(self, priors):
+        """Replace mpc_step_batch's prior set: normalised plans [M, H, d] (copied to the device), or None."""
+        if priors is not None:
+            H, d = self.spec.horizon, self.spec.state_dim
+            priors = torch.as_tensor(priors, dtype=torch.float32)
+            if priors.dim() != 3 or tuple(priors.shape[1:]) != (H, d):
+                raise ValueError(f"priors must be [M, {H}, {d}], got {tuple(priors.shape)}")
+            priors = priors.to(self.device).contiguous().clone()
+        self._batch_priors = priors
+
+    def _batch_step_call(self, x, t_start, priors, noise, system, n, w, sample_fn, n_wo_noise, ddim_steps, clamp_x0,
+                         seed, select, decimals, clip_rule, grouped, return_samples):
+        """One mpcd_mpc_step_batch call on the states x [M, n_x] (checked by mpc_step_batch): (BatchStepResult, whether
+        the call returned MPCD_ENONFINITE). priors: device [M, H, d] read when t_start > 0 and refreshed, or None."""
+        x = np.ascontiguousarray(x)
+        M = x.shape[0]
+        H, d, B, dev = self.spec.horizon, self.spec.state_dim, M * n, self.device
+        sampler = self._sampler_id(sample_fn)
+        if noise is not None:
+            steps = self.n_denoise_steps(sample_fn, n_wo_noise, ddim_steps, t_start or None)
+            noise = noise.to(dev, torch.float32).contiguous()
+            if tuple(noise.shape) != (steps + 1, B, H, d):
+                raise ValueError(f"noise must be [{steps + 1}, {B}, {H}, {d}], got {tuple(noise.shape)}")
+        desc = self._system_desc(system)
+        a = N.BatchStepArgs()
+        a.sys = ctypes.pointer(desc)
+        a.ctx_min, a.ctx_max = self.ctx_min.ctypes.data, self.ctx_max.ctypes.data
+        a.act_min, a.act_max = self.act_min.ctypes.data, self.act_max.ctypes.data
+        u_norm = torch.empty((B, H, d), dtype=torch.float32, device=dev) if return_samples else None
+        a.sample = self._args(sampler, B, _STEP_CONTEXT, w, n_wo_noise, ddim_steps, clamp_x0, seed, 0, noise,
+                              self._flag, None)
+        a.sample.x_out = None  # ignored by the call: it samples into its workspace
+        a.n_states, a.group = M, n
+        a.group_contexts = 1 if bool(grouped) and self.grouped_pays(M, n, sample_fn) else 0
+        a.clip_rule = _CLIP_RULES[clip_rule]
+        a.select_first = 1 if select == "first" else 0
+        a.decimals = -1 if decimals is None else int(decimals)
+        a.warm_t_start = int(t_start)
+        rec = np.empty(M, dtype=_STATE_RESULT)
+        u = np.empty((M, d), dtype=np.float64)
+        plan = np.empty((M, H, d), dtype=np.float32)
+        a.x_host = x.ctypes.data
+        a.priors = priors.data_ptr() if priors is not None else None
+        a.result_host, a.u_host, a.plan_host = rec.ctypes.data, u.ctypes.data, plan.ctypes.data
+        a.u_norm = u_norm.data_ptr() if u_norm is not None else None
+        rc = self._lib.mpcd_mpc_step_batch(self._ctx, ctypes.byref(a), self._stream())
+        if rc != N.MPCD_ENONFINITE:
+            N.check(rc, "mpcd_mpc_step_batch")
+        res = BatchStepResult(u=u, plan=plan, cost=rec["cost"].copy(), index=rec["index"].copy(),
+                              flags=rec["flags"].copy(), u_norm=u_norm)
+        return res, rc == N.MPCD_ENONFINITE
+
     def mpc_step(self, x0, system: System, n_samples, w=0.01, sample_fn="ddpm_cfg", n_wo_noise=0, ddim_steps=None,
                  clamp_x0=False, seed=0, noise=None, group=None, comm=None, native=None, clip_rule="chain",
                  warm_start=None, prior=None):
@@ -736,8 +902,10 @@ class DiffusionMPC:
                          u_norm=u_norm)
 
     def reset_warm_start(self):
-        """Drop the prior plan mpc_step(warm_start=K) keeps: the next warm-enabled call starts cold."""
+        """Drop the prior plan mpc_step(warm_start=K) keeps and the prior set mpc_step_batch(warm_start=K) keeps: the
+        next warm-enabled call of either starts cold."""
         self._prior = self._prior_spare = None
+        self._batch_priors = None
 
     def warm_prior(self):
         """The normalised prior plan [H, d] the next mpc_step(warm_start=K) starts from (device), or None."""
