@@ -169,13 +169,13 @@ struct RolloutSelect {
 };
 constexpr int kRolloutBlock = 64;  // candidates per rollout workgroup
 
-// One closed-loop iteration's control tail (rollout.hip closed_loop_tail_kernel, mpcd_closed_loop): everything
-// after the sampler in one launch of n_states * ceil(group / kRolloutBlock) workgroups. Device pointers.
-struct ClosedLoopTail {
-    const float *u_norm;   // [n_states * group][H][n_u] this iteration's samples
+// The two control tails (rollout.hip) do everything after the sampler in one launch of n_states * ceil(group /
+// kRolloutBlock) workgroups. What both take to select each state's candidate; device pointers.
+struct TailCommon {
+    const float *u_norm;   // [n_states * group][H][n_u] this call's samples
     const float *clip_src; // chain rule: chain_absmax [n_states * group]; final rule: u_norm
     int64_t clip_per_state;  // floats of clip_src per state: group, or group * H * n_u
-    double *x_dev;         // [n_states][n_x], in and out
+    double *x_dev;         // [n_states][n_x]; the closed loop steps it in place, the batched step only reads it
     int64_t n_states, group;
     int32_t H, select_first, decimals;
     // per-workgroup partials [n_states * ceil(group / kRolloutBlock)] and one zero-initialised, self-resetting
@@ -183,6 +183,9 @@ struct ClosedLoopTail {
     double *part_cost, *part_raw;
     int64_t *part_idx;
     unsigned *counters;
+};
+// One closed-loop iteration's control tail (rollout.hip closed_loop_tail_kernel, mpcd_closed_loop)
+struct ClosedLoopTail : TailCommon {
     // this iteration's history rows
     double *x_next, *u_applied, *best_cost;  // x_hist[it + 1], u_hist[it], cost_hist[it]
     int64_t *best_idx;                       // index_hist[it]
@@ -196,20 +199,9 @@ hipError_t launch_closed_loop_tail(const mpcd_system_desc &d, const float *umin_
                                    const float *cmin_host, const float *cmax_host, const ClosedLoopTail &t,
                                    hipStream_t stream);
 // One control step of externally supplied states (rollout.hip batch_step_tail_kernel, mpcd_mpc_step_batch):
-// everything after the sampler in one launch of closed_loop_tail_kernel's grid. Device pointers. The packed result
-// block `result` is what one device-to-host copy returns: n_states records of rec_stride bytes, each
-// {mpcd_state_result, double u[n_u]}, then at plan_off the selected plans, float [n_states][H * n_u].
-struct BatchStepTail {
-    const float *u_norm;   // [n_states * group][H][n_u] this step's samples
-    const float *clip_src; // chain rule: chain_absmax [n_states * group]; final rule: u_norm
-    int64_t clip_per_state;  // floats of clip_src per state: group, or group * H * n_u
-    const double *x_dev;   // [n_states][n_x], read only
-    int64_t n_states, group;
-    int32_t H, select_first, decimals;
-    // per-workgroup partials and self-resetting per-state counters, as ClosedLoopTail's
-    double *part_cost, *part_raw;
-    int64_t *part_idx;
-    unsigned *counters;
+// the packed result block `result` is what one device-to-host copy returns: n_states records of rec_stride bytes,
+// each {mpcd_state_result, double u[n_u]}, then at plan_off the selected plans, float [n_states][H * n_u].
+struct BatchStepTail : TailCommon {
     char *result;
     int64_t rec_stride, plan_off;
     float *prior_out;      // [n_states][H][n_u] the next priors, or null

@@ -1195,6 +1195,127 @@ int mpcd_control_step(mpcd_ctx *c, const mpcd_system_desc *sys, double *x, int64
     return MPCD_OK;
 }
 
+// ---- What mpcd_closed_loop and mpcd_mpc_step_batch share. `fn` is the entry point's name in the messages.
+extern "C++" {
+namespace {
+
+struct TailCall {
+    int H, nu, nx, row;    // horizon, n_u, n_x, H * n_u
+    int64_t M, n, B, wps;  // states, candidates per state, M * n, tail workgroups per state
+    int64_t rows;          // context rows / priors the sampler takes: M grouped, B otherwise
+    bool grouped, chain_rule;
+};
+
+// The refusals after the entry point's own argument checks, and the call's sizes. `what` is the entry point's word for
+// itself ("loop" / "step"), f16_why the end of its MPCD_F16X2 sentence.
+template <class Args>
+int check_tail_call(const mpcd_ctx *c, const Args *a, const char *fn, const char *what, const char *f16_why, TailCall &g)
+{
+    if (a->clip_rule != MPCD_CLIP_CHAIN && a->clip_rule != MPCD_CLIP_FINAL)
+        return fail(MPCD_EINVAL, "%s: clip_rule %d (MPCD_CLIP_CHAIN or MPCD_CLIP_FINAL)", fn, a->clip_rule);
+    if (a->decimals > 15) return fail(MPCD_EINVAL, "decimals > 15");
+    if (!c->net_loaded) return fail(MPCD_ESTATE, "no net loaded");
+    if (!c->n_steps) return fail(MPCD_ESTATE, "no schedule set");
+    const mpcd_net_desc &d = c->desc;
+    const mpcd_system_desc &sys = *a->sys;
+    if (sys.n_u != d.state_dim) return fail(MPCD_EINVAL, "system n_u %d != net state_dim %d", sys.n_u, d.state_dim);
+    if (sys.n_x != d.context_dim)
+        return fail(MPCD_EINVAL, "the %s conditions on the plant state: n_x %d != net context_dim %d", what, sys.n_x,
+                    d.context_dim);
+    if (d.dtype == MPCD_F16X2)
+        return fail(MPCD_EUNSUP, "%s: an MPCD_F16X2 net's range guard reads the chain maxima on the host %s", fn, f16_why);
+    if (c->comm) return fail(MPCD_EUNSUP, "%s is single-rank: the context has a communicator", fn);
+    g.H = d.horizon;
+    g.nu = sys.n_u;
+    g.nx = sys.n_x;
+    g.row = g.H * g.nu;
+    int rc = check_system(&sys, g.H);
+    if (rc) return rc;
+    if ((size_t)(g.row + 1) * 64 * sizeof(float) > 64 * 1024) return fail(MPCD_EUNSUP, "H*n_u too large");
+    g.M = a->n_states;
+    g.n = a->group;
+    if (g.M > INT32_MAX || g.n > ((int64_t)1 << 40) / g.M) return fail(MPCD_EINVAL, "n_states * group too large");
+    g.B = g.M * g.n;
+    g.wps = (g.n + kRolloutBlock - 1) / kRolloutBlock;
+    if (g.M * g.wps > INT32_MAX) return fail(MPCD_EINVAL, "n_states * ceil(group / 64) workgroups exceed a grid");
+    g.grouped = a->group_contexts != 0;
+    g.chain_rule = a->clip_rule == MPCD_CLIP_CHAIN;
+    g.rows = g.grouped ? g.M : g.B;
+    return MPCD_OK;
+}
+
+// The call's sampler arguments (context, x_out and chain_absmax are set once the workspace is laid out) and the
+// warm-start refusals; priors_given: the warm start has its priors (the closed loop makes its own)
+template <class Args>
+int tail_sample_args(const mpcd_ctx *c, const Args *a, const char *fn, bool priors_given, int64_t B, mpcd_sample_args &s)
+{
+    s = a->sample;
+    s.batch = B;
+    s.context_shared = 0;
+    s.global_offset = 0;
+    s.chain_out = nullptr;
+    if (a->warm_t_start < 0 || a->warm_t_start > c->n_steps)
+        return fail(MPCD_EINVAL, "warm_t_start %d outside [0, %d]", a->warm_t_start, c->n_steps);
+    if (a->warm_t_start > 0 && !priors_given) return fail(MPCD_EINVAL, "%s: warm_t_start %d without priors", fn, a->warm_t_start);
+    if (a->warm_t_start > 0 && s.sampler != MPCD_DDPM_CFG)
+        return fail(MPCD_EUNSUP, "warm start (warm_t_start > 0) is implemented for the CFG-DDPM sampler only");
+    return MPCD_OK;
+}
+
+// A workspace laid out part by part, every part 256-byte aligned: the next part's offset
+struct Carve {
+    size_t off = 0;
+    size_t operator()(size_t bytes)
+    {
+        const size_t at = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return at;
+    }
+};
+
+// One counter per state. New counters start at zero; the tail kernels leave them there
+int grow_counters(DevBuf &cnt, int64_t M, hipStream_t st)
+{
+    if (sizeof(unsigned) * M <= cnt.bytes) return MPCD_OK;
+    int rc = cnt.ensure(sizeof(unsigned) * M);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(cnt.p, 0, cnt.bytes, st));
+    return MPCD_OK;
+}
+
+// The sampler's context rows from the states x_dev [M][n_x]: grouped, one normalised row per state; otherwise one per
+// candidate, each state's row (normalised into ctx0 [M][n_x]) repeated
+int tail_context_rows(const TailCall &g, const double *x_dev, const float *cmin, const float *cmax, float *ctx0, float *ctx,
+                      hipStream_t st)
+{
+    HIP_TRY(launch_normalize_states(x_dev, g.M, g.nx, cmin, cmax, g.grouped ? ctx : ctx0, st));
+    if (!g.grouped) HIP_TRY(launch_repeat_rows(ctx0, g.M, g.n, g.nx, ctx, st));
+    return MPCD_OK;
+}
+
+// amax: the chain maxima [B] under the chain rule, else null (the final rule tests the samples themselves)
+void fill_tail_common(TailCommon &t, const TailCall &g, const float *u_norm, const float *amax, double *x_dev,
+                      int select_first, int decimals, double *part_cost, double *part_raw, int64_t *part_idx,
+                      unsigned *counters)
+{
+    t.u_norm = u_norm;
+    t.clip_src = amax ? amax : u_norm;
+    t.clip_per_state = amax ? g.n : g.n * g.row;
+    t.x_dev = x_dev;
+    t.n_states = g.M;
+    t.group = g.n;
+    t.H = g.H;
+    t.select_first = select_first;
+    t.decimals = decimals;
+    t.part_cost = part_cost;
+    t.part_raw = part_raw;
+    t.part_idx = part_idx;
+    t.counters = counters;
+}
+
+}  // namespace
+}  // extern "C++"
+
 int mpcd_closed_loop(mpcd_ctx *c, const mpcd_closed_loop_args *a, void *stream_ptr)
 {
     if (!c || !a) return fail(MPCD_EINVAL, "null argument");
@@ -1204,114 +1325,61 @@ int mpcd_closed_loop(mpcd_ctx *c, const mpcd_closed_loop_args *a, void *stream_p
     if (a->iterations < 1 || a->group < 1 || a->n_states < 1)
         return fail(MPCD_EINVAL, "mpcd_closed_loop: iterations %d / group %lld / n_states %lld < 1", a->iterations,
                     (long long)a->group, (long long)a->n_states);
-    if (a->clip_rule != MPCD_CLIP_CHAIN && a->clip_rule != MPCD_CLIP_FINAL)
-        return fail(MPCD_EINVAL, "mpcd_closed_loop: clip_rule %d (MPCD_CLIP_CHAIN or MPCD_CLIP_FINAL)", a->clip_rule);
-    if (a->decimals > 15) return fail(MPCD_EINVAL, "decimals > 15");
-    if (!c->net_loaded) return fail(MPCD_ESTATE, "no net loaded");
-    if (!c->n_steps) return fail(MPCD_ESTATE, "no schedule set");
-    const mpcd_net_desc &d = c->desc;
-    const mpcd_system_desc &sys = *a->sys;
-    if (sys.n_u != d.state_dim) return fail(MPCD_EINVAL, "system n_u %d != net state_dim %d", sys.n_u, d.state_dim);
-    if (sys.n_x != d.context_dim)
-        return fail(MPCD_EINVAL, "the loop conditions on the plant state: n_x %d != net context_dim %d", sys.n_x,
-                    d.context_dim);
-    if (d.dtype == MPCD_F16X2)
-        return fail(MPCD_EUNSUP, "mpcd_closed_loop: an MPCD_F16X2 net's range guard reads the chain maxima on the host in "
-                                 "every iteration, the round trip this call removes");
-    if (c->comm) return fail(MPCD_EUNSUP, "mpcd_closed_loop is single-rank: the context has a communicator");
-    const int H = d.horizon, nu = sys.n_u, nx = sys.n_x;
-    int rc = check_system(&sys, H);
+    TailCall g;
+    int rc = check_tail_call(c, a, "mpcd_closed_loop", "loop", "in every iteration, the round trip this call removes", g);
     if (rc) return rc;
-    if ((size_t)(H * nu + 1) * 64 * sizeof(float) > 64 * 1024) return fail(MPCD_EUNSUP, "H*n_u too large");
-    const int64_t M = a->n_states, n = a->group;
-    if (M > INT32_MAX || n > ((int64_t)1 << 40) / M) return fail(MPCD_EINVAL, "n_states * group too large");
-    const int64_t B = M * n, wps = (n + kRolloutBlock - 1) / kRolloutBlock;
-    if (M * wps > INT32_MAX) return fail(MPCD_EINVAL, "n_states * ceil(group / 64) workgroups exceed a grid");
-    const bool grouped = a->group_contexts != 0, chain_rule = a->clip_rule == MPCD_CLIP_CHAIN;
-    const int64_t rows = grouped ? M : B;  // context rows / priors the sampler takes
-
-    mpcd_sample_args s = a->sample;
-    s.batch = B;
-    s.context_shared = 0;
-    s.global_offset = 0;
-    s.chain_out = nullptr;
-    if (a->warm_t_start < 0 || a->warm_t_start > c->n_steps)
-        return fail(MPCD_EINVAL, "warm_t_start %d outside [0, %d]", a->warm_t_start, c->n_steps);
-    if (a->warm_t_start > 0 && s.sampler != MPCD_DDPM_CFG)
-        return fail(MPCD_EUNSUP, "warm start (warm_t_start > 0) is implemented for the CFG-DDPM sampler only");
+    mpcd_sample_args s;
+    if ((rc = tail_sample_args(c, a, "mpcd_closed_loop", true, g.B, s))) return rc;
+    const int nu = g.nu, nx = g.nx;
+    const int64_t M = g.M, n = g.n, B = g.B;
     hipStream_t st = static_cast<hipStream_t>(stream_ptr);
     DEVICE_GUARD(c->device);
 
-    // workspace, every part 256-byte aligned: fp64 partials first
-    size_t off = 0;
-    auto carve = [&off](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
-    const size_t o_pc = carve(sizeof(double) * M * wps), o_pr = carve(sizeof(double) * M * wps),
-                 o_pi = carve(sizeof(int64_t) * M * wps), o_u = carve(sizeof(float) * B * H * nu),
-                 o_amax = carve(chain_rule ? sizeof(float) * B : 0), o_ctx = carve(sizeof(float) * rows * nx),
-                 o_ctx0 = carve(grouped ? 0 : sizeof(float) * M * nx),
-                 o_prior = carve(a->warm_t_start ? sizeof(float) * rows * H * nu : 0);
-    if ((rc = c->loop_ws.ensure(off))) return rc;
-    if (sizeof(unsigned) * M > c->loop_cnt.bytes) {  // new counters start at zero; the kernel leaves them there
-        if ((rc = c->loop_cnt.ensure(sizeof(unsigned) * M))) return rc;
-        HIP_TRY(hipMemsetAsync(c->loop_cnt.p, 0, c->loop_cnt.bytes, st));
-    }
+    // workspace: fp64 partials first
+    Carve carve;
+    const size_t o_pc = carve(sizeof(double) * M * g.wps), o_pr = carve(sizeof(double) * M * g.wps),
+                 o_pi = carve(sizeof(int64_t) * M * g.wps), o_u = carve(sizeof(float) * B * g.row),
+                 o_amax = carve(g.chain_rule ? sizeof(float) * B : 0), o_ctx = carve(sizeof(float) * g.rows * nx),
+                 o_ctx0 = carve(g.grouped ? 0 : sizeof(float) * M * nx),
+                 o_prior = carve(a->warm_t_start ? sizeof(float) * g.rows * g.row : 0);
+    if ((rc = c->loop_ws.ensure(carve.off))) return rc;
+    if ((rc = grow_counters(c->loop_cnt, M, st))) return rc;
     char *w = c->loop_ws.as<char>();
     float *u_norm = reinterpret_cast<float *>(w + o_u);
-    float *amax = chain_rule ? reinterpret_cast<float *>(w + o_amax) : nullptr;
+    float *amax = g.chain_rule ? reinterpret_cast<float *>(w + o_amax) : nullptr;
     float *ctx = reinterpret_cast<float *>(w + o_ctx);
     float *prior = a->warm_t_start ? reinterpret_cast<float *>(w + o_prior) : nullptr;
 
     HIP_TRY(hipMemcpyAsync(a->x_hist, a->x_dev, sizeof(double) * M * nx, hipMemcpyDeviceToDevice, st));
-    if (grouped) {
-        HIP_TRY(launch_normalize_states(a->x_dev, M, nx, a->ctx_min, a->ctx_max, ctx, st));
-    } else {  // iteration 0's per-candidate rows; the later ones are written by the tail
-        float *ctx0 = reinterpret_cast<float *>(w + o_ctx0);
-        HIP_TRY(launch_normalize_states(a->x_dev, M, nx, a->ctx_min, a->ctx_max, ctx0, st));
-        HIP_TRY(launch_repeat_rows(ctx0, M, n, nx, ctx, st));
-    }
+    // iteration 0's rows; the later ones are written by the tail
+    if ((rc = tail_context_rows(g, a->x_dev, a->ctx_min, a->ctx_max, reinterpret_cast<float *>(w + o_ctx0), ctx, st))) return rc;
     s.context = ctx;
     s.x_out = u_norm;
     s.chain_absmax = amax;
 
     ClosedLoopTail t{};
-    t.u_norm = u_norm;
-    t.clip_src = chain_rule ? amax : u_norm;
-    t.clip_per_state = chain_rule ? n : n * H * nu;
-    t.x_dev = a->x_dev;
-    t.n_states = M;
-    t.group = n;
-    t.H = H;
-    t.select_first = a->select_first;
-    t.decimals = a->decimals;
-    t.part_cost = reinterpret_cast<double *>(w + o_pc);
-    t.part_raw = reinterpret_cast<double *>(w + o_pr);
-    t.part_idx = reinterpret_cast<int64_t *>(w + o_pi);
-    t.counters = c->loop_cnt.as<unsigned>();
+    fill_tail_common(t, g, u_norm, amax, a->x_dev, a->select_first, a->decimals, reinterpret_cast<double *>(w + o_pc),
+                     reinterpret_cast<double *>(w + o_pr), reinterpret_cast<int64_t *>(w + o_pi), c->loop_cnt.as<unsigned>());
     t.ctx_out = ctx;
     t.prior_out = prior;
-    t.repeat_rows = grouped ? 0 : 1;
+    t.repeat_rows = g.grouped ? 0 : 1;
     WarmArgs warm;
     if (a->warm_t_start) {
-        const mpcd_warm_start ws{prior, rows, a->warm_t_start};
-        if ((rc = resolve_warm(c, &s, grouped ? n : 0, &ws, warm))) return rc;
+        const mpcd_warm_start ws{prior, g.rows, a->warm_t_start};
+        if ((rc = resolve_warm(c, &s, g.grouped ? n : 0, &ws, warm))) return rc;
     }
     for (int32_t it = 0; it < a->iterations; ++it) {
         s.seed = a->sample.seed + (uint64_t)it;
         s.noise = a->noise_iters ? a->noise_iters[it] : nullptr;
-        rc = sample_impl(c, &s, stream_ptr, nullptr, grouped ? n : 0, a->warm_t_start && it > 0 ? &warm : nullptr);
+        rc = sample_impl(c, &s, stream_ptr, nullptr, g.grouped ? n : 0, a->warm_t_start && it > 0 ? &warm : nullptr);
         if (rc) return rc;
         t.x_next = a->x_hist + (size_t)(it + 1) * M * nx;
         t.u_applied = a->u_hist + (size_t)it * M * nu;
         t.best_cost = a->cost_hist + (size_t)it * M;
         t.best_idx = a->index_hist + (size_t)it * M;
-        HIP_TRY(launch_closed_loop_tail(sys, a->act_min, a->act_max, a->ctx_min, a->ctx_max, t, st));
+        HIP_TRY(launch_closed_loop_tail(*a->sys, a->act_min, a->act_max, a->ctx_min, a->ctx_max, t, st));
     }
-    if (a->u_norm)
-        HIP_TRY(hipMemcpyAsync(a->u_norm, u_norm, sizeof(float) * B * H * nu, hipMemcpyDeviceToDevice, st));
+    if (a->u_norm) HIP_TRY(hipMemcpyAsync(a->u_norm, u_norm, sizeof(float) * B * g.row, hipMemcpyDeviceToDevice, st));
     return MPCD_OK;
 }
 
@@ -1323,69 +1391,31 @@ int mpcd_mpc_step_batch(mpcd_ctx *c, const mpcd_batch_step_args *a, void *stream
     if (a->n_states < 1 || a->group < 1)
         return fail(MPCD_EINVAL, "mpcd_mpc_step_batch: n_states %lld / group %lld < 1", (long long)a->n_states,
                     (long long)a->group);
-    if (a->clip_rule != MPCD_CLIP_CHAIN && a->clip_rule != MPCD_CLIP_FINAL)
-        return fail(MPCD_EINVAL, "mpcd_mpc_step_batch: clip_rule %d (MPCD_CLIP_CHAIN or MPCD_CLIP_FINAL)", a->clip_rule);
-    if (a->decimals > 15) return fail(MPCD_EINVAL, "decimals > 15");
-    if (!c->net_loaded) return fail(MPCD_ESTATE, "no net loaded");
-    if (!c->n_steps) return fail(MPCD_ESTATE, "no schedule set");
-    const mpcd_net_desc &d = c->desc;
-    const mpcd_system_desc &sys = *a->sys;
-    if (sys.n_u != d.state_dim) return fail(MPCD_EINVAL, "system n_u %d != net state_dim %d", sys.n_u, d.state_dim);
-    if (sys.n_x != d.context_dim)
-        return fail(MPCD_EINVAL, "the step conditions on the plant state: n_x %d != net context_dim %d", sys.n_x,
-                    d.context_dim);
-    if (d.dtype == MPCD_F16X2)
-        return fail(MPCD_EUNSUP, "mpcd_mpc_step_batch: an MPCD_F16X2 net's range guard reads the chain maxima on the host "
-                                 "and re-runs the sampler, a second round trip inside the step");
-    if (c->comm) return fail(MPCD_EUNSUP, "mpcd_mpc_step_batch is single-rank: the context has a communicator");
-    const int H = d.horizon, nu = sys.n_u, nx = sys.n_x;
-    int rc = check_system(&sys, H);
+    TailCall g;
+    int rc = check_tail_call(c, a, "mpcd_mpc_step_batch", "step",
+                             "and re-runs the sampler, a second round trip inside the step", g);
     if (rc) return rc;
-    if ((size_t)(H * nu + 1) * 64 * sizeof(float) > 64 * 1024) return fail(MPCD_EUNSUP, "H*n_u too large");
-    const int64_t M = a->n_states, n = a->group;
-    if (M > INT32_MAX || n > ((int64_t)1 << 40) / M) return fail(MPCD_EINVAL, "n_states * group too large");
-    const int64_t B = M * n, wps = (n + kRolloutBlock - 1) / kRolloutBlock;
-    if (M * wps > INT32_MAX) return fail(MPCD_EINVAL, "n_states * ceil(group / 64) workgroups exceed a grid");
-    const bool grouped = a->group_contexts != 0, chain_rule = a->clip_rule == MPCD_CLIP_CHAIN;
-    const int64_t rows = grouped ? M : B;  // context rows / priors the sampler takes
-    const int row = H * nu;
-
-    mpcd_sample_args s = a->sample;
-    s.batch = B;
-    s.context_shared = 0;
-    s.global_offset = 0;
-    s.chain_out = nullptr;
-    if (a->warm_t_start < 0 || a->warm_t_start > c->n_steps)
-        return fail(MPCD_EINVAL, "warm_t_start %d outside [0, %d]", a->warm_t_start, c->n_steps);
-    if (a->warm_t_start > 0 && !a->priors)
-        return fail(MPCD_EINVAL, "mpcd_mpc_step_batch: warm_t_start %d without priors", a->warm_t_start);
-    if (a->warm_t_start > 0 && s.sampler != MPCD_DDPM_CFG)
-        return fail(MPCD_EUNSUP, "warm start (warm_t_start > 0) is implemented for the CFG-DDPM sampler only");
+    mpcd_sample_args s;
+    if ((rc = tail_sample_args(c, a, "mpcd_mpc_step_batch", a->priors != nullptr, g.B, s))) return rc;
+    const int nu = g.nu, nx = g.nx, row = g.row;
+    const int64_t M = g.M, n = g.n, B = g.B;
     hipStream_t st = static_cast<hipStream_t>(stream_ptr);
     DEVICE_GUARD(c->device);
 
-    // workspace, every part 256-byte aligned: fp64 parts first. The packed result block (BatchStepTail): M records
-    // {mpcd_state_result, u[n_u]}, then the selected plans
-    size_t off = 0;
-    auto carve = [&off](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
+    // workspace: fp64 parts first. The packed result block (BatchStepTail): M records {mpcd_state_result, u[n_u]},
+    // then the selected plans
+    Carve carve;
     const int64_t rec_stride = batch_step_rec_stride(nu);
     const size_t plan_off = ((size_t)(M * rec_stride) + 255) & ~(size_t)255;
     const size_t res_bytes = plan_off + sizeof(float) * M * row, x_bytes = sizeof(double) * M * nx;
-    const bool repeat_priors = a->warm_t_start > 0 && !grouped;
-    const size_t o_x = carve(x_bytes), o_pc = carve(sizeof(double) * M * wps), o_pr = carve(sizeof(double) * M * wps),
-                 o_pi = carve(sizeof(int64_t) * M * wps), o_res = carve(res_bytes), o_u = carve(sizeof(float) * B * row),
-                 o_amax = carve(chain_rule ? sizeof(float) * B : 0), o_ctx = carve(sizeof(float) * rows * nx),
-                 o_ctx0 = carve(grouped ? 0 : sizeof(float) * M * nx),
+    const bool repeat_priors = a->warm_t_start > 0 && !g.grouped;
+    const size_t o_x = carve(x_bytes), o_pc = carve(sizeof(double) * M * g.wps), o_pr = carve(sizeof(double) * M * g.wps),
+                 o_pi = carve(sizeof(int64_t) * M * g.wps), o_res = carve(res_bytes), o_u = carve(sizeof(float) * B * row),
+                 o_amax = carve(g.chain_rule ? sizeof(float) * B : 0), o_ctx = carve(sizeof(float) * g.rows * nx),
+                 o_ctx0 = carve(g.grouped ? 0 : sizeof(float) * M * nx),
                  o_prior = carve(repeat_priors ? sizeof(float) * B * row : 0);
-    if ((rc = c->batch_ws.ensure(off))) return rc;
-    if (sizeof(unsigned) * M > c->batch_cnt.bytes) {  // new counters start at zero; the kernel leaves them there
-        if ((rc = c->batch_cnt.ensure(sizeof(unsigned) * M))) return rc;
-        HIP_TRY(hipMemsetAsync(c->batch_cnt.p, 0, c->batch_cnt.bytes, st));
-    }
+    if ((rc = c->batch_ws.ensure(carve.off))) return rc;
+    if ((rc = grow_counters(c->batch_cnt, M, st))) return rc;
     const size_t h_res = (x_bytes + 255) & ~(size_t)255, host_bytes = h_res + res_bytes;
     if (c->batch_host_bytes < host_bytes) {  // the previous call ended in a stream synchronisation: nothing reads it
         if (c->batch_host) (void)hipHostFree(c->batch_host);
@@ -1397,18 +1427,12 @@ int mpcd_mpc_step_batch(mpcd_ctx *c, const mpcd_batch_step_args *a, void *stream
     char *w = c->batch_ws.as<char>(), *hs = static_cast<char *>(c->batch_host);
     double *x_dev = reinterpret_cast<double *>(w + o_x);
     float *u_norm = reinterpret_cast<float *>(w + o_u);
-    float *amax = chain_rule ? reinterpret_cast<float *>(w + o_amax) : nullptr;
+    float *amax = g.chain_rule ? reinterpret_cast<float *>(w + o_amax) : nullptr;
     float *ctx = reinterpret_cast<float *>(w + o_ctx);
 
     memcpy(hs, a->x_host, x_bytes);
     HIP_TRY(hipMemcpyAsync(x_dev, hs, x_bytes, hipMemcpyHostToDevice, st));
-    if (grouped) {
-        HIP_TRY(launch_normalize_states(x_dev, M, nx, a->ctx_min, a->ctx_max, ctx, st));
-    } else {  // one row per candidate, each state's repeated
-        float *ctx0 = reinterpret_cast<float *>(w + o_ctx0);
-        HIP_TRY(launch_normalize_states(x_dev, M, nx, a->ctx_min, a->ctx_max, ctx0, st));
-        HIP_TRY(launch_repeat_rows(ctx0, M, n, nx, ctx, st));
-    }
+    if ((rc = tail_context_rows(g, x_dev, a->ctx_min, a->ctx_max, reinterpret_cast<float *>(w + o_ctx0), ctx, st))) return rc;
     s.context = ctx;
     s.x_out = u_norm;
     s.chain_absmax = amax;
@@ -1420,31 +1444,20 @@ int mpcd_mpc_step_batch(mpcd_ctx *c, const mpcd_batch_step_args *a, void *stream
             HIP_TRY(launch_repeat_rows(a->priors, M, n, row, rep, st));
             prior = rep;
         }
-        const mpcd_warm_start ws{prior, rows, a->warm_t_start};
-        if ((rc = resolve_warm(c, &s, grouped ? n : 0, &ws, warm))) return rc;
+        const mpcd_warm_start ws{prior, g.rows, a->warm_t_start};
+        if ((rc = resolve_warm(c, &s, g.grouped ? n : 0, &ws, warm))) return rc;
     }
-    rc = sample_impl(c, &s, stream_ptr, nullptr, grouped ? n : 0, a->warm_t_start ? &warm : nullptr);
+    rc = sample_impl(c, &s, stream_ptr, nullptr, g.grouped ? n : 0, a->warm_t_start ? &warm : nullptr);
     if (rc) return rc;
 
     BatchStepTail t{};
-    t.u_norm = u_norm;
-    t.clip_src = chain_rule ? amax : u_norm;
-    t.clip_per_state = chain_rule ? n : n * row;
-    t.x_dev = x_dev;
-    t.n_states = M;
-    t.group = n;
-    t.H = H;
-    t.select_first = a->select_first;
-    t.decimals = a->decimals;
-    t.part_cost = reinterpret_cast<double *>(w + o_pc);
-    t.part_raw = reinterpret_cast<double *>(w + o_pr);
-    t.part_idx = reinterpret_cast<int64_t *>(w + o_pi);
-    t.counters = c->batch_cnt.as<unsigned>();
+    fill_tail_common(t, g, u_norm, amax, x_dev, a->select_first, a->decimals, reinterpret_cast<double *>(w + o_pc),
+                     reinterpret_cast<double *>(w + o_pr), reinterpret_cast<int64_t *>(w + o_pi), c->batch_cnt.as<unsigned>());
     t.result = w + o_res;
     t.rec_stride = rec_stride;
     t.plan_off = (int64_t)plan_off;
     t.prior_out = a->priors;
-    HIP_TRY(launch_batch_step_tail(sys, a->act_min, a->act_max, t, st));
+    HIP_TRY(launch_batch_step_tail(*a->sys, a->act_min, a->act_max, t, st));
     if (a->u_norm) HIP_TRY(hipMemcpyAsync(a->u_norm, u_norm, sizeof(float) * B * row, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(hs + h_res, w + o_res, res_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));

@@ -10,6 +10,7 @@
 #include <math.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "../../include/mpcd.h"
 #include "internal.h"
@@ -205,6 +206,18 @@ __device__ __forceinline__ float unnorm1(float v, bool clip, float mn, float mx)
     return h * (mx - mn) + mn;
 }
 
+// One component of the applied action: unnormalised in fp32, promoted to double and rounded to `decimals` places
+// (the reference's round(u, 4) on the fp32 value; < 0: none)
+__device__ __forceinline__ double rounded_action(float v, bool clip, float mn, float mx, int decimals)
+{
+    double o = (double)unnorm1(v, clip, mn, mx);
+    if (decimals >= 0) {
+        const double sc = pow(10.0, (double)decimals);
+        o = rint(o * sc) / sc;
+    }
+    return o;
+}
+
 __global__ void unnormalize_kernel(const float *x, int64_t n, int dim, const int *flag, const MinMax lim, float *out)
 {
     const bool clip = *flag == 1;
@@ -214,21 +227,14 @@ __global__ void unnormalize_kernel(const float *x, int64_t n, int dim, const int
     }
 }
 
-// x0_dev == nullptr: every candidate starts from S.x0; else candidate b starts from x0_dev[b / group]
-// (closed loop: one plant state per group of candidates). flags[b / group] is that group's clip flag
-// (group = batch for the single-state case: one global flag).
-// SEL: also select (SelectK above) - one launch for rollout, cost, argmin and the winner's row.
-template <int SYS, bool SEL>
-__global__ __launch_bounds__(RT_THREADS) void rollout_cost_kernel(const SysK S, const float *u_norm, const int *flags,
-                                                                  const double *x0_dev, int64_t group, int64_t batch,
-                                                                  int H, double *cost, const SelectK K)
+// ---- What the rollout kernel and the two control tails share: a workgroup's row staging, a candidate's cost, a
+// state's clip code and the cross-workgroup argmin. Each exists once, so a candidate's cost, a clip decision and a
+// tie are the same bits whichever kernel computes them.
+
+// nvalid candidates' contiguous [row] floats at src -> su[c][row + 1]
+__device__ __forceinline__ void stage_rows(const float *src, int64_t nvalid, int row, float *su)
 {
-    constexpr int nx = SysDim<SYS>::NX, nu = SysDim<SYS>::NU;
-    extern __shared__ float su[];  // [RT_THREADS][H*nu + 1]
-    const int row = H * nu, stride = row + 1;
-    const int64_t c0 = (int64_t)blockIdx.x * RT_THREADS;
-    const int64_t nvalid = min((int64_t)RT_THREADS, batch - c0);
-    const float *src = u_norm + (size_t)c0 * row;
+    const int stride = row + 1;
     if ((row & 3) == 0) {  // 16-byte loads (a row never straddles a quad)
         // in batches of UNR loads per lane, all issued before the first LDS store: one memory latency per batch
         // (a load -> store loop waits for every load in turn: 16 latencies at H = 32, nu = 2)
@@ -257,37 +263,18 @@ __global__ __launch_bounds__(RT_THREADS) void rollout_cost_kernel(const SysK S, 
             su[c * stride + k] = src[i];
         }
     }
-    int code = 0;  // SEL with clip_src: the clip code, recomputed by every workgroup (clip_flag_kernel's test)
-    if constexpr (SEL) {
-        if (K.clip_src) {
-            const float hi = (float)(1.0 + 1e-4), lo = (float)(-1.0 - 1e-4);
-            unsigned any = 0;
-            const int64_t n4 = ((uintptr_t)K.clip_src & 15) ? 0 : K.clip_n >> 2;
-#pragma unroll 8
-            for (int64_t i = threadIdx.x; i < n4; i += RT_THREADS) {  // unrolled: eight loads in flight per lane
-                const f32x4 v = ldg4(K.clip_src + 4 * i);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) any |= clip_bits(v[e], hi, lo);
-            }
-            for (int64_t i = 4 * n4 + threadIdx.x; i < K.clip_n; i += RT_THREADS) any |= clip_bits(K.clip_src[i], hi, lo);
-            __shared__ unsigned blk;
-            if (threadIdx.x == 0) blk = 0;
-            __syncthreads();
-            if (any) atomicOr(&blk, any);
-            __syncthreads();
-            code = clip_code(blk);
-        }
-    }
-    __syncthreads();
-    const int64_t b = min(c0 + threadIdx.x, batch - 1);  // lanes past the batch recompute the last one
-    const bool clip = (SEL && K.clip_src) ? code == 1 : flags[b / group] == 1;
+}
+
+// The MPC cost of the normalised plan ur[H][nu] from the state x (overwritten), both cost kinds. The fp64 operations
+// and their order are the contract with the C oracle (-ffp-contract=off: no contraction changes a rounding).
+template <int SYS>
+__device__ __forceinline__ double candidate_cost(const SysK &S, const float *ur, bool clip, double *x, int H)
+{
+    constexpr int nx = SysDim<SYS>::NX, nu = SysDim<SYS>::NU;
     float mn[nu], mx[nu];
 #pragma unroll
     for (int i = 0; i < nu; ++i) { mn[i] = S.umin[i]; mx[i] = S.umax[i]; }
-    const float *ur = su + (b - c0) * stride;
-    double x[nx], xn[nx], u[nu];
-#pragma unroll
-    for (int i = 0; i < nx; ++i) x[i] = x0_dev ? x0_dev[(b / group) * nx + i] : S.x0[i];
+    double xn[nx], u[nu];
     double J;
     if (S.cost_kind == MPCD_COST_CALMPC) {
         // calMPCCost (Cart_Diffusion_inference.py:247-283); num_u = 1 (batch axis of u_hor)
@@ -318,35 +305,105 @@ __global__ __launch_bounds__(RT_THREADS) void rollout_cost_kernel(const SysK S, 
             for (int j = 0; j < nx; ++j) x[j] = xn[j];
         }
     }
+    return J;
+}
+
+// clip_flag_kernel's test over cs[0, n) by one wave (a one-wave workgroup): the clip code of a state's slice, or of
+// the whole batch
+__device__ __forceinline__ int state_clip_code(const float *cs, int64_t n)
+{
+    const float hi = (float)(1.0 + 1e-4), lo = (float)(-1.0 - 1e-4);
+    unsigned any = 0;
+    const int64_t n4 = ((uintptr_t)cs & 15) ? 0 : n >> 2;
+#pragma unroll 8
+    for (int64_t i = threadIdx.x; i < n4; i += RT_THREADS) {  // unrolled: eight loads in flight per lane
+        const f32x4 v = ldg4(cs + 4 * i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) any |= clip_bits(v[e], hi, lo);
+    }
+    for (int64_t i = 4 * n4 + threadIdx.x; i < n; i += RT_THREADS) any |= clip_bits(cs[i], hi, lo);
+    __shared__ unsigned blk;
+    if (threadIdx.x == 0) blk = 0;
+    __syncthreads();
+    if (any) atomicOr(&blk, any);
+    __syncthreads();
+    return clip_code(blk);
+}
+
+// Cross-workgroup argmin: workgroup `slot` of `nslots` (one wave each) leaves its partial (v, i) - and raw, where
+// part_raw is not null - in part_*[slot] and counts itself on *counter; the last one to arrive reduces the nslots
+// partials. Returns whether this workgroup is that last one; if so (v, i) is the reduced winner in every lane
+// (i < 0: no entrant). *counter is zero between launches: the last workgroup puts it back.
+// Why it is sound: lane 0 stores the partials, __threadfence() makes them visible device-wide, and only then does its
+// atomicAdd count the workgroup. The workgroup whose add returns nslots - 1 therefore follows every other workgroup's
+// stores and fence; its own __threadfence() and the non-temporal reloads (which take no stale line of this CU's
+// cache) then read all nslots partials as written. The same order covers what a caller's partial depends on: a
+// partial is computed from the state the workgroup read (the tails' x_dev[m]), so every workgroup has finished
+// reading it before it counts itself, and the last workgroup may overwrite it (the closed loop's plant step).
+__device__ __forceinline__ bool last_arriver_argmin(double *part_cost, int64_t *part_idx, double *part_raw,
+                                                    unsigned *counter, int slot, int nslots, double &v, int64_t &i,
+                                                    double raw)
+{
+    __shared__ bool last;
+    if (threadIdx.x == 0) {
+        part_cost[slot] = v;
+        part_idx[slot] = i;
+        if (part_raw) part_raw[slot] = raw;
+        __threadfence();
+        last = atomicAdd(counter, 1u) == (unsigned)nslots - 1;
+    }
+    __syncthreads();
+    if (!last) return false;
+    __threadfence();
+    v = INFINITY;
+    i = -1;
+    for (int k = threadIdx.x; k < nslots; k += RT_THREADS) {
+        const double pv = __builtin_nontemporal_load(part_cost + k);
+        const int64_t pi = __builtin_nontemporal_load(part_idx + k);
+        if (better(pv, pi, v, i)) { v = pv; i = pi; }
+    }
+    wave_argmin(v, i);
+    if (threadIdx.x == 0) *counter = 0u;
+    return true;
+}
+
+// x0_dev == nullptr: every candidate starts from S.x0; else candidate b starts from x0_dev[b / group]
+// (closed loop: one plant state per group of candidates). flags[b / group] is that group's clip flag
+// (group = batch for the single-state case: one global flag).
+// SEL: also select (SelectK above) - one launch for rollout, cost, argmin and the winner's row.
+template <int SYS, bool SEL>
+__global__ __launch_bounds__(RT_THREADS) void rollout_cost_kernel(const SysK S, const float *u_norm, const int *flags,
+                                                                  const double *x0_dev, int64_t group, int64_t batch,
+                                                                  int H, double *cost, const SelectK K)
+{
+    constexpr int nx = SysDim<SYS>::NX, nu = SysDim<SYS>::NU;
+    extern __shared__ float su[];  // [RT_THREADS][H*nu + 1]
+    const int row = H * nu, stride = row + 1;
+    const int64_t c0 = (int64_t)blockIdx.x * RT_THREADS;
+    stage_rows(u_norm + (size_t)c0 * row, min((int64_t)RT_THREADS, batch - c0), row, su);
+    int code = 0;  // SEL with clip_src: the clip code, recomputed by every workgroup
+    if constexpr (SEL) {
+        if (K.clip_src) code = state_clip_code(K.clip_src, K.clip_n);
+    }
+    __syncthreads();
+    const int64_t b = min(c0 + threadIdx.x, batch - 1);  // lanes past the batch recompute the last one
+    const bool clip = (SEL && K.clip_src) ? code == 1 : flags[b / group] == 1;
+    double x[nx];
+#pragma unroll
+    for (int i = 0; i < nx; ++i) x[i] = x0_dev ? x0_dev[(b / group) * nx + i] : S.x0[i];
+    const double J = candidate_cost<SYS>(S, su + (b - c0) * stride, clip, x, H);
     if (c0 + threadIdx.x < batch) cost[b] = J;
     if constexpr (SEL) {
         double v = isnan(J) ? INFINITY : J;
         int64_t i = c0 + threadIdx.x < batch ? b : -1;
         wave_argmin(v, i);  // RT_THREADS == one wave
-        __shared__ bool last;
-        if (threadIdx.x == 0) {
-            K.part_cost[blockIdx.x] = v;
-            K.part_idx[blockIdx.x] = i;
-            __threadfence();
-            last = atomicAdd(K.counter, 1u) == gridDim.x - 1;
-        }
-        __syncthreads();
-        if (!last) return;
-        __threadfence();
-        v = INFINITY;
-        i = -1;
-        for (int k = threadIdx.x; k < (int)gridDim.x; k += RT_THREADS) {
-            const double pv = __builtin_nontemporal_load(K.part_cost + k);
-            const int64_t pi = __builtin_nontemporal_load(K.part_idx + k);
-            if (better(pv, pi, v, i)) { v = pv; i = pi; }
-        }
-        wave_argmin(v, i);
+        if (!last_arriver_argmin(K.part_cost, K.part_idx, nullptr, K.counter, (int)blockIdx.x, (int)gridDim.x, v, i, 0.0))
+            return;
         const int32_t ccode = K.clip_src ? code : flags[0];
         float *hrow = K.host_out ? reinterpret_cast<float *>(K.host_out + sizeof(mpcd_best)) : nullptr;
         if (threadIdx.x == 0) {
             const mpcd_best bst{v, i < 0 ? -1 : K.offset + i};
             *K.best = bst;
-            *K.counter = 0u;
             if (K.code_out) *K.code_out = ccode;
             if (hrow) {
                 *reinterpret_cast<mpcd_best *>(K.host_out) = bst;
@@ -455,14 +512,8 @@ __global__ __launch_bounds__(CS_THREADS) void control_step_kernel(const SysK S, 
 #pragma unroll
     for (int i = 0; i < nx; ++i) x[i] = x_dev[m * nx + i];
 #pragma unroll
-    for (int i = 0; i < nu; ++i) {
-        double v = (double)unnorm1(u_norm[(size_t)idx * H * nu + i], clip, S.umin[i], S.umax[i]);
-        if (decimals >= 0) {
-            const double sc = pow(10.0, (double)decimals);
-            v = rint(v * sc) / sc;
-        }
-        u[i] = v;
-    }
+    for (int i = 0; i < nu; ++i)
+        u[i] = rounded_action(u_norm[(size_t)idx * H * nu + i], clip, S.umin[i], S.umax[i], decimals);
     dyn_step<SYS>(S, x, u, xn);
 #pragma unroll
     for (int i = 0; i < nx; ++i) x_dev[m * nx + i] = xn[i];
@@ -535,98 +586,24 @@ __global__ __launch_bounds__(256) void shift_plan_kernel(const float *rows, int6
     }
 }
 
-// ---- The closed loop's control tail (mpcd_closed_loop): per iteration, everything after the sampler in one launch.
-// The two helpers restate rollout_cost_kernel's staging and per-candidate cost expression by expression (same fp64
-// operations in the same order, -ffp-contract=off), so a candidate's cost is bit for bit that kernel's.
-
-// nvalid candidates' contiguous [row] floats at src -> su[c][row + 1]
-__device__ __forceinline__ void stage_rows(const float *src, int64_t nvalid, int row, float *su)
-{
-    const int stride = row + 1;
-    if ((row & 3) == 0) {  // 16-byte loads, UNR per lane in flight before the first LDS store (as rollout_cost_kernel)
-        constexpr int UNR = 8;
-        const int nq = (int)(nvalid * row / 4);
-        for (int base = 0; base < nq; base += UNR * RT_THREADS) {
-            f32x4 v[UNR];
-#pragma unroll
-            for (int u = 0; u < UNR; ++u) {
-                const int i = base + u * RT_THREADS + (int)threadIdx.x;
-                v[u] = i < nq ? ldg4(src + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-#pragma unroll
-            for (int u = 0; u < UNR; ++u) {
-                const int i = base + u * RT_THREADS + (int)threadIdx.x;
-                if (i < nq) {
-                    const int c = 4 * i / row, k = 4 * i - c * row;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) su[c * stride + k + e] = v[u][e];
-                }
-            }
-        }
-    } else {
-        for (int i = threadIdx.x; i < nvalid * row; i += RT_THREADS) {
-            const int c = i / row, k = i - c * row;
-            su[c * stride + k] = src[i];
-        }
-    }
-}
-
-// The MPC cost of the normalised plan ur[H][nu] from the state x (overwritten), both cost kinds
-template <int SYS>
-__device__ __forceinline__ double candidate_cost(const SysK &S, const float *ur, bool clip, double *x, int H)
-{
-    constexpr int nx = SysDim<SYS>::NX, nu = SysDim<SYS>::NU;
-    float mn[nu], mx[nu];
-#pragma unroll
-    for (int i = 0; i < nu; ++i) { mn[i] = S.umin[i]; mx[i] = S.umax[i]; }
-    double xn[nx], u[nu];
-    double J;
-    if (S.cost_kind == MPCD_COST_CALMPC) {
-        J = 0.0;
-        for (int i = 0; i < nx; ++i) J = J + S.Q[i] * (x[i] * x[i]);
-        u[0] = (double)unnorm1(ur[0], clip, mn[0], mx[0]);
-        J = J + S.R[0] * (u[0] * u[0]);
-        for (int i = 0; i < nx; ++i) xn[i] = x[i];
-        double ucur = u[0];
-        for (int i = 1; i < H - 1; ++i) {
-            dyn_step<SYS>(S, x, &ucur, xn);
-            const double un = (double)unnorm1(ur[i * nu], clip, mn[0], mx[0]);
-            for (int j = 1; j < nx; ++j) J = J + S.Q[j] * (xn[j] * xn[j]);
-            J = J + S.R[0] * (un * un);
-            ucur = un;
-            for (int j = 0; j < nx; ++j) x[j] = xn[j];
-        }
-        for (int i = 0; i < nx; ++i) J = J + S.P[i] * (xn[i] * xn[i]);
-    } else {
-        const double zero[4] = {0.0, 0.0, 0.0, 0.0};
-        J = quadform<nx>(S.Q, x, S.xr);
-        for (int k = 0; k < H; ++k) {
-            for (int i = 0; i < nu; ++i) u[i] = (double)unnorm1(ur[k * nu + i], clip, mn[i], mx[i]);
-            dyn_step<SYS>(S, x, u, xn);
-            const double sx = k < H - 1 ? quadform<nx>(S.Q, xn, S.xr) : quadform<nx>(S.P, xn, S.xr);
-            const double sv = quadform<nu>(S.R, u, zero);
-            J = J + (sx + sv);
-            for (int j = 0; j < nx; ++j) x[j] = xn[j];
-        }
-    }
-    return J;
-}
+// ---- The control tails: per call, everything after the sampler in one launch (mpcd_closed_loop's iteration,
+// mpcd_mpc_step_batch's step). Grid: n_states * wps workgroups, wps = ceil(group / RT_THREADS); workgroup (m, j) owns
+// candidates [m * group + j * RT_THREADS, ...) of plant state m. Per state, every workgroup computes the state's clip
+// code (state_clip_code over the state's slice of clip_src), rolls out and costs its candidates from x_dev[m]
+// (stage_rows, candidate_cost) and enters its best one (select_first: the only entrant is the group's first
+// candidate); the state's last workgroup to arrive (last_arriver_argmin on counters[m]) holds the winner and writes the
+// state's results. The two kernels spell this front half out with the same calls in the same order: moved into one
+// __device__ function it compiles to other register figures (batch_step_tail_kernel<3> from 97 to 106 SGPRs and from
+// 8 to 7 waves per SIMD), so the shared pieces are the helpers it calls.
 
 // NormK's constants before their (exact) promotion to fp64: half the kernel-argument registers
 struct NormF {
     float mn[12], den[12];
 };
 
-// Grid: n_states * wps workgroups, wps = ceil(group / RT_THREADS); workgroup (m, j) owns candidates
-// [m * group + j * RT_THREADS, ...) of plant state m. Per state:
-//  - every workgroup recomputes the state's clip code (clip_flags_kernel's test over the state's slice of clip_src),
-//    rolls out and costs its candidates from x_dev[m] (rollout_cost_kernel's expressions) and leaves its argmin
-//    partial; select_first: the only entrant is the group's first candidate;
-//  - the last workgroup to arrive (counters[m], reset by it; rollout_cost_kernel<SYS, true>'s counter / fence /
-//    better() protocol) reduces the state's partials, takes control_step_kernel's plant step x_dev[m] <- f(x_dev[m],
-//    u0) - every other workgroup of the state has read x_dev[m] by then: its partial depends on it - and writes the
-//    history rows, the next context row (normalize_states_kernel's formula) and the next prior (shift_plan_kernel's
-//    rule on the winner's normalised plan), one row per state or one per candidate (repeat_rows).
+// The closed loop's tail: the state's last workgroup takes control_step_kernel's plant step x_dev[m] <- f(x_dev[m],
+// u0) and writes the history rows, the next context row (normalize_states_kernel's formula) and the next prior
+// (shift_plan_kernel's rule on the winner's normalised plan), one row per state or one per candidate (repeat_rows).
 template <int SYS>
 __global__ __launch_bounds__(RT_THREADS) void closed_loop_tail_kernel(const SysK S, const NormF nk, const ClosedLoopTail T)
 {
@@ -639,26 +616,7 @@ __global__ __launch_bounds__(RT_THREADS) void closed_loop_tail_kernel(const SysK
     const int64_t base = m * T.group, end = base + T.group;
     const int64_t c0 = base + (int64_t)j * RT_THREADS;
     stage_rows(T.u_norm + (size_t)c0 * row, min((int64_t)RT_THREADS, end - c0), row, su);
-    int code;
-    {
-        const float hi = (float)(1.0 + 1e-4), lo = (float)(-1.0 - 1e-4);
-        const float *cs = T.clip_src + (size_t)m * T.clip_per_state;
-        unsigned any = 0;
-        const int64_t n4 = ((uintptr_t)cs & 15) ? 0 : T.clip_per_state >> 2;
-#pragma unroll 8
-        for (int64_t i = threadIdx.x; i < n4; i += RT_THREADS) {
-            const f32x4 v = ldg4(cs + 4 * i);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) any |= clip_bits(v[e], hi, lo);
-        }
-        for (int64_t i = 4 * n4 + threadIdx.x; i < T.clip_per_state; i += RT_THREADS) any |= clip_bits(cs[i], hi, lo);
-        __shared__ unsigned blk;
-        if (threadIdx.x == 0) blk = 0;
-        __syncthreads();
-        if (any) atomicOr(&blk, any);
-        __syncthreads();
-        code = clip_code(blk);
-    }
+    const int code = state_clip_code(T.clip_src + (size_t)m * T.clip_per_state, T.clip_per_state);
     __syncthreads();
     const bool clip = code == 1;
     const int64_t b = min(c0 + threadIdx.x, end - 1);  // lanes past the group recompute its last candidate
@@ -670,27 +628,9 @@ __global__ __launch_bounds__(RT_THREADS) void closed_loop_tail_kernel(const SysK
     int64_t i = c0 + threadIdx.x < end && (!T.select_first || b == base) ? b : -1;
     wave_argmin(v, i);  // RT_THREADS == one wave; every lane holds the result
     const double raw = __shfl(J, i >= 0 ? (int)(i - c0) : 0);  // the entrant's cost as computed (a NaN stays one)
-    __shared__ bool last;
-    if (threadIdx.x == 0) {
-        T.part_cost[blockIdx.x] = v;
-        T.part_idx[blockIdx.x] = i;
-        T.part_raw[blockIdx.x] = raw;
-        __threadfence();
-        last = atomicAdd(T.counters + m, 1u) == (unsigned)wps - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
-    v = INFINITY;
-    i = -1;
-    for (int k = threadIdx.x; k < wps; k += RT_THREADS) {
-        const double pv = __builtin_nontemporal_load(T.part_cost + m * wps + k);
-        const int64_t pi = __builtin_nontemporal_load(T.part_idx + m * wps + k);
-        if (better(pv, pi, v, i)) { v = pv; i = pi; }
-    }
-    wave_argmin(v, i);
+    const int64_t p0 = blockIdx.x - j;
+    if (!last_arriver_argmin(T.part_cost + p0, T.part_idx + p0, T.part_raw + p0, T.counters + m, j, wps, v, i, raw)) return;
     __shared__ float ctx_row[16];
-    if (threadIdx.x == 0) T.counters[m] = 0u;
     if (i >= 0) {
         // every lane computes the (wave-uniform) plant step and lane 0 stores it: with the fp64 pow and the dynamics
         // inside a one-lane branch the quadrotor kernel reserved a 36-byte private segment
@@ -698,16 +638,10 @@ __global__ __launch_bounds__(RT_THREADS) void closed_loop_tail_kernel(const SysK
 #pragma unroll
         for (int e = 0; e < nx; ++e) xc[e] = T.x_dev[m * nx + e];
 #pragma unroll
-        for (int e = 0; e < nu; ++e) {
-            double o = (double)unnorm1(T.u_norm[(size_t)i * row + e], clip, S.umin[e], S.umax[e]);
-            if (T.decimals >= 0) {
-                const double sc = pow(10.0, (double)T.decimals);
-                o = rint(o * sc) / sc;
-            }
-            u[e] = o;
-        }
+        for (int e = 0; e < nu; ++e)
+            u[e] = rounded_action(T.u_norm[(size_t)i * row + e], clip, S.umin[e], S.umax[e], T.decimals);
         dyn_step<SYS>(S, xc, u, xn);
-        const double raw_best = __builtin_nontemporal_load(T.part_raw + m * wps + (i - base) / RT_THREADS);
+        const double raw_best = __builtin_nontemporal_load(T.part_raw + p0 + (i - base) / RT_THREADS);
         if (threadIdx.x == 0) {
 #pragma unroll
             for (int e = 0; e < nx; ++e) {
@@ -736,34 +670,11 @@ __global__ __launch_bounds__(RT_THREADS) void closed_loop_tail_kernel(const SysK
     }
 }
 
-// ---- The control tail of one step for externally supplied states (mpcd_mpc_step_batch): closed_loop_tail_kernel's
-// grid and, up to the cross-workgroup reduction, its pieces in its order; no plant step, no history, no context row.
-
-// clip_flags_kernel's test over one state's slice cs[0, n) by one wave, as closed_loop_tail_kernel restates it
-__device__ __forceinline__ int state_clip_code(const float *cs, int64_t n)
-{
-    const float hi = (float)(1.0 + 1e-4), lo = (float)(-1.0 - 1e-4);
-    unsigned any = 0;
-    const int64_t n4 = ((uintptr_t)cs & 15) ? 0 : n >> 2;
-#pragma unroll 8
-    for (int64_t i = threadIdx.x; i < n4; i += RT_THREADS) {
-        const f32x4 v = ldg4(cs + 4 * i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) any |= clip_bits(v[e], hi, lo);
-    }
-    for (int64_t i = 4 * n4 + threadIdx.x; i < n; i += RT_THREADS) any |= clip_bits(cs[i], hi, lo);
-    __shared__ unsigned blk;
-    if (threadIdx.x == 0) blk = 0;
-    __syncthreads();
-    if (any) atomicOr(&blk, any);
-    __syncthreads();
-    return clip_code(blk);
-}
-
-// Per state, the last workgroup to arrive (the closed-loop tail's counter / fence / better() protocol) writes into the
-// packed result block the state's record {cost as computed, index, flags, u[n_u] fp64: control_step_kernel's
-// unnormalise and rounding} and, cooperatively across the wave, the selected plan unnormalised under the state's clip
-// flag; with prior_out, the next prior (shift_plan_kernel's rule on the winner's normalised plan).
+// The batched external step's tail: closed_loop_tail_kernel's front half; no plant step, no history, no context row.
+// The state's last workgroup writes into the packed result block the state's record {cost as computed, index, flags,
+// u[n_u] fp64: control_step_kernel's unnormalise and rounding} and, cooperatively across the wave, the selected plan
+// unnormalised under the state's clip flag; with prior_out, the next prior (shift_plan_kernel's rule on the winner's
+// normalised plan).
 template <int SYS>
 __global__ __launch_bounds__(RT_THREADS) void batch_step_tail_kernel(const SysK S, const BatchStepTail T)
 {
@@ -788,38 +699,14 @@ __global__ __launch_bounds__(RT_THREADS) void batch_step_tail_kernel(const SysK 
     int64_t i = c0 + threadIdx.x < end && (!T.select_first || b == base) ? b : -1;
     wave_argmin(v, i);  // RT_THREADS == one wave; every lane holds the result
     const double raw = __shfl(J, i >= 0 ? (int)(i - c0) : 0);  // the entrant's cost as computed (a NaN stays one)
-    __shared__ bool last;
-    if (threadIdx.x == 0) {
-        T.part_cost[blockIdx.x] = v;
-        T.part_idx[blockIdx.x] = i;
-        T.part_raw[blockIdx.x] = raw;
-        __threadfence();
-        last = atomicAdd(T.counters + m, 1u) == (unsigned)wps - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
-    v = INFINITY;
-    i = -1;
-    for (int k = threadIdx.x; k < wps; k += RT_THREADS) {
-        const double pv = __builtin_nontemporal_load(T.part_cost + m * wps + k);
-        const int64_t pi = __builtin_nontemporal_load(T.part_idx + m * wps + k);
-        if (better(pv, pi, v, i)) { v = pv; i = pi; }
-    }
-    wave_argmin(v, i);
-    if (threadIdx.x == 0) T.counters[m] = 0u;
+    const int64_t p0 = blockIdx.x - j;
+    if (!last_arriver_argmin(T.part_cost + p0, T.part_idx + p0, T.part_raw + p0, T.counters + m, j, wps, v, i, raw)) return;
     if (i < 0) return;  // not reached: group >= 1 leaves an entrant in the state's first workgroup
     // every lane computes the (wave-uniform) action and lane 0 stores it, as in closed_loop_tail_kernel
     double u[nu];
 #pragma unroll
-    for (int e = 0; e < nu; ++e) {
-        double o = (double)unnorm1(T.u_norm[(size_t)i * row + e], clip, S.umin[e], S.umax[e]);
-        if (T.decimals >= 0) {
-            const double sc = pow(10.0, (double)T.decimals);
-            o = rint(o * sc) / sc;
-        }
-        u[e] = o;
-    }
+    for (int e = 0; e < nu; ++e)
+        u[e] = rounded_action(T.u_norm[(size_t)i * row + e], clip, S.umin[e], S.umax[e], T.decimals);
     const double raw_best = __builtin_nontemporal_load(T.part_raw + m * wps + (i - base) / RT_THREADS);
     if (threadIdx.x == 0) {
         char *rec = T.result + m * T.rec_stride;
@@ -856,6 +743,43 @@ __global__ __launch_bounds__(256) void repeat_rows_kernel(const float *rows, int
     }
 }
 
+// The by-value system argument of the kernels above (x0 zero: launch_rollout_cost sets it)
+SysK make_sysk(const mpcd_system_desc &d, const float *umin_host, const float *umax_host)
+{
+    SysK S = {};
+    S.system = d.system;
+    S.cost_kind = d.cost_kind;
+    S.nx = d.n_x;
+    S.nu = d.n_u;
+    for (int i = 0; i < 24; ++i) S.params[i] = d.params[i];
+    for (int i = 0; i < 12; ++i) { S.Q[i] = d.Q[i]; S.P[i] = d.P[i]; S.xr[i] = d.x_ref[i]; }
+    for (int i = 0; i < 4; ++i) S.R[i] = d.R[i];
+    for (int i = 0; i < d.n_u; ++i) { S.umin[i] = umin_host[i]; S.umax[i] = umax_host[i]; }
+    return S;
+}
+
+// launch(std::integral_constant<int, SYS>) for the descriptor's system, refused unless its sizes are that system's
+template <class Launch>
+hipError_t dispatch_system(const mpcd_system_desc &d, Launch launch)
+{
+#define MPCD_SYSTEM(SYS_)                                                                        \
+    case SYS_:                                                                                   \
+        if (d.n_x != SysDim<SYS_>::NX || d.n_u != SysDim<SYS_>::NU) return hipErrorInvalidValue; \
+        launch(std::integral_constant<int, SYS_>{});                                             \
+        break;
+    switch (d.system) {
+        MPCD_SYSTEM(MPCD_SYS_CARTPOLE_LIN5)
+        MPCD_SYSTEM(MPCD_SYS_CARTPOLE_NL5)
+        MPCD_SYSTEM(MPCD_SYS_CARTPOLE_ZOH4)
+        MPCD_SYSTEM(MPCD_SYS_DOUBLE_INT2D)
+        MPCD_SYSTEM(MPCD_SYS_PENDULUM)
+        MPCD_SYSTEM(MPCD_SYS_QUADROTOR12)
+    default: return hipErrorInvalidValue;
+    }
+#undef MPCD_SYSTEM
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_repeat_rows(const float *rows, int64_t n_rows, int64_t n, int row_len, float *out, hipStream_t stream)
@@ -871,15 +795,7 @@ hipError_t launch_closed_loop_tail(const mpcd_system_desc &d, const float *umin_
                                    const float *cmin_host, const float *cmax_host, const ClosedLoopTail &t,
                                    hipStream_t stream)
 {
-    SysK S = {};
-    S.system = d.system;
-    S.cost_kind = d.cost_kind;
-    S.nx = d.n_x;
-    S.nu = d.n_u;
-    for (int i = 0; i < 24; ++i) S.params[i] = d.params[i];
-    for (int i = 0; i < 12; ++i) { S.Q[i] = d.Q[i]; S.P[i] = d.P[i]; S.xr[i] = d.x_ref[i]; }
-    for (int i = 0; i < 4; ++i) S.R[i] = d.R[i];
-    for (int i = 0; i < d.n_u; ++i) { S.umin[i] = umin_host[i]; S.umax[i] = umax_host[i]; }
+    const SysK S = make_sysk(d, umin_host, umax_host);
     NormF nk;
     for (int i = 0; i < 12; ++i) {
         nk.mn[i] = i < d.n_x ? cmin_host[i] : 0.f;
@@ -888,56 +804,24 @@ hipError_t launch_closed_loop_tail(const mpcd_system_desc &d, const float *umin_
     const int64_t wgs = t.n_states * ((t.group + RT_THREADS - 1) / RT_THREADS);
     if (t.n_states < 1 || t.group < 1 || wgs > 0x7fffffff) return hipErrorInvalidValue;
     const size_t lds = sizeof(float) * RT_THREADS * (t.H * d.n_u + 1);
-#define MPCD_TAIL(SYS_)                                                                                            \
-    case SYS_:                                                                                                     \
-        if (d.n_x != SysDim<SYS_>::NX || d.n_u != SysDim<SYS_>::NU) return hipErrorInvalidValue;                   \
-        hipLaunchKernelGGL(closed_loop_tail_kernel<SYS_>, dim3((unsigned)wgs), dim3(RT_THREADS), lds, stream, S, nk, t); \
-        break;
-    switch (d.system) {
-        MPCD_TAIL(MPCD_SYS_CARTPOLE_LIN5)
-        MPCD_TAIL(MPCD_SYS_CARTPOLE_NL5)
-        MPCD_TAIL(MPCD_SYS_CARTPOLE_ZOH4)
-        MPCD_TAIL(MPCD_SYS_DOUBLE_INT2D)
-        MPCD_TAIL(MPCD_SYS_PENDULUM)
-        MPCD_TAIL(MPCD_SYS_QUADROTOR12)
-    default: return hipErrorInvalidValue;
-    }
-#undef MPCD_TAIL
-    return hipGetLastError();
+    return dispatch_system(d, [&](auto sys) {
+        hipLaunchKernelGGL(closed_loop_tail_kernel<decltype(sys)::value>, dim3((unsigned)wgs), dim3(RT_THREADS), lds, stream,
+                           S, nk, t);
+    });
 }
 
 hipError_t launch_batch_step_tail(const mpcd_system_desc &d, const float *umin_host, const float *umax_host,
                                   const BatchStepTail &t, hipStream_t stream)
 {
-    SysK S = {};
-    S.system = d.system;
-    S.cost_kind = d.cost_kind;
-    S.nx = d.n_x;
-    S.nu = d.n_u;
-    for (int i = 0; i < 24; ++i) S.params[i] = d.params[i];
-    for (int i = 0; i < 12; ++i) { S.Q[i] = d.Q[i]; S.P[i] = d.P[i]; S.xr[i] = d.x_ref[i]; }
-    for (int i = 0; i < 4; ++i) S.R[i] = d.R[i];
-    for (int i = 0; i < d.n_u; ++i) { S.umin[i] = umin_host[i]; S.umax[i] = umax_host[i]; }
+    const SysK S = make_sysk(d, umin_host, umax_host);
     const int64_t wgs = t.n_states * ((t.group + RT_THREADS - 1) / RT_THREADS);
     if (t.n_states < 1 || t.group < 1 || wgs > 0x7fffffff) return hipErrorInvalidValue;
     if (t.rec_stride != batch_step_rec_stride(d.n_u) || t.plan_off < t.n_states * t.rec_stride) return hipErrorInvalidValue;
     const size_t lds = sizeof(float) * RT_THREADS * (t.H * d.n_u + 1);
-#define MPCD_BTAIL(SYS_)                                                                                         \
-    case SYS_:                                                                                                   \
-        if (d.n_x != SysDim<SYS_>::NX || d.n_u != SysDim<SYS_>::NU) return hipErrorInvalidValue;                 \
-        hipLaunchKernelGGL(batch_step_tail_kernel<SYS_>, dim3((unsigned)wgs), dim3(RT_THREADS), lds, stream, S, t); \
-        break;
-    switch (d.system) {
-        MPCD_BTAIL(MPCD_SYS_CARTPOLE_LIN5)
-        MPCD_BTAIL(MPCD_SYS_CARTPOLE_NL5)
-        MPCD_BTAIL(MPCD_SYS_CARTPOLE_ZOH4)
-        MPCD_BTAIL(MPCD_SYS_DOUBLE_INT2D)
-        MPCD_BTAIL(MPCD_SYS_PENDULUM)
-        MPCD_BTAIL(MPCD_SYS_QUADROTOR12)
-    default: return hipErrorInvalidValue;
-    }
-#undef MPCD_BTAIL
-    return hipGetLastError();
+    return dispatch_system(d, [&](auto sys) {
+        hipLaunchKernelGGL(batch_step_tail_kernel<decltype(sys)::value>, dim3((unsigned)wgs), dim3(RT_THREADS), lds, stream,
+                           S, t);
+    });
 }
 
 hipError_t launch_shift_plans(const float *rows, int64_t batch, int H, int d, const int64_t *index, int64_t offset,
@@ -988,16 +872,8 @@ hipError_t launch_rollout_cost(const mpcd_system_desc &d, const double *x0_host,
                                int64_t batch, int H, double *cost, hipStream_t stream, const RolloutSelect *sel)
 {
     if (group < 1) group = batch;
-    SysK S = {};
-    S.system = d.system;
-    S.cost_kind = d.cost_kind;
-    S.nx = d.n_x;
-    S.nu = d.n_u;
-    for (int i = 0; i < 24; ++i) S.params[i] = d.params[i];
-    for (int i = 0; i < 12; ++i) { S.Q[i] = d.Q[i]; S.P[i] = d.P[i]; S.xr[i] = d.x_ref[i]; }
-    for (int i = 0; i < 4; ++i) S.R[i] = d.R[i];
+    SysK S = make_sysk(d, umin_host, umax_host);
     for (int i = 0; i < d.n_x; ++i) S.x0[i] = x0_host ? x0_host[i] : 0.0;
-    for (int i = 0; i < d.n_u; ++i) { S.umin[i] = umin_host[i]; S.umax[i] = umax_host[i]; }
     const size_t lds = sizeof(float) * RT_THREADS * (H * d.n_u + 1);
     SelectK K = {};
     if (sel) {
@@ -1006,27 +882,15 @@ hipError_t launch_rollout_cost(const mpcd_system_desc &d, const double *x0_host,
                     sel->code_out, sel->clip_src, sel->clip_n,   sel->host_out, sel->host_flag, sel->host_seq};
     }
     const dim3 grid((unsigned)((batch + RT_THREADS - 1) / RT_THREADS));
-#define MPCD_ROLLOUT(SYS_)                                                                                          \
-    case SYS_:                                                                                                      \
-        if (d.n_x != SysDim<SYS_>::NX || d.n_u != SysDim<SYS_>::NU) return hipErrorInvalidValue;                    \
-        if (sel)                                                                                                    \
-            hipLaunchKernelGGL((rollout_cost_kernel<SYS_, true>), grid, dim3(RT_THREADS), lds, stream, S, u_norm,   \
-                               flag_dev, x0_dev, group, batch, H, cost, K);                                         \
-        else                                                                                                        \
-            hipLaunchKernelGGL((rollout_cost_kernel<SYS_, false>), grid, dim3(RT_THREADS), lds, stream, S, u_norm,  \
-                               flag_dev, x0_dev, group, batch, H, cost, K);                                         \
-        break;
-    switch (d.system) {
-        MPCD_ROLLOUT(MPCD_SYS_CARTPOLE_LIN5)
-        MPCD_ROLLOUT(MPCD_SYS_CARTPOLE_NL5)
-        MPCD_ROLLOUT(MPCD_SYS_CARTPOLE_ZOH4)
-        MPCD_ROLLOUT(MPCD_SYS_DOUBLE_INT2D)
-        MPCD_ROLLOUT(MPCD_SYS_PENDULUM)
-        MPCD_ROLLOUT(MPCD_SYS_QUADROTOR12)
-    default: return hipErrorInvalidValue;
-    }
-#undef MPCD_ROLLOUT
-    return hipGetLastError();
+    return dispatch_system(d, [&](auto sys) {
+        constexpr int SYS = decltype(sys)::value;
+        if (sel)
+            hipLaunchKernelGGL((rollout_cost_kernel<SYS, true>), grid, dim3(RT_THREADS), lds, stream, S, u_norm, flag_dev,
+                               x0_dev, group, batch, H, cost, K);
+        else
+            hipLaunchKernelGGL((rollout_cost_kernel<SYS, false>), grid, dim3(RT_THREADS), lds, stream, S, u_norm, flag_dev,
+                               x0_dev, group, batch, H, cost, K);
+    });
 }
 
 hipError_t launch_argmin(const double *cost, int64_t n, int64_t offset, mpcd_best *best, hipStream_t stream)
@@ -1060,31 +924,9 @@ hipError_t launch_control_step(const mpcd_system_desc &d, double *x_dev, int64_t
                                const int *flags_dev, int select_first, int decimals, double *u_applied,
                                int64_t *best_idx, double *best_cost, hipStream_t stream)
 {
-    SysK S = {};
-    S.system = d.system;
-    S.cost_kind = d.cost_kind;
-    S.nx = d.n_x;
-    S.nu = d.n_u;
-    for (int i = 0; i < 24; ++i) S.params[i] = d.params[i];
-    for (int i = 0; i < d.n_u; ++i) {
-        S.umin[i] = umin_host[i];
-        S.umax[i] = umax_host[i];
-    }
-#define MPCD_CSTEP(SYS_)                                                                                         \
-    case SYS_:                                                                                                   \
-        if (d.n_x != SysDim<SYS_>::NX || d.n_u != SysDim<SYS_>::NU) return hipErrorInvalidValue;                 \
-        hipLaunchKernelGGL(control_step_kernel<SYS_>, dim3((unsigned)M), dim3(CS_THREADS), 0, stream, S, x_dev, group, \
-                           u_norm, H, cost, flags_dev, select_first, decimals, u_applied, best_idx, best_cost);  \
-        break;
-    switch (d.system) {
-        MPCD_CSTEP(MPCD_SYS_CARTPOLE_LIN5)
-        MPCD_CSTEP(MPCD_SYS_CARTPOLE_NL5)
-        MPCD_CSTEP(MPCD_SYS_CARTPOLE_ZOH4)
-        MPCD_CSTEP(MPCD_SYS_DOUBLE_INT2D)
-        MPCD_CSTEP(MPCD_SYS_PENDULUM)
-        MPCD_CSTEP(MPCD_SYS_QUADROTOR12)
-    default: return hipErrorInvalidValue;
-    }
-#undef MPCD_CSTEP
-    return hipGetLastError();
+    const SysK S = make_sysk(d, umin_host, umax_host);
+    return dispatch_system(d, [&](auto sys) {
+        hipLaunchKernelGGL(control_step_kernel<decltype(sys)::value>, dim3((unsigned)M), dim3(CS_THREADS), 0, stream, S,
+                           x_dev, group, u_norm, H, cost, flags_dev, select_first, decimals, u_applied, best_idx, best_cost);
+    });
 }

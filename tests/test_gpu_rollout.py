@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from mpc_via_diffusion_model_amd import DiffusionMPC, NetSpec, systems
+from mpc_via_diffusion_model_amd import _native as N
 from oracle import sampler as osam
 from oracle import schedule as osch
 from oracle import systems as osys
@@ -34,24 +35,71 @@ def _x0(name, rng):
     return x
 
 
-@pytest.mark.parametrize("name", sorted(systems.REGISTRY))
-@pytest.mark.parametrize("spread", [0.9, 1.3])  # 1.3: global clip rule triggers
-def test_rollout_cost_matches_c_oracle(name, spread):
+def _limits(name):
+    return (-0.5, 0.3) if name == "quadrotor12" else (-3.0, 2.0)
+
+
+def _assert_cost(name, got, ref):
+    if name in EXACT:
+        np.testing.assert_array_equal(got, ref)
+    else:
+        np.testing.assert_allclose(got, ref, rtol=RTOL[name], atol=0)
+
+
+def _check_rollout_cost(name, spread, B, H):
     sysd = systems.get(name)
     rng = np.random.default_rng(5)
-    B, H = 1000, 32
-    lo, hi = (-0.5, 0.3) if name == "quadrotor12" else (-3.0, 2.0)
-    plan = _planner(d=sysd.n_u, H=H, C=2, lo=lo, hi=hi)
+    lo, hi = _limits(name)
+    plan = _planner(d=sysd.n_u, C=2, lo=lo, hi=hi)  # the cost call takes H from the samples
     x0 = _x0(name, rng)
     u_norm = rng.uniform(-spread, spread, (B, H, sysd.n_u)).astype(np.float32)
     u_dev = torch.from_numpy(u_norm).cuda()
     got = plan.rollout_cost(sysd, x0, u_dev).cpu().numpy()
     u = unnormalize_np(u_norm, np.full(sysd.n_u, lo), np.full(sysd.n_u, hi)).astype(np.float64)
-    ref = osys.rollout_cost(name, x0, u)
-    if name in EXACT:
-        np.testing.assert_array_equal(got, ref)
-    else:
-        np.testing.assert_allclose(got, ref, rtol=RTOL[name], atol=0)
+    _assert_cost(name, got, osys.rollout_cost(name, x0, u))
+
+
+@pytest.mark.parametrize("name", sorted(systems.REGISTRY))
+@pytest.mark.parametrize("spread", [0.9, 1.3])  # 1.3: global clip rule triggers
+def test_rollout_cost_matches_c_oracle(name, spread):
+    _check_rollout_cost(name, spread, B=1000, H=32)
+
+
+@pytest.mark.parametrize("name", sorted(systems.REGISTRY))
+@pytest.mark.parametrize("spread", [0.9, 1.3])
+def test_rollout_cost_odd_rows_match_c_oracle(name, spread):
+    """H = 7: rows of 7, 14 and 28 floats (n_u 1, 2, 4), so n_u = 1 and 2 stage their rows through the scalar loads
+    and n_u = 4 through the 16-byte ones at a row length that is no power of two; B = 70: one full workgroup and one of
+    6 candidates."""
+    _check_rollout_cost(name, spread, B=70, H=7)
+
+
+@pytest.mark.parametrize("name", sorted(systems.REGISTRY))
+def test_rollout_cost_grouped_odd_rows_match_c_oracle(name):
+    """The same shape through mpcd_rollout_cost_grouped: two plant states of 35 candidates each (the first workgroup
+    holds candidates of both), each with its own start state and clip flag (state 0 in range, state 1 clipped)."""
+    sysd = systems.get(name)
+    rng = np.random.default_rng(6)
+    M, n, H, d = 2, 35, 7, sysd.n_u
+    lo, hi = _limits(name)
+    plan = _planner(d=d, C=2, lo=lo, hi=hi)
+    x0 = np.stack([_x0(name, rng) for _ in range(M)])
+    u_norm = np.stack([rng.uniform(-s, s, (n, H, d)) for s in (0.9, 1.3)]).astype(np.float32)
+    u_dev = torch.from_numpy(u_norm.reshape(M * n, H, d)).cuda()
+    x_dev = torch.from_numpy(x0).cuda()
+    flags = torch.empty(M, dtype=torch.int32, device="cuda")
+    cost = torch.empty(M * n, dtype=torch.float64, device="cuda")
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    desc = sysd.desc()
+    N.check(plan._lib.mpcd_clip_flags(plan._ctx, ptr(u_dev), M, n * H * d, ptr(flags), plan._stream()), "mpcd_clip_flags")
+    N.check(plan._lib.mpcd_rollout_cost_grouped(plan._ctx, ctypes.byref(desc), ptr(x_dev), n, ptr(u_dev),
+                                                plan.act_min.ctypes.data, plan.act_max.ctypes.data, M * n, H, ptr(flags),
+                                                ptr(cost), plan._stream()), "mpcd_rollout_cost_grouped")
+    got = cost.cpu().numpy().reshape(M, n)
+    assert flags.cpu().tolist() == [0, 1]
+    for m in range(M):
+        u = unnormalize_np(u_norm[m], np.full(d, lo), np.full(d, hi)).astype(np.float64)
+        _assert_cost(name, got[m], osys.rollout_cost(name, x0[m], u))
 
 
 def test_calmpccost_kat5_on_gpu():
