@@ -248,6 +248,54 @@ struct MlpRw {
         }
     }
 
+    // accumulator init of pass p of hidden layer l: this wave's 4 values of the layer's bias / cond-table row
+    template <int l>
+    static MPCD_DEV f32x4 init_rd(const char *lds, int wave, int lane, int p)
+    {
+        constexpr int NT = A::N[l] / 16, NC = CL<l>, EPI = epi_of(l);
+        const int col = lane & 15, q = lane >> 4;
+        const int ct = ct_of<l>(wave, p % NC);
+        const float *init = reinterpret_cast<const float *>(
+            lds + (EPI == EPI_CMISH ? (masked_of(ct, col) ? L::TPU : L::TPC) + cond_off(l / 2) * 4 : L::BI + A::boff(l) * 4));
+        return *reinterpret_cast<const f32x4 *>(init + min(nt_of<l>(wave, p / NC), NT - 1) * 16 + 4 * q);
+    }
+    // byte offset in LDS of the operand fragments of pass p, k-chunk 0, plane 0
+    template <int l>
+    static MPCD_DEV int x_off(int wave, int lane, int p)
+    {
+        const int col = lane & 15, q = lane >> 4;
+        const int ct = ct_of<l>(wave, p % CL<l>);
+        const int row = (l == 0 && NB == 2) ? cand_of(ct, col) : ct * 16 + col;  // CFG: both branches read the candidate's x
+        return L::in_off(l) + row * L::in_rs(l) + 16 * (q ^ swz(row));
+    }
+
+    // The part of a layer's head that does not depend on the previous layer, issued BEFORE the barrier that opens the
+    // layer: the accumulator-init reads of its first two passes and the LDS address of its first operand reads. Behind
+    // the barrier they stood in front of the first MFMA (LDS reads complete in order: the MFMA waited for the init read
+    // and every operand read the compiler had placed before it); here the barrier's own lgkmcnt(0) retires them.
+    // Safe: the biases (BI) are written once, before the step loop. Step s + 1's cond tables (TPU / TPC) are written in
+    // Linear 12's last slot of step s and first read here before Linear 1's barrier, i.e. behind the barriers that open
+    // the final layer and Linear 0: two barriers later (step 0's are written before the loop's first barrier). Step s's
+    // are read last before Linear 11's barrier, and Linear 12's write stands behind Linear 12's barrier.
+    // The 8-wave form only: the 4-wave kernels stand at their 512 registers (rw32 spilled another 20 with the nine
+    // registers this keeps live across the barrier); they read inits and operands behind the barrier as before.
+    static constexpr bool HEAD_PRE = W == 8;
+    struct Pre {
+        f32x4 i0, i1;
+        int xa;
+    };
+    template <int l>
+    static MPCD_DEV Pre pre_of(const char *lds, int wave, int lane)
+    {
+        Pre h = {};
+        if constexpr (!HEAD_PRE) return h;
+        h.i0 = init_rd<l>(lds, wave, lane, 0);
+        h.i1 = TL<l> * CL<l> > 1 ? init_rd<l>(lds, wave, lane, 1) : h.i0;
+        h.xa = x_off<l>(wave, lane, 0);
+        asm volatile("" : "+v"(h.xa));  // formed here, not behind the barrier
+        return h;
+    }
+
     // Hidden layer l as a pipeline of passes (one n-tile x one column tile: a chain of 6 KC MFMAs, k-chunks in order):
     // the previous pass's epilogue (4 Mish, the 3-way split, the LDS stores of the next layer's operand planes) is
     // issued one micro-step after each of this pass's first MFMAs (pinned with sched_barrier: a bf16 MFMA leaves the
@@ -256,13 +304,16 @@ struct MlpRw {
     // n-tile j with this wave's fragments.
     // SIDE(k), k < NS: side work, one item per MFMA slot in order; items beyond the layer's slots (and all of them
     // on a wave with no tile) run after the layer's MFMAs
+    // The head (barrier to first MFMA) is on the critical path of every layer: pre (pre_of, issued before the barrier)
+    // brings the accumulator inits and the first operand address; behind the barrier stand only the operand reads,
+    // k-chunk 0's three planes first and in product order (pinned), so that the first three products wait on counted
+    // lgkmcnt for one plane each and never for the k-chunks read ahead.
     template <int l, int NS, class MM1, class SIDE>
-    static MPCD_DEV void hidden_ilv(MM1 mm1, SIDE side, char *lds, int wave, int lane)
+    static MPCD_DEV void hidden_ilv(MM1 mm1, SIDE side, const Pre &pre, char *lds, int wave, int lane)
     {
         constexpr int K = A::K[l], N = A::N[l], KC = K / 32, NT = N / 16, T = TL<l>, NC = CL<l>, EPI = epi_of(l);
         constexpr int NP = T * NC, NI = NP * KC;  // passes; (pass, k-chunk) steps
         const int col = lane & 15, q = lane >> 4;
-        constexpr bool in_shared = l == 0 && NB == 2;  // CFG: both branches read the candidate's x
         static_assert(T == 1 || NT % 4 == 0, "only a one-tile layer can leave a wave idle");
         if constexpr (NT < 4 && !SPL<l>)
             if (wave >= NT) {  // N = 32 at 16 rows: waves 2, 3 have no tile
@@ -279,20 +330,24 @@ struct MlpRw {
         auto jp = [](int p) { return p / NC; };
         auto cp = [](int p) { return p % NC; };
         auto init_of = [&](int p) {
-            const int ct = ct_of<l>(wave, cp(p));
-            const float *init = reinterpret_cast<const float *>(
-                lds + (EPI == EPI_CMISH ? (masked_of(ct, col) ? L::TPU : L::TPC) + cond_off(l / 2) * 4
-                                        : L::BI + A::boff(l) * 4));
-            return *reinterpret_cast<const f32x4 *>(init + min(nt_of<l>(wave, jp(p)), NT - 1) * 16 + 4 * q);
+            return HEAD_PRE && p == 0 ? pre.i0 : HEAD_PRE && p == 1 ? pre.i1 : init_rd<l>(lds, wave, lane, p);
         };
         auto ldx = [&](u32x4 (&x)[3], int i) {  // step i = (pass i / KC, k-chunk i % KC)
-            const int p = i / KC, kc = i % KC, ct = ct_of<l>(wave, cp(p));
-            const int row = in_shared ? cand_of(ct, col) : ct * 16 + col;
-            load_x3(x, lds + L::in_off(l) + row * L::in_rs(l) + kc * 64 + 16 * (q ^ swz(row)), L::in_pl(l));
+            const int p = i / KC, kc = i % KC;
+            load_x3(x, lds + (HEAD_PRE && p == 0 ? pre.xa : x_off<l>(wave, lane, p)) + kc * 64, L::in_pl(l));
         };
         u32x4 xb[PF + 1][3];  // operand fragments read PF k-chunks ahead
+        if constexpr (HEAD_PRE) {  // k-chunk 0: plane 0, 1, 2 in this order, ahead of every other read of the layer
+            const char *x0 = lds + pre.xa;
+            __builtin_amdgcn_sched_barrier(0);  // nothing of the layer's later address arithmetic ahead of the reads
 #pragma unroll
-        for (int i = 0; i < PF; ++i)
+            for (int pl = 0; pl < 3; ++pl) {
+                xb[0][pl] = *reinterpret_cast<const u32x4 *>(x0 + pl * L::in_pl(l));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+#pragma unroll
+        for (int i = HEAD_PRE ? 1 : 0; i < PF; ++i)
             if (i < NI) ldx(xb[i], i);
         f32x4 acc = init_of(0), nxt = acc, ev = acc;
         // The previous pass's epilogue as NSTEP micro-steps of one or two VALU instructions, one after each MFMA:
@@ -390,15 +445,15 @@ struct MlpRw {
     }
 
     template <int l, int NS = 0, class SIDE>
-    static MPCD_DEV void layer(const WS<l> &w, SIDE side, char *lds, int wave, int lane)
+    static MPCD_DEV void layer(const WS<l> &w, SIDE side, const Pre &pre, char *lds, int wave, int lane)
     {
         hidden_ilv<l, NS>(
             [&](int j, int kc, int m, const u32x4 (&x)[3], f32x4 acc) { return mfma_bf(w.v[j][kc][wpl(m)], x[xpl(m)], acc); },
-            side, lds, wave, lane);
+            side, pre, lds, wave, lane);
     }
 
     template <int li, int NS = 0, class SIDE>
-    static MPCD_DEV void layer_res(const Res &r, const Tail &t, SIDE side, char *lds, int wave, int lane)
+    static MPCD_DEV void layer_res(const Res &r, const Tail &t, SIDE side, const Pre &pre, char *lds, int wave, int lane)
     {
         hidden_ilv<RES_L0 + li, NS>(
             [&](int j, int kc, int m, const u32x4 (&x)[3], f32x4 acc) {
@@ -413,7 +468,7 @@ struct MlpRw {
                 if (last) return mfma_agpr1<false, true>(r.a[g][wpl(m)], x[xpl(m)], acc);
                 return mfma_agpr1<false, false>(r.a[g][wpl(m)], x[xpl(m)], acc);
             },
-            side, lds, wave, lane);
+            side, pre, lds, wave, lane);
     }
 
     // x (4 features) -> fp32 row in XB and the three bf16 planes layer 0 reads
@@ -475,7 +530,29 @@ struct MlpRw {
             }
     }
 
-    static MPCD_DEV void final_and_update(const FW &f, char *lds, const MlpSampleArgs &p, const StepPlan &sp, int s,
+    // The final layer's head before its barrier (as pre_of): its bias reads and its first operand address
+    struct FPre {
+        f32x4 b[NZT];
+        int xa;
+    };
+    static MPCD_DEV FPre final_pre(const char *lds, int wave, int lane)
+    {
+        constexpr int NT = D0 / 16;
+        const int col = lane & 15, q = lane >> 4;
+        const float *bias = reinterpret_cast<const float *>(lds + L::BI + A::boff(13) * 4);
+        FPre h = {};
+        if constexpr (!HEAD_PRE) return h;
+#pragma unroll
+        for (int j = 0; j < NZT; ++j) {
+            const int nt = (NT % 4 == 0 || (wave & 3) + 4 * j < NT) ? (wave & 3) + 4 * j : 0;
+            h.b[j] = *reinterpret_cast<const f32x4 *>(bias + nt * 16 + 4 * q);
+        }
+        h.xa = L::T1 + col * L::RS + 16 * (q ^ swz(col));
+        asm volatile("" : "+v"(h.xa));
+        return h;
+    }
+
+    static MPCD_DEV void final_and_update(const FW &f, const FPre &pre, char *lds, const MlpSampleArgs &p, const StepPlan &sp, int s,
                                           int64_t cand0, int n_cand, const f32x4 (&nz)[NZT][NB],
                                           uint32_t (&am)[2], f32x4 (&xr)[NZT][XG], int wave, int lane, ProfAcc &tacc)
     {
@@ -488,12 +565,23 @@ struct MlpRw {
 #pragma unroll
         for (int j = 0; j < T; ++j) {
             const int nt = (NT % 4 == 0 || wave + 4 * j < NT) ? wave + 4 * j : 0;
-            acc[j][0] = acc[j][1] = *reinterpret_cast<const f32x4 *>(bias + nt * 16 + 4 * q);
+            acc[j][0] = acc[j][1] = HEAD_PRE ? pre.b[j] : *reinterpret_cast<const f32x4 *>(bias + nt * 16 + 4 * q);
         }
-        // both column tiles' operand reads in flight before the first MFMA: one LDS latency instead of two in a row
+        // both column tiles' operand reads in flight before the first MFMA: one LDS latency instead of two in a row;
+        // HEAD_PRE: the first tile's planes in product order (pinned), so that the first product waits for one read
         u32x4 xf[NCT][3];
 #pragma unroll
-        for (int c = 0; c < NCT; ++c) load_x3(xf[c], lds + L::T1 + (c * 16 + col) * L::RS + 16 * (q ^ swz(col)), L::PL);
+        for (int c = 0; c < NCT; ++c) {
+            if constexpr (HEAD_PRE) {
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) {
+                    xf[c][pl] = *reinterpret_cast<const u32x4 *>(lds + pre.xa + c * 16 * L::RS + pl * L::PL);
+                    if (c == 0) __builtin_amdgcn_sched_barrier(0);
+                }
+            } else {
+                load_x3(xf[c], lds + L::T1 + (c * 16 + col) * L::RS + 16 * (q ^ swz(col)), L::PL);
+            }
+        }
         // XREG, DDPM: the x-only products of the update under the operand reads' latency (each through a
         // fence, the same values as in the update's order: a x, c2 x, std z are separate roundings there too)
         constexpr bool PRE = XREG && IS_DDPM;
@@ -757,10 +845,9 @@ struct MlpRw {
             store_x(lds, c, qd * 4, z);
         }
         f32x4 xr[NZT][XG];
-        if constexpr (XREG) {
-            lds_barrier();
-            load_xr(xr, lds, wave, lane);
-        }
+        // the staged biases, context projection and x_T: read by load_xr, and by step 0's tables below (HEAD_PRE)
+        if constexpr (XREG || HEAD_PRE) lds_barrier();
+        if constexpr (XREG) load_xr(xr, lds, wave, lane);
 
         int wofs = 0;
         WS<0> w0;
@@ -770,6 +857,23 @@ struct MlpRw {
         if constexpr (W == 4) fetch_noise(nz, p, sp, 0, cand0, n_cand, wave, lane);
         const int tpi = threadIdx.x < COND_TOTAL / 4 ? (int)threadIdx.x : threadIdx.x < COND_TOTAL / 2 ? (int)threadIdx.x - COND_TOTAL / 4 : 0;
         f32x4 tpre = reinterpret_cast<const f32x4 *>(p.tproj)[tpi];
+        // A step's time projections + cond biases (+ shared context part) -> TPU / TPC: one f32x4 per thread. Step
+        // s + 1's are written as Linear 12's side work. The first step's: HEAD_PRE here, ordered before every read by the
+        // step loop's first barrier (Linear 1's init reads are issued behind it, before Linear 1's own barrier: pre_of);
+        // the 4-wave kernels behind that barrier (their loop as it was, instruction for instruction)
+        auto table = [&] {
+            if (threadIdx.x < COND_TOTAL / 2) {
+                const bool ctx_half = threadIdx.x >= COND_TOTAL / 4;
+                const int k = ctx_half ? (int)threadIdx.x - COND_TOTAL / 4 : (int)threadIdx.x;
+                f32x4 u = tpre + reinterpret_cast<const f32x4 *>(lds + L::BIC)[k];
+                if (ctx_half) u = u + reinterpret_cast<const f32x4 *>(lds + L::CPS)[k];
+                reinterpret_cast<f32x4 *>(lds + (ctx_half ? L::TPC : L::TPU))[k] = u;
+            }
+        };
+        if constexpr (HEAD_PRE) {
+            table();
+            tpre = reinterpret_cast<const f32x4 *>(p.tproj + (size_t)(1 < p.n_steps ? 1 : 0) * COND_TOTAL)[tpi];
+        }
         // MPCD_PROF_LAYERS build (mlp_common.h): cycles of each barrier-to-barrier segment (tools/layer_prof.py)
         ProfAcc tacc = {};
         const uint64_t rt0 = prof_realtime();
@@ -778,13 +882,20 @@ struct MlpRw {
 #ifdef MPCD_PROF_LAYERS
         int bk = 0;  // the segment: 14 barriers per denoise step
         auto bar = [&] {
+            if constexpr (HEAD_PRE) __builtin_amdgcn_s_waitcnt(0xC07F);  // as in the product build, below
             prof_barrier(tacc, tprev, bk);
             bk = bk == 13 ? 0 : bk + 1;
         };
 #else
         // No capture here and no mark in noise_next below in the product build: the empty forms of both in the lambdas'
         // closures changed the order of two scalar copies in three rw32 kernels (profiles/mlp_switch_cleanup_isa.txt)
-        auto bar = [] { lds_barrier(); };
+        // HEAD_PRE: the barrier's lgkmcnt(0) once more as the builtin (0xC07F: lgkmcnt(0) alone), which the compiler's
+        // wait counting sees (the one inside lds_barrier's asm it does not): with a scalar load or an LDS operation of
+        // the previous layer still outstanding in its books, every head's first wait came out as lgkmcnt(0)
+        auto bar = [] {
+            if constexpr (HEAD_PRE) __builtin_amdgcn_s_waitcnt(0xC07F);
+            lds_barrier();
+        };
 #endif
         int lane_l = lane;
         for (int s = 0; s < p.n_steps; ++s) {
@@ -804,31 +915,28 @@ struct MlpRw {
             load_ws<1>(w1, ws, wave, lane16);
             WS<2> w2;
             load_ws<2>(w2, ws, wave, lane16);
+            // Every layer's pre_of / final_pre stands before the barrier that opens the layer (see pre_of)
+            Pre hd = pre_of<0>(lds, wave, lane);
             bar();
-            // A step's time projections + cond biases (+ shared context part) -> TPU / TPC: one f32x4 per thread. The
-            // first step's here; step s + 1's are written after Linear 11 (the last layer that reads step s's) and not at
-            // the step's start, where their LDS round trip delayed Linear 0's first operand reads
-            auto table = [&] {
-                if (threadIdx.x < COND_TOTAL / 2) {
-                    const bool ctx_half = threadIdx.x >= COND_TOTAL / 4;
-                    const int k = ctx_half ? (int)threadIdx.x - COND_TOTAL / 4 : (int)threadIdx.x;
-                    f32x4 u = tpre + reinterpret_cast<const f32x4 *>(lds + L::BIC)[k];
-                    if (ctx_half) u = u + reinterpret_cast<const f32x4 *>(lds + L::CPS)[k];
-                    reinterpret_cast<f32x4 *>(lds + (ctx_half ? L::TPC : L::TPU))[k] = u;
+            if constexpr (!HEAD_PRE)
+                if (s == 0) {
+                    table();
+                    tpre = reinterpret_cast<const f32x4 *>(p.tproj + (size_t)(s + 1 < p.n_steps ? s + 1 : s) * COND_TOTAL)[tpi];
                 }
-            };
-            if (s == 0) {
-                table();
-                tpre = reinterpret_cast<const f32x4 *>(p.tproj + (size_t)(s + 1 < p.n_steps ? s + 1 : s) * COND_TOTAL)[tpi];
-            }
             // W = 8 (256 registers per wave, 120 of them resident weights): every streamed layer's fragments are
-            // issued one layer later than at W = 4, so that at most two layers' stand in registers at a time
+            // issued one layer later than at W = 4, so that at most two layers' stand in registers at a time.
+            // A layer that leaves waves 4-7 without a tile (N = 32) has two arms, and loads issued inside the arms are
+            // no longer counted at the join: the next head then drains vmcnt(0), on waves 4-7 for loads issued just
+            // before the barrier. So at W = 8 no fragment load stands inside such a layer: Linear 3's are issued behind
+            // Linear 1 (after the join), Linear 11's in Linear 9's slots, Linear 12's and the final layer's behind
+            // Linear 10.
             WS<3> w3;
             WS<4> w4;
             auto side3 = [&](int k) { load_ws1<3>(w3, ws, wave, lane16, k); };
             auto side4 = [&](int k) { load_ws1<4>(w4, ws, wave, lane16, k); };
-            if constexpr (W == 8) layer<0>(w0, none, lds, wave, lane);
-            else layer<0, NFRAG<3>>(w0, side3, lds, wave, lane);
+            if constexpr (W == 8) layer<0>(w0, none, hd, lds, wave, lane);
+            else layer<0, NFRAG<3>>(w0, side3, hd, lds, wave, lane);
+            hd = pre_of<1>(lds, wave, lane);
             bar();
             WS<8> w8;
             Tail tail;
@@ -862,70 +970,91 @@ struct MlpRw {
 #endif
                 }
             };
-            if constexpr (W == 8) layer<1, NFRAG<3>>(w1, side3, lds, wave, lane);
-            else layer<1, NFRAG<4>>(w1, side4, lds, wave, lane);
+            if constexpr (W == 8) {
+                layer<1>(w1, none, hd, lds, wave, lane);
+                load_ws<3>(w3, ws, wave, lane16);
+            } else {
+                layer<1, NFRAG<4>>(w1, side4, hd, lds, wave, lane);
+            }
+            hd = pre_of<2>(lds, wave, lane);
             bar();
-            if constexpr (W == 8) layer<2, NFRAG<4>>(w2, side4, lds, wave, lane);
-            else layer<2>(w2, none, lds, wave, lane);
+            if constexpr (W == 8) layer<2, NFRAG<4>>(w2, side4, hd, lds, wave, lane);
+            else layer<2>(w2, none, hd, lds, wave, lane);
+            hd = pre_of<3>(lds, wave, lane);
             bar();
-            layer<3>(w3, none, lds, wave, lane);
+            layer<3>(w3, none, hd, lds, wave, lane);
+            hd = pre_of<4>(lds, wave, lane);
             bar();
-            layer<4>(w4, none, lds, wave, lane);
+            layer<4>(w4, none, hd, lds, wave, lane);
+            hd = pre_of<5>(lds, wave, lane);
             bar();
+            // The next step's plan: a scalar load, which returns out of order and so makes any wait behind it an
+            // lgkmcnt(0). Issued before Linear 8's barrier, whose own lgkmcnt(0) retires it, never at a head. The last
+            // step reads its own entry again (nothing past the plan's end) and does not use it.
             if constexpr (W == 8) {
                 // 256 registers per wave, 120 of them resident weights: Linear 8's 24 fragments (96 registers) never
-                // stand whole. Its first W8P k-chunks are issued behind Linear 7's MFMAs (the Tail's registers die
-                // there as they are used), k-chunk c >= W8P in the MFMA slots of k-chunk c - W8P + 1 of Linear 8
-                // itself (into registers its first chunks have left), Linear 9's in the slots of k-chunk 6.
-                constexpr int W8P = 4, KC8 = A::K[8] / 32, S9 = 6 * 6;
+                // stand whole. Its first W8P k-chunks are issued in the MFMA slots of Linear 7's second pass (Linear 7's
+                // own streamed Tail in Linear 6's slots), k-chunk c >= W8P in the MFMA slots of k-chunk c - W8P + 1 of
+                // Linear 8 itself (into registers its first chunks have left), Linear 9's in the slots of k-chunk 6.
+                constexpr int W8P = 4, KC8 = A::K[8] / 32, S9 = 6 * 6, S7 = 5 * 6, W8S = 12, NTL = (NRG - NAG) * 3;
                 static_assert(NFRAG<8> == KC8 * 3 && NFRAG<9> == 6 && W8P >= 2);
-                layer_res<0>(res, tail, none, lds, wave, lane);
+                layer_res<0>(res, tail, none, hd, lds, wave, lane);
+                hd = pre_of<6>(lds, wave, lane);
                 bar();
-                layer_res<1>(res, tail, none, lds, wave, lane);
-                load_tail(tail, ws, wave, lane16);
+                layer_res<1, 6 + NTL>(res, tail, [&](int k) { if (k >= 6) load_tail1(tail, ws, wave, lane16, k - 6); }, hd, lds, wave, lane);
+                hd = pre_of<7>(lds, wave, lane);
                 bar();
-                layer_res<2>(res, tail, none, lds, wave, lane);
+                layer_res<2, S7 + W8S>(res, tail, [&](int k) { if (k >= S7) load_ws1<8>(w8, ws, wave, lane16, k - S7); }, hd,
+                                       lds, wave, lane);
 #pragma unroll
-                for (int f = 0; f < W8P * 3; ++f) load_ws1<8>(w8, ws, wave, lane16, f);
+                for (int f = W8S; f < W8P * 3; ++f) load_ws1<8>(w8, ws, wave, lane16, f);
+                sp = load_plan(p.plan, s + 1 < p.n_steps ? s + 1 : s);
+                hd = pre_of<8>(lds, wave, lane);
                 bar();
-                if (s + 1 < p.n_steps) sp = load_plan(p.plan, s + 1);
                 auto stream8 = [&](int k) {
                     const int kc = k / 6, m = k % 6;
                     if (kc >= 1 && kc + W8P - 1 < KC8 && m < 3) load_ws1<8>(w8, ws, wave, lane16, (kc + W8P - 1) * 3 + m);
                     if (k >= S9 && k < S9 + NFRAG<9>) load_ws1<9>(w9, ws, wave, lane16, k - S9);
                 };
-                layer<8, KC8 * 6>(w8, stream8, lds, wave, lane);
+                layer<8, KC8 * 6>(w8, stream8, hd, lds, wave, lane);
                 load_ws<10>(w10, ws, wave, lane16);
+                hd = pre_of<9>(lds, wave, lane);
                 bar();
             } else {
                 // Linear 8's streamed fragments issued half in Linear 5's MFMA slots, half in Linear 6's (all 24 in
                 // Linear 6's measured slower, profiles/r6_mlp_tuning_ab.txt)
                 constexpr int W8A = NFRAG<8> / 2;
-                layer_res<0, W8A>(res, tail, [&](int k) { load_ws1<8>(w8, ws, wave, lane16, k); }, lds, wave, lane);
+                layer_res<0, W8A>(res, tail, [&](int k) { load_ws1<8>(w8, ws, wave, lane16, k); }, hd, lds, wave, lane);
+                hd = pre_of<6>(lds, wave, lane);
                 bar();
-                layer_res<1, NFRAG<8> - W8A>(res, tail, [&](int k) { load_ws1<8>(w8, ws, wave, lane16, W8A + k); }, lds, wave,
+                layer_res<1, NFRAG<8> - W8A>(res, tail, [&](int k) { load_ws1<8>(w8, ws, wave, lane16, W8A + k); }, hd, lds, wave,
                                              lane);
                 load_tail(tail, ws, wave, lane16);
+                hd = pre_of<7>(lds, wave, lane);
                 bar();
-                layer_res<2>(res, tail, none, lds, wave, lane);
+                layer_res<2>(res, tail, none, hd, lds, wave, lane);
                 load_ws<9>(w9, ws, wave, lane16);
+                hd = pre_of<8>(lds, wave, lane);
                 bar();
                 if (s + 1 < p.n_steps) sp = load_plan(p.plan, s + 1);
                 if constexpr (STAGED_NOISE) {
                     ph_init(ph, p, s + 2, cand0, wave, lane);  // step s + 1's noise is Philox slice s + 2 (fetch_noise)
-                    layer<8, NPH>(w8, [&](int k) { ph_step(ph, k); }, lds, wave, lane);
+                    layer<8, NPH>(w8, [&](int k) { ph_step(ph, k); }, hd, lds, wave, lane);
                 } else {
-                    layer<8>(w8, none, lds, wave, lane);
+                    layer<8>(w8, none, hd, lds, wave, lane);
                 }
                 load_ws<10>(w10, ws, wave, lane16);  // after L8: w8's 96 registers are free again
+                hd = pre_of<9>(lds, wave, lane);
                 bar();
             }
             constexpr int NS9 = NFRAG<11> + NFRAG<12> + NFRAG<13>;
             if constexpr (W == 8) {
-                // Linear 11-13's fragments behind the second half of Linear 10's MFMAs, where half of its own 12
+                // Linear 11's fragments behind Linear 9 (every wave has a tile there: no join; in its slots they do not
+                // fit beside Linear 9's and 10's), Linear 12's and the final layer's behind Linear 10, where its own 12
                 // fragments are spent
-                constexpr int S10 = (A::K[10] / 32) * 6 / 2;
-                layer<9>(w9, none, lds, wave, lane);
+                layer<9>(w9, none, hd, lds, wave, lane);
+                load_ws<11>(w11, ws, wave, lane16);
+                hd = pre_of<10>(lds, wave, lane);
                 bar();
                 // This step's noise, drawn (or fetched) by waves 4-7, which have no tile in Linear 10-12 and the final
                 // layer: lane for lane what wave - 4 would draw (fetch_noise: the same bits), handed over in the C0
@@ -939,47 +1068,66 @@ struct MlpRw {
                         for (int j = 0; j < NZT; ++j)
                             *reinterpret_cast<f32x4 *>(lds + L::C0 + ((j * 4 + wave - 4) * 64 + lane) * 16) = nzh[j][0];
                     }
-                layer<10, S10 + NS9>(w10, [&](int k) { if (k >= S10) side9(k - S10); }, lds, wave, lane);
+                layer<10>(w10, none, hd, lds, wave, lane);
+                load_ws<12>(w12, ws, wave, lane16);
+                load_ws<13>(w13, ws, wave, lane16);
             } else {
-                layer<9, NS9>(w9, side9, lds, wave, lane);
+                layer<9, NS9>(w9, side9, hd, lds, wave, lane);
+                hd = pre_of<10>(lds, wave, lane);
                 bar();
-                layer<10>(w10, none, lds, wave, lane);
+                layer<10>(w10, none, hd, lds, wave, lane);
                 noise_next();
                 load_ws<0>(w0, ws, wave, lane16);  // next step's layer 0 (unconditional: path-independent load count)
             }
+            hd = pre_of<11>(lds, wave, lane);
             bar();
-            layer<11>(w11, none, lds, wave, lane);
+            layer<11>(w11, none, hd, lds, wave, lane);
+            hd = pre_of<12>(lds, wave, lane);
+            // W = 8: the thread's table slot from the laundered lane, formed here in front of Linear 12's barrier (as a
+            // loop invariant it stood in a register the step loop does not have: it was spilled)
+            const int tid = wave * 64 + lane;
+            int tpl = W == 8 ? (tid < COND_TOTAL / 4 ? tid : tid < COND_TOTAL / 2 ? tid - COND_TOTAL / 4 : 0) : tpi;
+            if constexpr (W == 8) asm volatile("" : "+v"(tpl));
             bar();
             {
                 // step s + 1's tables as Linear 12's side work: both reads in its first MFMA slot, the add and the
                 // write in its last (Linear 11 read step s's tables last; the barrier above orders them)
                 constexpr int NS12 = TL<12> * CL<12> * (A::K[12] / 32) * 6;
-                const bool ctx_half = threadIdx.x >= COND_TOTAL / 4;
+                const bool ctx_half = W == 8 ? tid >= COND_TOTAL / 4 : threadIdx.x >= COND_TOTAL / 4;
+                const bool in_tab = W == 8 ? tid < COND_TOTAL / 2 : threadIdx.x < COND_TOTAL / 2;
                 f32x4 tb0, tb1;
                 layer<12, NS12>(w12, [&](int k) {
                     if (k == 0) {
-                        tb0 = reinterpret_cast<const f32x4 *>(lds + L::BIC)[tpi];
-                        tb1 = reinterpret_cast<const f32x4 *>(lds + L::CPS)[tpi];
-                    } else if (k == NS12 - 1 && s + 1 < p.n_steps && threadIdx.x < COND_TOTAL / 2) {
+                        tb0 = reinterpret_cast<const f32x4 *>(lds + L::BIC)[tpl];
+                        tb1 = reinterpret_cast<const f32x4 *>(lds + L::CPS)[tpl];
+                    } else if (k == NS12 - 1 && s + 1 < p.n_steps && in_tab) {
                         f32x4 u = tpre + tb0;
                         if (ctx_half) u = u + tb1;
-                        reinterpret_cast<f32x4 *>(lds + (ctx_half ? L::TPC : L::TPU))[tpi] = u;
+                        reinterpret_cast<f32x4 *>(lds + (ctx_half ? L::TPC : L::TPU))[tpl] = u;
                     }
-                }, lds, wave, lane);
-                if (s + 1 < p.n_steps)
-                    tpre = reinterpret_cast<const f32x4 *>(p.tproj + (size_t)(s + 2 < p.n_steps ? s + 2 : s + 1) * COND_TOTAL)[tpi];
+                }, hd, lds, wave, lane);
+                // HEAD_PRE: unconditional (no load inside a branch ahead of the final layer's head); the last steps read
+                // the last row again and do not use it
+                if (HEAD_PRE || s + 1 < p.n_steps)
+                    tpre = reinterpret_cast<const f32x4 *>(
+                        p.tproj + (size_t)(s + 2 < p.n_steps ? s + 2 : HEAD_PRE ? p.n_steps - 1 : s + 1) * COND_TOTAL)[tpl];
             }
             if constexpr (W == 8 && !W0_LATE) load_ws<0>(w0, ws, wave, lane16);  // next step's layer 0, behind the final layer
-            bar();
-            if constexpr (W == 8) {
+            const FPre fhd = final_pre(lds, wave, lane);
+            // W = 8: the noise waves 4-7 left in C0 behind Linear 9's barrier. One quad per lane: read here, two barriers
+            // later and before the final layer's own; more quads: behind it (registers)
+            auto take_noise = [&] {
 #pragma unroll
                 for (int j = 0; j < NZT; ++j) {
 #pragma unroll
                     for (int g = 0; g < NB; ++g) nzc[j][g] = f32x4{0.f, 0.f, 0.f, 0.f};
                     if (IS_DDPM && wave < 4) nzc[j][0] = *reinterpret_cast<const f32x4 *>(lds + L::C0 + ((j * 4 + wave) * 64 + lane) * 16);
                 }
-            }
-            final_and_update(w13, lds, p, cur, s, cand0, n_cand, nzc, am, xr, wave, lane, tacc);
+            };
+            if constexpr (W == 8 && NZT == 1) take_noise();
+            bar();
+            if constexpr (W == 8 && NZT != 1) take_noise();
+            final_and_update(w13, fhd, lds, p, cur, s, cand0, n_cand, nzc, am, xr, wave, lane, tacc);
             if constexpr (W == 8 && W0_LATE) load_ws<0>(w0, ws, wave, lane16);  // H*d = 128: after the update's registers
         }
         MPCD_PROF_DUMP(W, threadIdx.x >> 6, lane);
