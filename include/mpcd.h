@@ -253,6 +253,31 @@ typedef struct {
 int mpcd_argmin(mpcd_ctx *ctx, const double *cost, int64_t n, int64_t index_offset, mpcd_best *best_dev,
                 void *hip_stream);
 
+/* ---- Elite sets: the k best plans of each plant state, ranked on the device, and the per-candidate warm-start priors
+ * seeded from them (mpcd_warm_start.rows == batch). One shared prior collapses a warm-started candidate set onto one
+ * mode at a small t_start; seeding candidate j from elite j mod k keeps k modes alive. The ranked list also serves a
+ * caller that wants fallback plans, or the first plan that passes a safety filter, without downloading every cost. */
+#define MPCD_MAX_ELITES 64
+/* Ranked top-k per group: for m < n_groups, out_dev[m][0..k) = the k best of cost[m * group, (m + 1) * group), best
+ * first, in mpcd_argmin's order: NaN ranks (and is reported) as +inf, lower cost wins, then lower index. index =
+ * index_offset + the entry's position in cost[] (m * group + j: mpcd_control_step's global candidate index), so with
+ * n_groups == 1 entry 0 is bit for bit mpcd_argmin's winner, and entry 0 of group m mpcd_control_step's. One launch, one
+ * workgroup per group; every cost is read from memory once. cost dev fp64 [n_groups * group]; out_dev dev
+ * [n_groups][k]. MPCD_EINVAL: a null pointer, n_groups / group < 1, k < 1, k > group or k > MPCD_MAX_ELITES. */
+int mpcd_topk(mpcd_ctx *ctx, const double *cost, int64_t n_groups, int64_t group, int32_t k, int64_t index_offset,
+              mpcd_best *out_dev /* [n_groups][k], best first */, void *hip_stream);
+/* The priors an elite set seeds: with batch = n_groups * group, for candidate b = m * group + j
+ *     out[b][h] = u_norm[elites_dev[m][j mod k].index - index_offset][min(h + shift, H - 1)]
+ * shift == 1: mpcd_shift_plans' rule (the plan moved one horizon point ahead, its last point repeated), for the next
+ * control step; shift == 0: the plan as it is, for re-sampling within one control step. u_norm and out dev
+ * [batch][H][d] (d = the net's state_dim), elites_dev dev [n_groups][k] as mpcd_topk writes it (only .index is read).
+ * An elite whose index falls outside [index_offset, index_offset + batch) leaves its candidates' rows of out as they
+ * are (mpcd_shift_plans' rule). One launch, spread over the whole of out. MPCD_EINVAL: a null pointer, n_groups / group
+ * < 1, k < 1, k > group or k > MPCD_MAX_ELITES, shift not 0 or 1, horizon != the net's, out overlapping u_norm. */
+int mpcd_elite_priors(mpcd_ctx *ctx, const float *u_norm, int64_t n_groups, int64_t group, int32_t horizon,
+                      const mpcd_best *elites_dev, int32_t k, int64_t index_offset, int32_t shift,
+                      float *out /* dev [n_groups*group][H][d] */, void *hip_stream);
+
 /* ---- Closed loop on the device: M plant states advanced together, each with its
  * own group of `group` consecutive candidates, no host round trip inside the loop
  * (Cart_Diffusion_inference.py:405-512 runs one state at a time on the host). */
@@ -504,6 +529,25 @@ int mpcd_mpc_step(mpcd_ctx *ctx, const mpcd_step_args *args, mpcd_best *best_hos
 int mpcd_mpc_step_warm(mpcd_ctx *ctx, const mpcd_step_args *args, const mpcd_warm_start *warm /* rows == 1 */,
                        float *next_init_out /* dev [H][d] or NULL */, mpcd_best *best_host, float *u_best_host,
                        void *hip_stream);
+/* mpcd_mpc_step_warm with an elite set (single rank). Differences:
+ *  - warm->rows is 1 (one prior for every candidate) or sample.batch (one per candidate: the priors a previous call
+ *    wrote); t_start == 0 is a cold step that still fills the priors.
+ *  - after the selection, mpcd_topk over cost_local (one group of `batch`, index_offset = sample.global_offset) and,
+ *    next_priors_out non-null, mpcd_elite_priors(shift = 1) of sample.x_out into next_priors_out follow on hip_stream:
+ *    candidate j's next prior is elite j mod k's plan moved one horizon point ahead, so row 0 is the winner's.
+ *    next_priors_out is a DEVICE output ordered on hip_stream, like next_init_out.
+ *  - elites_host non-null: the k elites {cost, global index}, best first, complete when the call returns like
+ *    best_host (the top-k launch writes them to mapped host memory and the call waits for its completion word);
+ *    elites_host[0] equals *best_host.
+ * The MPCD_F16X2 re-run rule is mpcd_mpc_step's: next_priors_out may not overlap warm->x_init (keep two buffers and swap
+ * them), nor sample.x_out.
+ * MPCD_EINVAL: mpcd_mpc_step_warm's cases; k < 1, k > sample.batch or k > MPCD_MAX_ELITES; t_start > 0 with rows
+ * neither 1 nor batch; next_priors_out overlapping warm->x_init. MPCD_EUNSUP: a context with a communicator (the elite
+ * rows live on other ranks; exchanging them is separate work); t_start > 0 with a DDIM sampler. */
+int mpcd_mpc_step_elite(mpcd_ctx *ctx, const mpcd_step_args *args, const mpcd_warm_start *warm /* rows == 1 or batch */,
+                        int32_t k, float *next_priors_out /* dev [batch][H][d] or NULL */,
+                        mpcd_best *elites_host /* [k] or NULL */, mpcd_best *best_host, float *u_best_host,
+                        void *hip_stream);
 
 /* Failure-detection flags of the last mpcd_mpc_step on this context (read after it returned):
  * bit 0 (MPCD_STEP_CLIPPED): LimitsNormalizer's global clip was applied; bit 1 (MPCD_STEP_NAN_SAMPLES): some

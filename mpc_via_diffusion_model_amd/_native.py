@@ -18,6 +18,7 @@ MPCD_F32, MPCD_F16, MPCD_F32X3, MPCD_F16X2 = 0, 1, 2, 3
 MPCD_DDPM_CFG, MPCD_DDIM_CFG, MPCD_DDIM = 0, 1, 2
 MPCD_COST_CANONICAL, MPCD_COST_CALMPC = 0, 1
 MPCD_COMM_ID_BYTES = 128
+MPCD_MAX_ELITES = 64
 MPCD_CLIP_CHAIN, MPCD_CLIP_FINAL, MPCD_CLIP_NONE = 0, 1, 2
 
 _STATUS = {-1: "EINVAL", -2: "EHIP", -3: "ESTATE", -4: "ENOMEM", -5: "EUNSUP", -6: "ENONFINITE"}
@@ -114,6 +115,14 @@ EXPORTS = {
                           ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "mpcd_mpc_step_warm": ([ctypes.c_void_p, ctypes.POINTER(StepArgs), ctypes.POINTER(WarmStart), ctypes.c_void_p,
                             ctypes.POINTER(Best), ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "mpcd_topk": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                   ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "mpcd_elite_priors": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                           ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p,
+                           ctypes.c_void_p], ctypes.c_int),
+    "mpcd_mpc_step_elite": ([ctypes.c_void_p, ctypes.POINTER(StepArgs), ctypes.POINTER(WarmStart), ctypes.c_int32,
+                             ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Best), ctypes.c_void_p, ctypes.c_void_p],
+                            ctypes.c_int),
     "mpcd_eps": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "mpcd_clip_flag": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p],

@@ -209,5 +209,19 @@ struct BatchStepTail : TailCommon {
 constexpr int64_t batch_step_rec_stride(int n_u) { return (int64_t)sizeof(mpcd_state_result) + 8 * n_u; }
 hipError_t launch_batch_step_tail(const mpcd_system_desc &d, const float *umin_host, const float *umax_host,
                                   const BatchStepTail &t, hipStream_t stream);
+// Elite sets (elite.hip). launch_topk: out[m][0..k) = the k best of cost[m * group, (m + 1) * group), best first, in
+// rollout.hip's better() order, index = offset + position in cost[]; 1 <= k <= min(group, MPCD_MAX_ELITES).
+// mirror (n_groups == 1 only): the entries also written to mapped host memory, then *host_flag = host_seq after a
+// system-scope fence, as RolloutSelect's result block is.
+struct TopkMirror {
+    mpcd_best *host_out;
+    uint32_t *host_flag;
+    uint32_t host_seq;
+};
+hipError_t launch_topk(const double *cost, int64_t n_groups, int64_t group, int k, int64_t offset, mpcd_best *out,
+                       hipStream_t stream, const TopkMirror *mirror = nullptr);
+// out[m * group + j][h] = rows[elites[m][j % k].index - offset][min(h + shift, H - 1)]; rows / out [n_groups * group][H][d]
+hipError_t launch_elite_priors(const float *rows, int64_t n_groups, int64_t group, int H, int d, const mpcd_best *elites,
+                               int k, int64_t offset, int shift, float *out, hipStream_t stream);
 // out[r * n + j][:] = rows[r][:] for j < n (the per-candidate rows of iteration 0 when the loop is not grouped)
 hipError_t launch_repeat_rows(const float *rows, int64_t n_rows, int64_t n, int row_len, float *out, hipStream_t stream);

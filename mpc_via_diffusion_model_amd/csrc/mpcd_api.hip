@@ -299,6 +299,7 @@ struct mpcd_ctx {
     // mpcd_mpc_step: device context row, per-block argmin partials, {best, winner row} result block
     // and its pinned host mirror (one D2H copy per control step)
     DevBuf step_ctx, step_part, step_out, step_amax;
+    DevBuf step_elite;  // mpcd_mpc_step_elite: the k elites on the device, mpcd_best [MPCD_MAX_ELITES]
     // mpcd_closed_loop: partials, samples, chain maxima, context rows and priors; one self-resetting counter per state
     DevBuf loop_ws, loop_cnt;
     // mpcd_mpc_step_batch: the same kinds of parts plus the states and the packed result block; its own self-resetting
@@ -631,7 +632,7 @@ void mpcd_destroy(mpcd_ctx *c)
     if (!c) return;
     DeviceGuard device_guard_(c->device);
     for (DevBuf *b : {&c->params, &c->wpack, &c->wpack3, &c->wpackh, &c->cond_layers, &c->unet_pack, &c->plan, &c->tproj, &c->cproj, &c->flag,
-                      &c->unet_ws, &c->step_ctx, &c->step_part, &c->step_out, &c->step_amax, &c->loop_ws, &c->loop_cnt,
+                      &c->unet_ws, &c->step_ctx, &c->step_part, &c->step_out, &c->step_amax, &c->step_elite, &c->loop_ws, &c->loop_cnt,
                       &c->batch_ws, &c->batch_cnt})
         b->release();
     for (int i = 0; i < mpcd_ctx::kEvRing; ++i)
@@ -1504,6 +1505,42 @@ int mpcd_argmin(mpcd_ctx *c, const double *cost, int64_t n, int64_t offset, mpcd
     return MPCD_OK;
 }
 
+static int check_elite_k(const char *fn, int64_t n_groups, int64_t group, int32_t k)
+{
+    if (n_groups < 1 || n_groups > INT32_MAX || group < 1)
+        return fail(MPCD_EINVAL, "%s: n_groups %lld / group %lld", fn, (long long)n_groups, (long long)group);
+    if (k < 1 || k > group || k > MPCD_MAX_ELITES)
+        return fail(MPCD_EINVAL, "%s: k %d outside [1, min(group %lld, %d)]", fn, k, (long long)group, MPCD_MAX_ELITES);
+    return MPCD_OK;
+}
+
+int mpcd_topk(mpcd_ctx *c, const double *cost, int64_t n_groups, int64_t group, int32_t k, int64_t offset,
+              mpcd_best *out_dev, void *stream_ptr)
+{
+    if (!c || !cost || !out_dev) return fail(MPCD_EINVAL, "null argument");
+    if (int rc = check_elite_k("mpcd_topk", n_groups, group, k)) return rc;
+    DEVICE_GUARD(c->device);
+    HIP_TRY(launch_topk(cost, n_groups, group, k, offset, out_dev, static_cast<hipStream_t>(stream_ptr)));
+    return MPCD_OK;
+}
+
+int mpcd_elite_priors(mpcd_ctx *c, const float *u_norm, int64_t n_groups, int64_t group, int32_t horizon,
+                      const mpcd_best *elites_dev, int32_t k, int64_t offset, int32_t shift, float *out, void *stream_ptr)
+{
+    if (!c || !u_norm || !elites_dev || !out) return fail(MPCD_EINVAL, "null argument");
+    if (!c->net_loaded) return fail(MPCD_ESTATE, "no net loaded");
+    if (int rc = check_elite_k("mpcd_elite_priors", n_groups, group, k)) return rc;
+    if (shift != 0 && shift != 1) return fail(MPCD_EINVAL, "mpcd_elite_priors: shift %d is neither 0 nor 1", shift);
+    if (horizon != c->desc.horizon)
+        return fail(MPCD_EINVAL, "mpcd_elite_priors: horizon %d != the net's %d", horizon, c->desc.horizon);
+    const size_t n = (size_t)n_groups * group * horizon * c->desc.state_dim;
+    if (out < u_norm + n && u_norm < out + n) return fail(MPCD_EINVAL, "mpcd_elite_priors: out overlaps u_norm");
+    DEVICE_GUARD(c->device);
+    HIP_TRY(launch_elite_priors(u_norm, n_groups, group, horizon, c->desc.state_dim, elites_dev, k, offset, shift, out,
+                                static_cast<hipStream_t>(stream_ptr)));
+    return MPCD_OK;
+}
+
 // ---- candidate-batch data parallelism over RCCL
 
 int mpcd_comm_unique_id(void *id_out)
@@ -1610,27 +1647,36 @@ int mpcd_select(mpcd_ctx *c, const double *cost_local, int64_t n_local, const fl
     return comm_reduce(c, row_out, (size_t)row_len, COMM_SUM_F32, st);
 }
 
-// WARM (mpcd_mpc_step_warm): the sampler call takes the resolved warm start and, next_init_out non-null, one
-// shift_plan launch on the winner follows the selection. A template flag: mpcd_mpc_step's instantiation compiles the
-// code it had, with no branch on either.
+// STEP_WARM (mpcd_mpc_step_warm): the sampler call takes the resolved warm start and, next_init_out non-null, one
+// shift_plan launch on the winner follows the selection. STEP_ELITE (mpcd_mpc_step_elite): the warm sampler call, then
+// the top-k launch over cost_local and the elite-prior launch into next_init_out ([batch][H][d] here); the call waits
+// for the top-k launch's completion word. A template value: mpcd_mpc_step's and mpcd_mpc_step_warm's instantiations
+// compile the code they had, with no branch on any of it.
+enum { STEP_COLD = 0, STEP_WARM = 1, STEP_ELITE = 2 };
+struct EliteArgs {
+    int32_t k;
+    mpcd_best *elites_host;  // [k] or null
+};
 extern "C++" {  // templates cannot have C linkage
-template <bool WARM>
+template <int MODE>
 static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream,
-                         const WarmArgs *warm = nullptr, float *next_init_out = nullptr);
+                         const WarmArgs *warm = nullptr, float *next_init_out = nullptr,
+                         const EliteArgs *elite = nullptr);
 
 // An MPCD_F16X2 net computes in the fp16 range: a step whose sampled trajectories came back with a NaN (an
 // activation beyond 65504 turns into one: hi = inf, lo = inf - inf) or with no finite cost is re-run with the net's
 // split-bf16 (MPCD_F32X3) programs and flagged MPCD_STEP_F32X3_RERUN. Single rank only: with a communicator every
 // rank would have to agree to re-run (the flag and the ENONFINITE return report it there).
-template <bool WARM>
+template <int MODE>
 static int mpc_step_rerun(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream,
-                          const WarmArgs *warm = nullptr, float *next_init_out = nullptr)
+                          const WarmArgs *warm = nullptr, float *next_init_out = nullptr,
+                          const EliteArgs *elite = nullptr)
 {
-    int rc = mpc_step_impl<WARM>(c, a, best_host, u_best_host, stream, warm, next_init_out);
+    int rc = mpc_step_impl<MODE>(c, a, best_host, u_best_host, stream, warm, next_init_out, elite);
     const bool f16x2 = c && c->net_loaded && c->desc.dtype == MPCD_F16X2 && !c->force_x3;
     if (f16x2 && !c->comm && (rc == MPCD_ENONFINITE || (rc == MPCD_OK && (c->step_flags & MPCD_STEP_NAN_SAMPLES)))) {
         c->force_x3 = c->unet.force3 = true;
-        rc = mpc_step_impl<WARM>(c, a, best_host, u_best_host, stream, warm, next_init_out);
+        rc = mpc_step_impl<MODE>(c, a, best_host, u_best_host, stream, warm, next_init_out, elite);
         c->force_x3 = c->unet.force3 = false;
         c->step_flags |= MPCD_STEP_F32X3_RERUN;
     }
@@ -1640,7 +1686,7 @@ static int mpc_step_rerun(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_
 
 int mpcd_mpc_step(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream)
 {
-    return mpc_step_rerun<false>(c, a, best_host, u_best_host, stream);
+    return mpc_step_rerun<STEP_COLD>(c, a, best_host, u_best_host, stream);
 }
 
 int mpcd_mpc_step_warm(mpcd_ctx *c, const mpcd_step_args *a, const mpcd_warm_start *warm, float *next_init_out,
@@ -1655,14 +1701,42 @@ int mpcd_mpc_step_warm(mpcd_ctx *c, const mpcd_step_args *a, const mpcd_warm_sta
         return fail(MPCD_EINVAL, "mpcd_mpc_step_warm: next_init_out aliases warm->x_init");
     WarmArgs w;
     if (int rc = resolve_warm(c, &a->sample, 0, warm, w)) return rc;
-    return mpc_step_rerun<true>(c, a, best_host, u_best_host, stream, &w, next_init_out);
+    return mpc_step_rerun<STEP_WARM>(c, a, best_host, u_best_host, stream, &w, next_init_out);
+}
+
+int mpcd_mpc_step_elite(mpcd_ctx *c, const mpcd_step_args *a, const mpcd_warm_start *warm, int32_t k,
+                        float *next_priors_out, mpcd_best *elites_host, mpcd_best *best_host, float *u_best_host,
+                        void *stream)
+{
+    if (!c || !a || !warm) return fail(MPCD_EINVAL, "null argument");
+    if (c->comm)
+        return fail(MPCD_EUNSUP, "mpcd_mpc_step_elite: single-rank only (the elite rows live on other ranks)");
+    const int64_t B = a->sample.batch;
+    if (k < 1 || k > B || k > MPCD_MAX_ELITES)
+        return fail(MPCD_EINVAL, "mpcd_mpc_step_elite: k %d outside [1, min(batch %lld, %d)]", k, (long long)B,
+                    MPCD_MAX_ELITES);
+    if (warm->t_start > 0 && warm->rows != 1 && warm->rows != B)
+        return fail(MPCD_EINVAL, "mpcd_mpc_step_elite: one prior (rows == 1) or one per candidate (rows == batch %lld), not "
+                                 "%lld rows", (long long)B, (long long)warm->rows);
+    // the re-run of an MPCD_F16X2 step reads the priors again: the next priors must not have replaced them
+    if (next_priors_out && warm->t_start > 0 && warm->x_init && c->net_loaded) {
+        const size_t row = (size_t)c->desc.horizon * c->desc.state_dim;
+        const float *in_end = warm->x_init + (size_t)warm->rows * row, *out_end = next_priors_out + (size_t)B * row;
+        if (next_priors_out < in_end && warm->x_init < out_end)
+            return fail(MPCD_EINVAL, "mpcd_mpc_step_elite: next_priors_out aliases warm->x_init");
+    }
+    WarmArgs w;
+    if (int rc = resolve_warm(c, &a->sample, 0, warm, w)) return rc;
+    const EliteArgs e{k, elites_host};
+    return mpc_step_rerun<STEP_ELITE>(c, a, best_host, u_best_host, stream, &w, next_priors_out, &e);
 }
 
 extern "C++" {
-template <bool WARM>
+template <int MODE>
 static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream,
-                         const WarmArgs *warm, float *next_init_out)
+                         const WarmArgs *warm, float *next_init_out, const EliteArgs *elite)
 {
+    constexpr bool WARM = MODE == STEP_WARM, ELITE = MODE == STEP_ELITE;
     if (!c || !a || !a->sys || !a->x0 || !a->act_min || !a->act_max || !a->cost_local || !best_host || !u_best_host)
         return fail(MPCD_EINVAL, "null argument");
     if (!c->net_loaded) return fail(MPCD_ESTATE, "no net loaded");
@@ -1685,7 +1759,9 @@ static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_h
     // result block: {best, winner row [row] fp32, clip code int32} - one D2H copy
     const size_t out_bytes = sizeof(mpcd_best) + sizeof(float) * (size_t)row + sizeof(int32_t);
     const size_t flag_off = 64 + ((out_bytes + 63) & ~(size_t)63);  // the completion word, own 64-byte line
-    const size_t host_bytes = flag_off + 64;
+    // STEP_ELITE: [the k elites, MPCD_MAX_ELITES entries | the top-k launch's completion word] follow
+    const size_t elite_off = flag_off + 64, elite_flag_off = elite_off + sizeof(mpcd_best) * MPCD_MAX_ELITES;
+    const size_t host_bytes = ELITE ? elite_flag_off + 64 : flag_off + 64;
     if (c->step_host_bytes < host_bytes) {
         if (c->step_host) (void)hipHostFree(c->step_host);
         c->step_host = nullptr;
@@ -1725,7 +1801,15 @@ static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_h
         if ((rc = c->step_amax.ensure(sizeof(float) * (size_t)B))) return rc;
         sa.chain_absmax = c->step_amax.as<float>();
     }
-    if constexpr (WARM) {
+    if constexpr (ELITE) {
+        if (next_init_out) {  // the elite-prior launch reads x_out and writes next_init_out
+            const float *x_end = sa.x_out + (size_t)B * row, *o_end = next_init_out + (size_t)B * row;
+            if (next_init_out < x_end && sa.x_out < o_end)
+                return fail(MPCD_EINVAL, "mpcd_mpc_step_elite: next_priors_out overlaps sample.x_out");
+        }
+        if ((rc = c->step_elite.ensure(sizeof(mpcd_best) * MPCD_MAX_ELITES))) return rc;
+    }
+    if constexpr (WARM || ELITE) {
         if ((rc = sample_impl(c, &sa, stream, by_value ? &ctx_row : nullptr, 0, warm))) return rc;
     } else {
         if ((rc = sample_impl(c, &sa, stream, by_value ? &ctx_row : nullptr))) return rc;
@@ -1754,7 +1838,8 @@ static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_h
     int64_t *part_idx = reinterpret_cast<int64_t *>(part_cost + n_part);
     int32_t *code_dev = reinterpret_cast<int32_t *>(u_dev + row);
     void *host_out = static_cast<char *>(c->step_host) + 64;
-    volatile uint32_t *host_flag = reinterpret_cast<volatile uint32_t *>(static_cast<char *>(c->step_host) + flag_off);
+    volatile uint32_t *host_flag =
+        reinterpret_cast<volatile uint32_t *>(static_cast<char *>(c->step_host) + (ELITE ? elite_flag_off : flag_off));
     uint32_t seq = 0;
     if (!c->comm) {  // rollout + cost + argmin + the winner's unnormalised row + the clip code in one launch
         seq = ++c->step_seq;
@@ -1788,6 +1873,18 @@ static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_h
                                            next_init_out, st));
         }
     }
+    if constexpr (ELITE) {
+        // the k best of cost_local, ranked (entry 0 = the selection above), mirrored to mapped host memory with a
+        // completion word of their own, which the wait below takes instead of the rollout launch's: it follows that
+        // launch on the stream, so the result block is complete too. Then every candidate's next prior.
+        char *hdev = static_cast<char *>(c->step_host_dev);
+        const TopkMirror mir{reinterpret_cast<mpcd_best *>(hdev + elite_off),
+                             reinterpret_cast<uint32_t *>(hdev + elite_flag_off), seq};
+        HIP_TRY(launch_topk(a->cost_local, 1, B, elite->k, sa.global_offset, c->step_elite.as<mpcd_best>(), st, &mir));
+        if (next_init_out)
+            HIP_TRY(launch_elite_priors(sa.x_out, 1, B, H, d.state_dim, c->step_elite.as<mpcd_best>(), elite->k,
+                                        sa.global_offset, 1, next_init_out, st));
+    }
     if (c->comm) {
         HIP_TRY(hipMemcpyAsync(host_out, c->step_out.p, out_bytes, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -1814,6 +1911,10 @@ static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_h
     memcpy(u_best_host, static_cast<char *>(host_out) + sizeof(mpcd_best), sizeof(float) * (size_t)row);
     int32_t code = 0;
     memcpy(&code, static_cast<char *>(host_out) + sizeof(mpcd_best) + sizeof(float) * (size_t)row, sizeof code);
+    if constexpr (ELITE) {
+        if (elite->elites_host)
+            memcpy(elite->elites_host, static_cast<char *>(c->step_host) + elite_off, sizeof(mpcd_best) * elite->k);
+    }
     c->step_flags = (code == 1 ? MPCD_STEP_CLIPPED : 0) | (code == 2 ? MPCD_STEP_NAN_SAMPLES : 0);
     if (!std::isfinite(best_host->cost)) {
         c->step_flags |= MPCD_STEP_NONFINITE_WINNER;

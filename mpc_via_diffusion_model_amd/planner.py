@@ -112,6 +112,8 @@ class MPCResult:
     costs: torch.Tensor     # [B_total] fp64 on device (all ranks' candidates)
     u_norm: torch.Tensor    # [B_local, H, d] this rank's normalised samples
     flags: int = 0          # mpcd_last_step_flags bits (native step): 1 clipped, 2 NaN in the samples
+    elite_index: np.ndarray = None  # [k] int64 global indices of the k best candidates, best first (elites=k)
+    elite_cost: np.ndarray = None   # [k] fp64 their costs, nondecreasing (a NaN cost is reported as +inf)
 
 
 @dataclass
@@ -134,6 +136,7 @@ class BatchStepResult:
 
 
 _STATE_RESULT = np.dtype([("cost", "<f8"), ("index", "<i8"), ("flags", "<i4"), ("reserved", "<i4")])
+_BEST = np.dtype([("cost", "<f8"), ("index", "<i8")])  # mpcd_best
 
 
 class DiffusionMPC:
@@ -540,9 +543,72 @@ class DiffusionMPC:
         host = self._best.cpu()
         return int(host.view(torch.int64)[1]), float(host[0])
 
+    def _check_elites(self, k, group):
+        k = int(k)
+        if k < 1 or k > group or k > N.MPCD_MAX_ELITES:
+            raise ValueError(f"elites / k = {k} must be in [1, min({group} candidates, {N.MPCD_MAX_ELITES})]")
+        return k
+
+    def _topk_raw(self, cost, k, n_groups, index_offset=0):
+        """mpcd_topk into a fresh device buffer of mpcd_best records, viewed as int64 [n_groups, k, 2] (cost bits, index)."""
+        if cost.dtype != torch.float64 or cost.device != self.device or not cost.is_contiguous():
+            raise ValueError(f"cost must be a contiguous float64 tensor on {self.device}")
+        M = int(n_groups)
+        if M < 1 or cost.numel() < 1 or cost.numel() % M != 0:
+            raise ValueError(f"cost has {cost.numel()} entries: not n_groups={M} groups of equal size")
+        group = cost.numel() // M
+        k = self._check_elites(k, group)
+        raw = torch.empty((M, k, 2), dtype=torch.int64, device=self.device)
+        N.check(self._lib.mpcd_topk(self._ctx, ctypes.c_void_p(cost.data_ptr()), M, group, k, int(index_offset),
+                                    ctypes.c_void_p(raw.data_ptr()), self._stream()), "mpcd_topk")
+        return raw
+
+    def topk(self, cost, k, n_groups=1, index_offset=0):
+        """The k best candidates of each of n_groups equal groups of consecutive costs, ranked on the device (mpcd_topk):
+        (cost [M, k] float64, index [M, k] int64) device tensors, best first, in argmin()'s order (NaN = +inf and
+        reported as +inf, lower cost, then lower index). index = index_offset + the position in `cost`, so [:, 0] is each
+        group's argmin / closed_loop's selected index. cost: device float64 [M * group]; 1 <= k <= min(group, 64)."""
+        raw = self._topk_raw(cost, k, n_groups, index_offset)
+        return raw[..., 0].contiguous().view(torch.float64), raw[..., 1].contiguous()
+
+    def elite_priors(self, u_norm, elite_index, group, shift=True, index_offset=0, out=None):
+        """Per-candidate warm-start priors seeded from elite sets (mpcd_elite_priors): for candidate b = m * group + j,
+        out[b, h] = u_norm[elite_index[m, j % k] - index_offset, min(h + shift, H - 1)]. shift=True moves each plan one
+        horizon point ahead (shift_plans' rule, for the next control step); shift=False copies it (re-sampling within
+        one step). u_norm [M * group, H, d] device fp32; elite_index [M, k] device int64 (topk's index). An index outside
+        [index_offset, index_offset + M * group) leaves its candidates' rows of `out` as they are. Returns out
+        [M * group, H, d], which must not overlap u_norm; hand it to sample_trajectories(x_init=out, t_start=K)."""
+        B, H, d = u_norm.shape
+        u_norm = u_norm.contiguous()
+        group = int(group)
+        if elite_index.dim() == 1:
+            elite_index = elite_index[None]
+        if elite_index.dtype != torch.int64 or elite_index.device != self.device or elite_index.dim() != 2:
+            raise ValueError(f"elite_index must be an int64 [M, k] tensor on {self.device}")
+        M, k = elite_index.shape
+        if group < 1 or M * group != B:
+            raise ValueError(f"u_norm has {B} rows: not {M} states x group={group}")
+        self._check_elites(k, group)
+        raw = torch.zeros((M, k, 2), dtype=torch.int64, device=self.device)
+        raw[..., 1] = elite_index
+        return self._elite_priors_raw(u_norm, raw, group, shift, index_offset, out)
+
+    def _elite_priors_raw(self, u_norm, raw, group, shift, index_offset, out):
+        B, H, d = u_norm.shape
+        if out is None:
+            out = torch.empty((B, H, d), dtype=torch.float32, device=self.device)
+        elif (tuple(out.shape) != (B, H, d) or out.dtype != torch.float32 or out.device != self.device
+              or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous fp32 [{B}, {H}, {d}] tensor on {self.device}")
+        N.check(self._lib.mpcd_elite_priors(self._ctx, ctypes.c_void_p(u_norm.data_ptr()), raw.shape[0], group, H,
+                                            ctypes.c_void_p(raw.data_ptr()), raw.shape[1], int(index_offset),
+                                            1 if shift else 0, ctypes.c_void_p(out.data_ptr()), self._stream()),
+                "mpcd_elite_priors")
+        return out
+
     def closed_loop(self, x0_states, system: System, iterations, n_samples=1, w=0.01, sample_fn="ddpm_cfg",
                     n_wo_noise=0, ddim_steps=None, clamp_x0=False, select="argmin", decimals=4, seed=0, noise=None,
-                    clip_rule="chain", grouped=False, warm_start=None, native=False):
+                    clip_rule="chain", grouped=False, warm_start=None, native=False, elites=None):
         """Closed-loop diffusion MPC for M plant states at once, resident on the device.
         The reference runs one initial state at a time on the host (Cart_Diffusion_inference.py:405-512:
         normalize_condition -> run_CFG -> unnormalize -> u0 = round(u[0], 4) -> x = f(x, u0), repeated
@@ -573,8 +639,22 @@ class DiffusionMPC:
         with results bit for bit those of native=False (the default, the composed calls above). noise(it) is then
         evaluated for every iteration up front, and the result's u_norm holds the last iteration's samples. An f16x2
         spec raises ValueError: its range guard reads the chain maxima on the host in every iteration, the round trip
-        the native loop removes."""
+        the native loop removes.
+        elites=k (with warm_start, select="argmin", native=False; 1 <= k <= min(n_samples, 64)): after every control
+        step each state's k best plans are ranked on the device (mpcd_topk) and candidate j of the state is seeded from
+        elite j % k, moved one horizon point ahead (mpcd_elite_priors): the next iteration samples from [M * n, H, d]
+        priors, one per candidate, instead of one per state. elites=1 computes what warm_start alone computes. The
+        fused tail of native=True writes one prior per state: elites there raises ValueError."""
         K = None if warm_start is None else int(warm_start)
+        if elites is not None:
+            if K is None:
+                raise ValueError("elites needs warm_start=K: the elite set seeds the warm-start priors")
+            if native:
+                raise ValueError("elites is not available with native=True: mpcd_closed_loop's fused tail writes one "
+                                 "prior per state; use native=False")
+            if select != "argmin":
+                raise ValueError("elites ranks candidates by cost: it needs select='argmin'")
+            elites = self._check_elites(elites, int(n_samples))
         if K is not None and (K < 1 or K > self.n_steps or self._sampler_id(sample_fn) != N.MPCD_DDPM_CFG):
             raise ValueError(f"warm_start={K} needs 1 <= K <= {self.n_steps} and the CFG-DDPM sampler")
         if select not in ("argmin", "first"):
@@ -606,12 +686,17 @@ class DiffusionMPC:
         absmax = torch.empty(B, dtype=torch.float32, device=dev) if clip_rule == "chain" else None
         ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         grouped = bool(grouped) and self.grouped_pays(M, n, sample_fn)
-        priors = torch.empty((M, H, d), dtype=torch.float32, device=dev) if K is not None else None
+        priors = None
+        if K is not None:  # one prior per state, or (elites) one per candidate
+            priors = torch.empty((M if elites is None else B, H, d), dtype=torch.float32, device=dev)
         xs[0] = x
         for it in range(T):
             warm = {}
             if K is not None and it > 0:
-                warm = dict(x_init=priors if grouped else priors.repeat_interleave(n, dim=0), t_start=K)
+                if elites is not None:
+                    warm = dict(x_init=priors, t_start=K)
+                else:
+                    warm = dict(x_init=priors if grouped else priors.repeat_interleave(n, dim=0), t_start=K)
             N.check(self._lib.mpcd_normalize_states(self._ctx, ptr(x), M, nx, self.ctx_min.ctypes.data,
                                                     self.ctx_max.ctypes.data, ptr(ctx), st), "mpcd_normalize_states")
             self.sample_trajectories(ctx if grouped else ctx.repeat_interleave(n, dim=0), B, H, w, sample_fn, n_wo_noise,
@@ -628,7 +713,9 @@ class DiffusionMPC:
                                                 self.act_min.ctypes.data, self.act_max.ctypes.data, ptr(flags),
                                                 1 if select == "first" else 0, -1 if decimals is None else int(decimals),
                                                 ptr(us[it]), ptr(ix[it]), ptr(cs[it]), st), "mpcd_control_step")
-            if K is not None:
+            if elites is not None:
+                self._elite_priors_raw(u_norm, self._topk_raw(cost, elites, M), n, True, 0, priors)
+            elif K is not None:
                 self.shift_plans(u_norm, ix[it], 0, out=priors)
             xs[it + 1] = x
         return ClosedLoopResult(x=xs.transpose(0, 1).cpu().numpy(), u=us.transpose(0, 1).cpu().numpy(),
@@ -841,7 +928,7 @@ class DiffusionMPC:
 
     def mpc_step(self, x0, system: System, n_samples, w=0.01, sample_fn="ddpm_cfg", n_wo_noise=0, ddim_steps=None,
                  clamp_x0=False, seed=0, noise=None, group=None, comm=None, native=None, clip_rule="chain",
-                 warm_start=None, prior=None):
+                 warm_start=None, prior=None, elites=None):
         """One control step: sample n_samples candidates on this rank (weak scaling: every rank adds
         n_samples), roll out + cost them, all-gather costs, pick the global argmin, broadcast it.
         comm: a distributed.NativeComm (the exchange inside libmpcd.so over RCCL) or None
@@ -860,7 +947,15 @@ class DiffusionMPC:
         K steps from the prior noised to level K (noise then has K + n_wo_noise + 1 slices) and refresh it.
         reset_warm_start() drops the prior (a new episode); prior= (normalised [H, d]) overrides it for this call.
         Under clip_rule="chain" a warm step's test sees the noised prior instead of x_T, so the clip is no longer
-        practically certain. What K costs in control quality depends on the model: measure it."""
+        practically certain. What K costs in control quality depends on the model: measure it.
+        elites=k (with warm_start=K, the native single-rank step; 1 <= k <= min(n_samples, 64); mpcd_mpc_step_elite):
+        the planner keeps one prior per candidate, [n_samples, H, d]: after the selection the k best plans are ranked on
+        the device and candidate j's next prior is elite j % k's plan moved one horizon point ahead, so a small K keeps
+        k modes instead of one. The result carries elite_index / elite_cost (host arrays, best first; entry 0 is the
+        winner) and warm_prior() returns row 0, the best plan shifted. A stored prior of one row (from a call without
+        elites) seeds every candidate; prior= may be [H, d] or [n_samples, H, d]. elites=1 computes what warm_start
+        alone computes. ValueError: elites without warm_start, with native=False or on several ranks, or stored priors
+        whose row count is neither 1 nor n_samples (call reset_warm_start() after changing n_samples)."""
         if clip_rule not in _CLIP_RULES:
             raise ValueError(f"clip_rule must be one of {sorted(_CLIP_RULES)}")
         if comm is not None:
@@ -869,11 +964,18 @@ class DiffusionMPC:
             rank, size = D.world(group)
         if native is None:
             native = comm is not None or size == 1
+        if elites is not None:
+            if warm_start is None:
+                raise ValueError("elites needs warm_start=K: the elite set seeds the warm-start priors")
+            if not native:
+                raise ValueError("elites needs the native step (native=True)")
+            if comm is not None or size > 1:
+                raise ValueError("elites is single-rank: the elite rows live on other ranks (no comm / process group)")
         if native:
             if size > 1 and comm is None:
                 raise ValueError("native mpc_step on several ranks needs a NativeComm")
             return self._mpc_step_native(x0, system, n_samples, w, sample_fn, n_wo_noise, ddim_steps, clamp_x0, seed,
-                                         noise, comm, clip_rule, warm_start, prior)
+                                         noise, comm, clip_rule, warm_start, prior, elites)
         if warm_start is not None or prior is not None:
             raise ValueError("warm_start / prior need the native step (native=True)")
         offset = rank * n_samples
@@ -913,7 +1015,7 @@ class DiffusionMPC:
         return None if p is None else p[0]
 
     def _mpc_step_native(self, x0, system, n_samples, w, sample_fn, n_wo_noise, ddim_steps, clamp_x0, seed, noise,
-                         comm, clip_rule="chain", warm_start=None, prior=None):
+                         comm, clip_rule="chain", warm_start=None, prior=None, elites=None):
         """mpc_step as one libmpcd call (mpcd_mpc_step): one H2D copy of the context row, the kernels,
         the result block {best, u_best} written to pinned host memory by the selecting workgroup (one rank) or one
         D2H copy + stream synchronisation (with a communicator)."""
@@ -927,15 +1029,21 @@ class DiffusionMPC:
             K = int(warm_start) if warm_start is not None else 0
             if K < 1 or K > self.n_steps or sampler != N.MPCD_DDPM_CFG:
                 raise ValueError(f"warm_start={warm_start} needs 1 <= K <= {self.n_steps} and the CFG-DDPM sampler")
+            if elites is not None:
+                elites = self._check_elites(elites, B)
             if prior is None:
                 prior = getattr(self, "_prior", None)
+                if elites is not None and prior is not None and prior.shape[0] not in (1, B):
+                    raise ValueError(f"the stored priors have {prior.shape[0]} rows, neither 1 nor n_samples={B}: call "
+                                     "reset_warm_start() after changing n_samples")
             # no prior yet: a cold step (t_start 0) that fills it
             warm, prior = self._warm(prior, K if prior is not None else 0, B)
-            if prior is not None and prior.shape[0] != 1:
+            if elites is None and prior is not None and prior.shape[0] != 1:
                 raise ValueError(f"prior must be one plan [{H}, {d}], got {tuple(prior.shape)}")
+            rows = 1 if elites is None else B  # the next priors: the winner's plan, or one per candidate
             nxt = getattr(self, "_prior_spare", None)
-            if nxt is None or (prior is not None and nxt.data_ptr() == prior.data_ptr()):
-                nxt = torch.empty((1, H, d), dtype=torch.float32, device=self.device)
+            if nxt is None or nxt.shape[0] != rows or (prior is not None and nxt.data_ptr() == prior.data_ptr()):
+                nxt = torch.empty((rows, H, d), dtype=torch.float32, device=self.device)
         if noise is not None:
             steps = self.n_denoise_steps(sample_fn, n_wo_noise, ddim_steps, warm.t_start or None if warm else None)
             noise = noise.to(self.device, torch.float32).contiguous()
@@ -974,9 +1082,17 @@ class DiffusionMPC:
         a.costs_all = costs.data_ptr()
         u_best = np.empty((H, d), dtype=np.float32)
         # MPCD_ENONFINITE (no candidate with a finite cost: NaN / Inf samples) raises MpcdError here
+        el = None
         if warm is None:
             N.check(self._lib.mpcd_mpc_step(self._ctx, a_ref, ctypes.byref(best), u_best.__array_interface__["data"][0],
                                             self._stream()), "mpcd_mpc_step")
+        elif elites is not None:
+            el = np.empty(elites, dtype=_BEST)
+            N.check(self._lib.mpcd_mpc_step_elite(self._ctx, a_ref, ctypes.byref(warm), elites,
+                                                  ctypes.c_void_p(nxt.data_ptr()), el.ctypes.data, ctypes.byref(best),
+                                                  u_best.__array_interface__["data"][0], self._stream()),
+                    "mpcd_mpc_step_elite")
+            self._prior, self._prior_spare = nxt, getattr(self, "_prior", None)
         else:
             N.check(self._lib.mpcd_mpc_step_warm(self._ctx, a_ref, ctypes.byref(warm), ctypes.c_void_p(nxt.data_ptr()),
                                                  ctypes.byref(best), u_best.__array_interface__["data"][0],
@@ -985,4 +1101,5 @@ class DiffusionMPC:
             self._prior, self._prior_spare = nxt, getattr(self, "_prior", None)
         N.check(self._lib.mpcd_last_step_flags(self._ctx, ctypes.byref(fl)), "mpcd_last_step_flags")
         return MPCResult(u0=u_best[0].copy(), u_best=u_best, best_cost=best.cost, best_index=best.index, costs=costs,
-                         u_norm=u_norm, flags=fl.value)
+                         u_norm=u_norm, flags=fl.value, elite_index=None if el is None else el["index"].copy(),
+                         elite_cost=None if el is None else el["cost"].copy())
