@@ -416,6 +416,32 @@ typedef struct {
  * loop's; the per-state counters reset themselves. Like every context workspace it is ordered on ONE stream. */
 int mpcd_mpc_step_batch(mpcd_ctx *ctx, const mpcd_batch_step_args *args, void *hip_stream);
 
+/* mpcd_mpc_step_batch with elite sets: the same call - one state upload, the sampler, ONE tail launch
+ * (batch_step_elite_tail_kernel), one download, one synchronisation - that also ranks each state's k best candidates
+ * inside the tail (no cost array, no mpcd_topk launch) and keeps one warm-start prior per CANDIDATE: one
+ * mpcd_elite_priors(shift = 1) launch after the tail seeds candidate j of state m from the state's elite j mod k.
+ * Everything mpcd_mpc_step_batch returns is returned, computed the same way; elites_host[m][0..k) is bit for bit
+ * mpcd_topk over mpcd_rollout_cost_grouped's costs of this step's samples (NaN reported as +inf, ties to the lower
+ * index, global indices m * group + j), so elites_host[m][0].index == result_host[m].index, while result_host[m].cost
+ * stays the cost as computed. A state without a finite cost gets k elites of cost +inf in index order and carries
+ * MPCD_STEP_NONFINITE_WINNER (the call returns MPCD_ENONFINITE as mpcd_mpc_step_batch does). With
+ * args->group_contexts == 0 the priors are not repeated: they are per candidate already.
+ * MPCD_EINVAL: mpcd_mpc_step_batch's cases; elite == NULL; k outside [1, min(args->group, MPCD_MAX_ELITES)];
+ * reserved != 0; args->select_first != 0 (ranking needs costs); args->priors != NULL (the per-state prior buffer has
+ * no meaning here); warm_t_start > 0 with elite->priors == NULL. MPCD_EUNSUP: mpcd_mpc_step_batch's cases. */
+typedef struct {
+    int32_t k;              /* elites per state: 1 <= k <= min(args->group, MPCD_MAX_ELITES) */
+    int32_t reserved;       /* 0 */
+    float *priors;          /* dev [M*group][H][d] or NULL: one prior per CANDIDATE (mpcd_warm_start.rows == batch, grouped or
+                               not). Read when warm_t_start > 0 (then required); when non-NULL overwritten, after the sampler
+                               has read it, with mpcd_elite_priors(shift = 1) of this step's samples and elites */
+    mpcd_best *elites_host; /* host [M][k] or NULL: each state's k best, best first, mpcd_topk's order and cost reporting */
+} mpcd_batch_elite_args;
+/* The partial ranked lists and the larger result block belong to the same context workspace as mpcd_mpc_step_batch's;
+ * the per-state counters are the same self-resetting ones. */
+int mpcd_mpc_step_batch_elite(mpcd_ctx *ctx, const mpcd_batch_step_args *args, const mpcd_batch_elite_args *elite,
+                              void *hip_stream);
+
 /* ---- Candidate-batch data parallelism over RCCL / xGMI. One process per GPU, one
  * communicator per context; rank r owns global candidates [r*B_local, (r+1)*B_local). The reference has
  * no distributed code: these entry points are new design, not replacements. */

@@ -89,6 +89,11 @@ class BatchStepArgs(ctypes.Structure):
                 ("u_norm", ctypes.c_void_p)]
 
 
+class BatchEliteArgs(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_int32), ("reserved", ctypes.c_int32), ("priors", ctypes.c_void_p),
+                ("elites_host", ctypes.c_void_p)]
+
+
 class TrainCfg(ctypes.Structure):
     _fields_ = [("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
                 ("ema_decay", ctypes.c_float), ("step_start_ema", ctypes.c_int32), ("update_ema_every", ctypes.c_int32)]
@@ -149,6 +154,8 @@ EXPORTS = {
                            ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "mpcd_closed_loop": ([ctypes.c_void_p, ctypes.POINTER(ClosedLoopArgs), ctypes.c_void_p], ctypes.c_int),
     "mpcd_mpc_step_batch": ([ctypes.c_void_p, ctypes.POINTER(BatchStepArgs), ctypes.c_void_p], ctypes.c_int),
+    "mpcd_mpc_step_batch_elite": ([ctypes.c_void_p, ctypes.POINTER(BatchStepArgs), ctypes.POINTER(BatchEliteArgs),
+                                   ctypes.c_void_p], ctypes.c_int),
     "mpcd_comm_unique_id": ([ctypes.c_void_p], ctypes.c_int),
     "mpcd_comm_init": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p], ctypes.c_int),
     "mpcd_philox_noise": ([ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,

@@ -209,6 +209,18 @@ struct BatchStepTail : TailCommon {
 constexpr int64_t batch_step_rec_stride(int n_u) { return (int64_t)sizeof(mpcd_state_result) + 8 * n_u; }
 hipError_t launch_batch_step_tail(const mpcd_system_desc &d, const float *umin_host, const float *umax_host,
                                   const BatchStepTail &t, hipStream_t stream);
+// The same step that also ranks each state's k best candidates (rollout.hip batch_step_elite_tail_kernel,
+// mpcd_mpc_step_batch_elite): the result block gains, at elite_off (256-byte aligned, after the plans), the elites
+// mpcd_best [n_states][k], best first in launch_topk's order and cost reporting. part_elite [n_states][ceil(group /
+// kRolloutBlock)][k] holds the workgroups' ranked lists. select_first must be 0; prior_out is not written: the next
+// priors are a launch_elite_priors on result + elite_off.
+struct BatchEliteTail : BatchStepTail {
+    mpcd_best *part_elite;
+    int64_t elite_off;
+    int32_t k;  // 1 <= k <= min(group, MPCD_MAX_ELITES)
+};
+hipError_t launch_batch_elite_tail(const mpcd_system_desc &d, const float *umin_host, const float *umax_host,
+                                   const BatchEliteTail &t, hipStream_t stream);
 // Elite sets (elite.hip). launch_topk: out[m][0..k) = the k best of cost[m * group, (m + 1) * group), best first, in
 // rollout.hip's better() order, index = offset + position in cost[]; 1 <= k <= min(group, MPCD_MAX_ELITES).
 // mirror (n_groups == 1 only): the entries also written to mapped host memory, then *host_flag = host_seq after a

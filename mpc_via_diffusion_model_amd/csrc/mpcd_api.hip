@@ -1384,20 +1384,36 @@ int mpcd_closed_loop(mpcd_ctx *c, const mpcd_closed_loop_args *a, void *stream_p
     return MPCD_OK;
 }
 
-int mpcd_mpc_step_batch(mpcd_ctx *c, const mpcd_batch_step_args *a, void *stream_ptr)
+// mpcd_mpc_step_batch and, ELITE, mpcd_mpc_step_batch_elite (e: its own arguments, else null): one host body. The
+// elite parts are compiled out of the plain call, which runs the statements it always ran.
+extern "C++" {
+template <bool ELITE>
+static int batch_step_impl(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpcd_batch_elite_args *e, void *stream_ptr)
 {
+    constexpr const char *fn = ELITE ? "mpcd_mpc_step_batch_elite" : "mpcd_mpc_step_batch";
     if (!c || !a) return fail(MPCD_EINVAL, "null argument");
+    if constexpr (ELITE) {
+        if (!e) return fail(MPCD_EINVAL, "%s: null argument (elite)", fn);
+    }
     if (!a->sys || !a->ctx_min || !a->ctx_max || !a->act_min || !a->act_max || !a->x_host || !a->result_host || !a->u_host)
-        return fail(MPCD_EINVAL, "mpcd_mpc_step_batch: null argument");
+        return fail(MPCD_EINVAL, "%s: null argument", fn);
     if (a->n_states < 1 || a->group < 1)
-        return fail(MPCD_EINVAL, "mpcd_mpc_step_batch: n_states %lld / group %lld < 1", (long long)a->n_states,
-                    (long long)a->group);
+        return fail(MPCD_EINVAL, "%s: n_states %lld / group %lld < 1", fn, (long long)a->n_states, (long long)a->group);
+    if constexpr (ELITE) {
+        if (e->k < 1 || e->k > a->group || e->k > MPCD_MAX_ELITES)
+            return fail(MPCD_EINVAL, "%s: k %d outside [1, min(group %lld, %d)]", fn, e->k, (long long)a->group,
+                        MPCD_MAX_ELITES);
+        if (e->reserved) return fail(MPCD_EINVAL, "%s: reserved %d != 0", fn, e->reserved);
+        if (a->select_first) return fail(MPCD_EINVAL, "%s: select_first != 0 (ranking the elites needs the costs)", fn);
+        if (a->priors)
+            return fail(MPCD_EINVAL, "%s: args->priors (one per state) has no meaning here: the priors are "
+                                     "elite->priors, one per candidate", fn);
+    }
     TailCall g;
-    int rc = check_tail_call(c, a, "mpcd_mpc_step_batch", "step",
-                             "and re-runs the sampler, a second round trip inside the step", g);
+    int rc = check_tail_call(c, a, fn, "step", "and re-runs the sampler, a second round trip inside the step", g);
     if (rc) return rc;
     mpcd_sample_args s;
-    if ((rc = tail_sample_args(c, a, "mpcd_mpc_step_batch", a->priors != nullptr, g.B, s))) return rc;
+    if ((rc = tail_sample_args(c, a, fn, (ELITE ? e->priors : a->priors) != nullptr, g.B, s))) return rc;
     const int nu = g.nu, nx = g.nx, row = g.row;
     const int64_t M = g.M, n = g.n, B = g.B;
     hipStream_t st = static_cast<hipStream_t>(stream_ptr);
@@ -1408,13 +1424,18 @@ int mpcd_mpc_step_batch(mpcd_ctx *c, const mpcd_batch_step_args *a, void *stream
     Carve carve;
     const int64_t rec_stride = batch_step_rec_stride(nu);
     const size_t plan_off = ((size_t)(M * rec_stride) + 255) & ~(size_t)255;
-    const size_t res_bytes = plan_off + sizeof(float) * M * row, x_bytes = sizeof(double) * M * nx;
-    const bool repeat_priors = a->warm_t_start > 0 && !g.grouped;
+    // ELITE: the elites mpcd_best [M][k] follow the plans
+    const int64_t k = ELITE ? e->k : 0;
+    const size_t elite_off = (plan_off + sizeof(float) * M * row + 255) & ~(size_t)255;
+    const size_t res_bytes = ELITE ? elite_off + sizeof(mpcd_best) * M * k : plan_off + sizeof(float) * M * row;
+    const size_t x_bytes = sizeof(double) * M * nx;
+    const bool repeat_priors = !ELITE && a->warm_t_start > 0 && !g.grouped;  // ELITE: one per candidate already
     const size_t o_x = carve(x_bytes), o_pc = carve(sizeof(double) * M * g.wps), o_pr = carve(sizeof(double) * M * g.wps),
                  o_pi = carve(sizeof(int64_t) * M * g.wps), o_res = carve(res_bytes), o_u = carve(sizeof(float) * B * row),
                  o_amax = carve(g.chain_rule ? sizeof(float) * B : 0), o_ctx = carve(sizeof(float) * g.rows * nx),
                  o_ctx0 = carve(g.grouped ? 0 : sizeof(float) * M * nx),
-                 o_prior = carve(repeat_priors ? sizeof(float) * B * row : 0);
+                 o_prior = carve(repeat_priors ? sizeof(float) * B * row : 0),
+                 o_pe = carve(sizeof(mpcd_best) * M * g.wps * k);  // ELITE: the workgroups' ranked lists
     if ((rc = c->batch_ws.ensure(carve.off))) return rc;
     if ((rc = grow_counters(c->batch_cnt, M, st))) return rc;
     const size_t h_res = (x_bytes + 255) & ~(size_t)255, host_bytes = h_res + res_bytes;
@@ -1439,26 +1460,36 @@ int mpcd_mpc_step_batch(mpcd_ctx *c, const mpcd_batch_step_args *a, void *stream
     s.chain_absmax = amax;
     WarmArgs warm;
     if (a->warm_t_start) {  // resolved as mpcd_closed_loop resolves it: [M] priors grouped, else one per candidate
-        const float *prior = a->priors;
+        const float *prior = ELITE ? e->priors : a->priors;
         if (repeat_priors) {
             float *rep = reinterpret_cast<float *>(w + o_prior);
             HIP_TRY(launch_repeat_rows(a->priors, M, n, row, rep, st));
             prior = rep;
         }
-        const mpcd_warm_start ws{prior, g.rows, a->warm_t_start};
+        const mpcd_warm_start ws{prior, ELITE ? B : g.rows, a->warm_t_start};
         if ((rc = resolve_warm(c, &s, g.grouped ? n : 0, &ws, warm))) return rc;
     }
     rc = sample_impl(c, &s, stream_ptr, nullptr, g.grouped ? n : 0, a->warm_t_start ? &warm : nullptr);
     if (rc) return rc;
 
-    BatchStepTail t{};
+    std::conditional_t<ELITE, BatchEliteTail, BatchStepTail> t{};
     fill_tail_common(t, g, u_norm, amax, x_dev, a->select_first, a->decimals, reinterpret_cast<double *>(w + o_pc),
                      reinterpret_cast<double *>(w + o_pr), reinterpret_cast<int64_t *>(w + o_pi), c->batch_cnt.as<unsigned>());
     t.result = w + o_res;
     t.rec_stride = rec_stride;
     t.plan_off = (int64_t)plan_off;
-    t.prior_out = a->priors;
-    HIP_TRY(launch_batch_step_tail(*a->sys, a->act_min, a->act_max, t, st));
+    if constexpr (ELITE) {
+        t.part_elite = reinterpret_cast<mpcd_best *>(w + o_pe);
+        t.elite_off = (int64_t)elite_off;
+        t.k = e->k;
+        HIP_TRY(launch_batch_elite_tail(*a->sys, a->act_min, a->act_max, t, st));
+        if (e->priors)  // the next priors, from the elites where the tail left them
+            HIP_TRY(launch_elite_priors(u_norm, M, n, g.H, nu, reinterpret_cast<const mpcd_best *>(w + o_res + elite_off),
+                                        e->k, 0, 1, e->priors, st));
+    } else {
+        t.prior_out = a->priors;
+        HIP_TRY(launch_batch_step_tail(*a->sys, a->act_min, a->act_max, t, st));
+    }
     if (a->u_norm) HIP_TRY(hipMemcpyAsync(a->u_norm, u_norm, sizeof(float) * B * row, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(hs + h_res, w + o_res, res_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -1473,11 +1504,25 @@ int mpcd_mpc_step_batch(mpcd_ctx *c, const mpcd_batch_step_args *a, void *stream
         }
     }
     if (a->plan_host) memcpy(a->plan_host, hs + h_res + plan_off, sizeof(float) * M * row);
+    if constexpr (ELITE) {
+        if (e->elites_host) memcpy(e->elites_host, hs + h_res + elite_off, sizeof(mpcd_best) * M * e->k);
+    }
     if (bad)
-        return fail(MPCD_ENONFINITE, "mpcd_mpc_step_batch: %lld of %lld states have no candidate with a finite cost "
+        return fail(MPCD_ENONFINITE, "%s: %lld of %lld states have no candidate with a finite cost "
                                      "(first: state %lld); the other states' results are valid",
-                    (long long)bad, (long long)M, (long long)first_bad);
+                    fn, (long long)bad, (long long)M, (long long)first_bad);
     return MPCD_OK;
+}
+}  // extern "C++"
+
+int mpcd_mpc_step_batch(mpcd_ctx *c, const mpcd_batch_step_args *a, void *stream_ptr)
+{
+    return batch_step_impl<false>(c, a, nullptr, stream_ptr);
+}
+
+int mpcd_mpc_step_batch_elite(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpcd_batch_elite_args *e, void *stream_ptr)
+{
+    return batch_step_impl<true>(c, a, e, stream_ptr);
 }
 
 int mpcd_unnormalize(mpcd_ctx *c, const float *x, int64_t n_rows, int32_t dim, const float *mn, const float *mx,

@@ -330,41 +330,125 @@ __device__ __forceinline__ int state_clip_code(const float *cs, int64_t n)
     return clip_code(blk);
 }
 
-// Cross-workgroup argmin: workgroup `slot` of `nslots` (one wave each) leaves its partial (v, i) - and raw, where
-// part_raw is not null - in part_*[slot] and counts itself on *counter; the last one to arrive reduces the nslots
-// partials. Returns whether this workgroup is that last one; if so (v, i) is the reduced winner in every lane
-// (i < 0: no entrant). *counter is zero between launches: the last workgroup puts it back.
+// The cross-workgroup hand-off, of which there is one copy: each of `nslots` one-wave workgroups leaves its partial
+// result in memory and counts itself on *counter; the last one to arrive reads them all. Lane 0 runs store0() (its
+// stores), fences and counts the workgroup; the last workgroup fences, runs reload() on every lane and puts the counter
+// back: *counter is zero between launches. Returns whether this workgroup is that last one.
 // Why it is sound: lane 0 stores the partials, __threadfence() makes them visible device-wide, and only then does its
 // atomicAdd count the workgroup. The workgroup whose add returns nslots - 1 therefore follows every other workgroup's
-// stores and fence; its own __threadfence() and the non-temporal reloads (which take no stale line of this CU's
-// cache) then read all nslots partials as written. The same order covers what a caller's partial depends on: a
-// partial is computed from the state the workgroup read (the tails' x_dev[m]), so every workgroup has finished
-// reading it before it counts itself, and the last workgroup may overwrite it (the closed loop's plant step).
-__device__ __forceinline__ bool last_arriver_argmin(double *part_cost, int64_t *part_idx, double *part_raw,
-                                                    unsigned *counter, int slot, int nslots, double &v, int64_t &i,
-                                                    double raw)
+// stores and fence; its own __threadfence() and non-temporal reloads (which take no stale line of this CU's cache)
+// then read all nslots partials as written. What the other lanes of a wave stored before the call (the elite tail's
+// ranked list) is covered the same way once they have fenced too: the wave's stores and fences precede lane 0's
+// atomicAdd in program order. The same order covers what a caller's partial depends on: a partial is computed from
+// the state the workgroup read (the tails' x_dev[m]), so every workgroup has finished reading it before it counts
+// itself, and the last workgroup may overwrite it (the closed loop's plant step).
+template <class Store0, class Reload>
+__device__ __forceinline__ bool last_arriver(unsigned *counter, int nslots, Store0 store0, Reload reload)
 {
     __shared__ bool last;
     if (threadIdx.x == 0) {
-        part_cost[slot] = v;
-        part_idx[slot] = i;
-        if (part_raw) part_raw[slot] = raw;
+        store0();
         __threadfence();
         last = atomicAdd(counter, 1u) == (unsigned)nslots - 1;
     }
     __syncthreads();
     if (!last) return false;
     __threadfence();
-    v = INFINITY;
-    i = -1;
-    for (int k = threadIdx.x; k < nslots; k += RT_THREADS) {
-        const double pv = __builtin_nontemporal_load(part_cost + k);
-        const int64_t pi = __builtin_nontemporal_load(part_idx + k);
-        if (better(pv, pi, v, i)) { v = pv; i = pi; }
-    }
-    wave_argmin(v, i);
+    reload();
     if (threadIdx.x == 0) *counter = 0u;
     return true;
+}
+// Cross-workgroup argmin on that hand-off: workgroup `slot` leaves its partial (v, i) - and raw, where part_raw is not
+// null - in part_*[slot]; the last one reduces the nslots partials: (v, i) is then the winner in every lane (i < 0: no
+// entrant).
+__device__ __forceinline__ bool last_arriver_argmin(double *part_cost, int64_t *part_idx, double *part_raw,
+                                                    unsigned *counter, int slot, int nslots, double &v, int64_t &i,
+                                                    double raw)
+{
+    return last_arriver(
+        counter, nslots,
+        [&] {
+            part_cost[slot] = v;
+            part_idx[slot] = i;
+            if (part_raw) part_raw[slot] = raw;
+        },
+        [&] {
+            v = INFINITY;
+            i = -1;
+            for (int k = threadIdx.x; k < nslots; k += RT_THREADS) {
+                const double pv = __builtin_nontemporal_load(part_cost + k);
+                const int64_t pi = __builtin_nontemporal_load(part_idx + k);
+                if (better(pv, pi, v, i)) { v = pv; i = pi; }
+            }
+            wave_argmin(v, i);
+        });
+}
+
+// ---- Ranked lists (the elite tail). A list is k mpcd_best entries, best first in better()'s order, empty entries
+// (index -1, cost +inf) last. (v, i) comes strictly after the last pick (pv, pi) in that order (elite.hip's tk_after); pi < 0:
+// nothing picked yet
+__device__ __forceinline__ bool after(double v, int64_t i, double pv, int64_t pi)
+{
+    return pi < 0 || v > pv || (v == pv && i > pi);
+}
+__device__ __forceinline__ void load_entry(const mpcd_best *e, double &v, int64_t &i)
+{
+    v = __builtin_nontemporal_load(&e->cost);
+    i = __builtin_nontemporal_load(&e->index);
+}
+// The best entry after the pick (pv, pi) over this lane's lists lane, lane + 64, ... of nlists sorted lists: in each,
+// the first entry after the pick. Stateless (topk_kernel's rule): no per-list position is kept, so a lane may own any
+// number of lists without an array in registers.
+__device__ __forceinline__ void lane_best_after(const mpcd_best *lists, int nlists, int k, double pv, int64_t pi,
+                                                double &lv, int64_t &li)
+{
+    lv = INFINITY;
+    li = -1;
+    for (int w = threadIdx.x; w < nlists; w += RT_THREADS) {
+        const mpcd_best *L = lists + (size_t)w * k;
+        for (int e = 0; e < k; ++e) {
+            double ev;
+            int64_t ei;
+            load_entry(L + e, ev, ei);
+            if (ei < 0) break;
+            if (after(ev, ei, pv, pi)) {
+                if (better(ev, ei, lv, li)) { lv = ev; li = ei; }
+                break;
+            }
+        }
+    }
+}
+// The k best of nlists sorted lists by one wave: k rounds of wave argmin over each lane's best remaining entry; only
+// the pick's owner moves on. Up to 64 lists: one per lane, its position h in a register; more: lane_best_after.
+// Lane r < k leaves with entry r in (mv, mi).
+__device__ __forceinline__ void merge_lists(const mpcd_best *lists, int nlists, int k, double &mv, int64_t &mi)
+{
+    const bool one = nlists <= RT_THREADS;
+    double lv = INFINITY;
+    int64_t li = -1;
+    int h = 0;
+    if (!one)
+        lane_best_after(lists, nlists, k, -INFINITY, -1, lv, li);
+    else if ((int)threadIdx.x < nlists)
+        load_entry(lists + (size_t)threadIdx.x * k, lv, li);
+    mv = INFINITY;
+    mi = -1;
+    for (int r = 0; r < k; ++r) {
+        double wv = lv;
+        int64_t wi = li;
+        wave_argmin(wv, wi);
+        if ((int)threadIdx.x == r) { mv = wv; mi = wi; }
+        if (wi >= 0 && li == wi) {
+            if (!one) {
+                lane_best_after(lists, nlists, k, wv, wi, lv, li);
+            } else if (++h < k) {
+                load_entry(lists + (size_t)threadIdx.x * k + h, lv, li);
+            } else {
+                lv = INFINITY;
+                li = -1;
+            }
+        }
+    }
 }
 
 // x0_dev == nullptr: every candidate starts from S.x0; else candidate b starts from x0_dev[b / group]
@@ -735,6 +819,96 @@ __global__ __launch_bounds__(RT_THREADS) void batch_step_tail_kernel(const SysK 
     }
 }
 
+// batch_step_tail_kernel that also ranks each state's k best candidates (mpcd_mpc_step_batch_elite): no cost array and
+// no top-k launch. After candidate_cost every lane holds one (cost, index) pair; min(k, candidates of the workgroup)
+// rounds of wave_argmin, the picked lane retiring itself, leave the workgroup's ranked list with entry r in lane r. It
+// goes to part_elite[m][j][0..k) (empty entries: index -1), the raw cost of entry 0 to part_raw as in the tail above.
+// The state's last workgroup (last_arriver) merges the wps lists (merge_lists; one workgroup per state: its own list is
+// the result) into the k elites, bit for bit mpcd_topk over mpcd_rollout_cost_grouped's costs: NaN reported as +inf,
+// ties to the lower index, global indices. Elite 0 is the winner; the record, u0 and the plan are written as above and
+// the elites to result + elite_off [n_states][k], where the launch_elite_priors that follows reads them: a state's one
+// wave does not write group * H * d floats of priors.
+template <int SYS>
+__global__ __launch_bounds__(RT_THREADS) void batch_step_elite_tail_kernel(const SysK S, const BatchEliteTail T)
+{
+    constexpr int nx = SysDim<SYS>::NX, nu = SysDim<SYS>::NU;
+    extern __shared__ float su[];  // [RT_THREADS][H*nu + 1]
+    const int H = T.H, row = H * nu, stride = row + 1, k = T.k;
+    const int wps = (int)((T.group + RT_THREADS - 1) / RT_THREADS);
+    const int64_t m = blockIdx.x / wps;
+    const int j = (int)(blockIdx.x - m * wps);
+    const int64_t base = m * T.group, end = base + T.group;
+    const int64_t c0 = base + (int64_t)j * RT_THREADS;
+    const int nc = (int)min((int64_t)RT_THREADS, end - c0);
+    stage_rows(T.u_norm + (size_t)c0 * row, nc, row, su);
+    const int code = state_clip_code(T.clip_src + (size_t)m * T.clip_per_state, T.clip_per_state);
+    __syncthreads();
+    const bool clip = code == 1;
+    const int64_t b = min(c0 + threadIdx.x, end - 1);  // lanes past the group recompute its last candidate
+    double x[nx];
+#pragma unroll
+    for (int i = 0; i < nx; ++i) x[i] = T.x_dev[m * nx + i];
+    const double J = candidate_cost<SYS>(S, su + (b - c0) * stride, clip, x, H);
+    double v = isnan(J) ? INFINITY : J;
+    int64_t i = (int)threadIdx.x < nc ? b : -1;
+    double mv = INFINITY, raw = J;  // lane r: entry r of the list
+    int64_t mi = -1;
+    const int rounds = min(k, nc);
+    for (int r = 0; r < rounds; ++r) {
+        double wv = v;
+        int64_t wi = i;
+        wave_argmin(wv, wi);  // RT_THREADS == one wave; every lane holds the result
+        if (r == 0) raw = __shfl(J, (int)(wi - c0));  // entry 0's cost as computed (a NaN stays one)
+        if ((int)threadIdx.x == r) { mv = wv; mi = wi; }
+        if (i == wi) i = -1;
+    }
+    const size_t p0 = (size_t)m * wps;
+    if (wps > 1) {
+        mpcd_best *pl = T.part_elite + (p0 + j) * k;
+        if ((int)threadIdx.x < k) pl[threadIdx.x] = mpcd_best{mv, mi};
+        __threadfence();
+    }
+    if (!last_arriver(
+            T.counters + m, wps, [&] { T.part_raw[p0 + j] = raw; },
+            [&] {
+                if (wps > 1) merge_lists(T.part_elite + p0 * k, wps, k, mv, mi);
+            }))
+        return;
+    v = __shfl(mv, 0);
+    i = __shfl(mi, 0);
+    if (i < 0) return;  // not reached: group >= 1 leaves an entrant in the state's first workgroup
+    // every lane computes the (wave-uniform) action and lane 0 stores it, as in closed_loop_tail_kernel
+    double u[nu];
+#pragma unroll
+    for (int e = 0; e < nu; ++e)
+        u[e] = rounded_action(T.u_norm[(size_t)i * row + e], clip, S.umin[e], S.umax[e], T.decimals);
+    const double raw_best = __builtin_nontemporal_load(T.part_raw + p0 + (i - base) / RT_THREADS);
+    if (threadIdx.x == 0) {
+        char *rec = T.result + m * T.rec_stride;
+        mpcd_state_result r;
+        r.cost = raw_best;
+        r.index = i;
+        r.flags = (code == 1 ? MPCD_STEP_CLIPPED : 0) | (code == 2 ? MPCD_STEP_NAN_SAMPLES : 0) |
+                  (isfinite(raw_best) ? 0 : MPCD_STEP_NONFINITE_WINNER);
+        r.reserved = 0;
+        *reinterpret_cast<mpcd_state_result *>(rec) = r;
+        double *uo = reinterpret_cast<double *>(rec + sizeof(mpcd_state_result));
+#pragma unroll
+        for (int e = 0; e < nu; ++e) uo[e] = u[e];
+    }
+    if ((int)threadIdx.x < k) reinterpret_cast<mpcd_best *>(T.result + T.elite_off)[m * k + threadIdx.x] = mpcd_best{mv, mi};
+    const float *wr = T.u_norm + (size_t)i * row;
+    float *plan = reinterpret_cast<float *>(T.result + T.plan_off) + (size_t)m * row;
+    for (int q = threadIdx.x; q < row; q += RT_THREADS) {
+        const int e = q % nu;
+        float mn = S.umin[0], mx = S.umax[0];
+#pragma unroll
+        for (int c = 1; c < nu; ++c)
+            if (e == c) { mn = S.umin[c]; mx = S.umax[c]; }
+        plan[q] = unnorm1(wr[q], clip, mn, mx);
+    }
+}
+
 __global__ __launch_bounds__(256) void repeat_rows_kernel(const float *rows, int64_t total, int64_t n, int row_len, float *out)
 {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
@@ -821,6 +995,23 @@ hipError_t launch_batch_step_tail(const mpcd_system_desc &d, const float *umin_h
     return dispatch_system(d, [&](auto sys) {
         hipLaunchKernelGGL(batch_step_tail_kernel<decltype(sys)::value>, dim3((unsigned)wgs), dim3(RT_THREADS), lds, stream,
                            S, t);
+    });
+}
+
+hipError_t launch_batch_elite_tail(const mpcd_system_desc &d, const float *umin_host, const float *umax_host,
+                                   const BatchEliteTail &t, hipStream_t stream)
+{
+    const SysK S = make_sysk(d, umin_host, umax_host);
+    const int64_t wgs = t.n_states * ((t.group + RT_THREADS - 1) / RT_THREADS);
+    if (t.n_states < 1 || t.group < 1 || wgs > 0x7fffffff) return hipErrorInvalidValue;
+    if (t.rec_stride != batch_step_rec_stride(d.n_u) || t.plan_off < t.n_states * t.rec_stride) return hipErrorInvalidValue;
+    if (t.k < 1 || t.k > MPCD_MAX_ELITES || t.k > t.group || t.select_first || !t.part_elite ||
+        t.elite_off < t.plan_off + (int64_t)sizeof(float) * t.n_states * t.H * d.n_u || t.elite_off % alignof(mpcd_best))
+        return hipErrorInvalidValue;
+    const size_t lds = sizeof(float) * RT_THREADS * (t.H * d.n_u + 1);
+    return dispatch_system(d, [&](auto sys) {
+        hipLaunchKernelGGL(batch_step_elite_tail_kernel<decltype(sys)::value>, dim3((unsigned)wgs), dim3(RT_THREADS), lds,
+                           stream, S, t);
     });
 }
 

@@ -133,6 +133,8 @@ class BatchStepResult:
     index: np.ndarray       # [M] global index m * n + j of the selected candidate in this step's batch
     flags: np.ndarray       # [M] int32 MPCD_STEP_CLIPPED | MPCD_STEP_NAN_SAMPLES | MPCD_STEP_NONFINITE_WINNER
     u_norm: torch.Tensor = None  # [M * n, H, d] this step's normalised samples (return_samples=True)
+    elite_index: np.ndarray = None  # [M, k] int64 global indices of each state's k best, best first (elites=k)
+    elite_cost: np.ndarray = None   # [M, k] fp64 their costs, nondecreasing (a NaN cost is reported as +inf)
 
 
 _STATE_RESULT = np.dtype([("cost", "<f8"), ("index", "<i8"), ("flags", "<i4"), ("reserved", "<i4")])
@@ -776,7 +778,7 @@ class DiffusionMPC:
     def mpc_step_batch(self, x_states, system: System, n_samples, w=0.01, sample_fn="ddpm_cfg", n_wo_noise=0,
                        ddim_steps=None, clamp_x0=False, seed=0, noise=None, select="argmin", decimals=4,
                        clip_rule="chain", grouped=False, warm_start=None, reset=None, return_samples=False,
-                       allow_nonfinite=False):
+                       allow_nonfinite=False, elites=None):
         """One control step for M plant states that arrive from OUTSIDE (a vectorised simulator, a plant with model
         mismatch, a fleet of devices): ONE library call (mpcd_mpc_step_batch) - one upload of the [M, n_x] fp64
         states, the sampler over M * n_samples candidates, one fused launch (batch_step_tail_kernel) for each state's
@@ -798,8 +800,23 @@ class DiffusionMPC:
         (noise of the cold call, noise of the warm call).
         A state without a finite cost carries MPCD_STEP_NONFINITE_WINNER and the call raises MpcdError
         (MPCD_ENONFINITE) unless allow_nonfinite=True, which returns the result with its flags (the other states'
-        entries are valid); either way the kept priors are dropped, so the next step is cold."""
+        entries are valid); either way the kept priors are dropped, so the next step is cold.
+        elites=k (with warm_start and select="argmin"; 1 <= k <= min(n_samples, 64)): the same single call
+        (mpcd_mpc_step_batch_elite) also ranks each state's k best candidates inside the fused launch and keeps one prior
+        per candidate, [M, n_samples, H, d]: candidate j of a state is seeded from the state's elite j % k, moved one
+        horizon point ahead (one mpcd_elite_priors launch after the tail). The result carries elite_index / elite_cost
+        [M, k] (topk()'s order and cost reporting; column 0 is `index`). The first such call, and any after M or
+        n_samples changed, samples cold. A stored [M, H, d] set seeds every candidate of a state from its one prior; a
+        call without elites after one with them starts from row 0 of each state, the winner's (as warm_prior() does).
+        elites=1 computes what warm_start alone computes."""
         K = None if warm_start is None else int(warm_start)
+        if elites is not None:
+            if K is None:
+                raise ValueError("elites needs warm_start=K: the elite set seeds the warm-start priors")
+            if select != "argmin":
+                raise ValueError("elites ranks candidates by cost: it needs select='argmin'")
+            if int(n_samples) >= 1:
+                elites = self._check_elites(elites, int(n_samples))
         if K is not None and (K < 1 or K > self.n_steps or self._sampler_id(sample_fn) != N.MPCD_DDPM_CFG):
             raise ValueError(f"warm_start={K} needs 1 <= K <= {self.n_steps} and the CFG-DDPM sampler")
         if select not in ("argmin", "first"):
@@ -832,10 +849,18 @@ class DiffusionMPC:
         H, d = self.spec.horizon, self.spec.state_dim
         kw = dict(system=system, n=n, w=w, sample_fn=sample_fn, n_wo_noise=n_wo_noise, ddim_steps=ddim_steps,
                   clamp_x0=clamp_x0, seed=seed, select=select, decimals=decimals, clip_rule=clip_rule, grouped=grouped,
-                  return_samples=return_samples)
+                  return_samples=return_samples, elites=elites)
         priors = getattr(self, "_batch_priors", None) if K is not None else None
         if priors is not None and priors.shape[0] != M:
             priors = None  # the fleet changed size: a cold start
+        if priors is not None and elites is None and priors.dim() == 4:
+            priors = priors[:, 0].contiguous()  # an elite set: each state's winner
+        elif priors is not None and elites is not None:
+            if priors.dim() == 3:  # one prior per state seeds all its candidates
+                priors = priors[:, None].expand(M, n, H, d).contiguous()
+            elif priors.shape[1] != n:
+                priors = None  # another candidate count: a cold start
+        pshape = (H, d) if elites is None else (n, H, d)
         split = K is not None and priors is not None and mask is not None and mask.any() and not mask.all()
         if isinstance(noise, (tuple, list)) != split:
             raise ValueError("noise is a pair (cold call's, warm call's) exactly when `reset` names some but not all "
@@ -843,12 +868,12 @@ class DiffusionMPC:
         if not split:
             warm = K is not None and priors is not None and not (mask is not None and mask.all())
             if K is not None and not warm:
-                priors = torch.empty((M, H, d), dtype=torch.float32, device=self.device)
+                priors = torch.empty((M,) + pshape, dtype=torch.float32, device=self.device)
             res, bad = self._batch_step_call(x, K if warm else 0, priors, noise, **kw)
         else:
             ic, iw = np.flatnonzero(mask), np.flatnonzero(~mask)
             tc, tw = torch.from_numpy(ic).to(self.device), torch.from_numpy(iw).to(self.device)
-            pc = torch.empty((len(ic), H, d), dtype=torch.float32, device=self.device)
+            pc = torch.empty((len(ic),) + pshape, dtype=torch.float32, device=self.device)
             pw = priors.index_select(0, tw)
             rc_, bad_c = self._batch_step_call(x[ic], 0, pc, noise[0], **kw)
             rw_, bad_w = self._batch_step_call(x[iw], K, pw, noise[1], **kw)
@@ -859,9 +884,15 @@ class DiffusionMPC:
                                   index=np.empty(M, dtype=np.int64), flags=np.empty(M, dtype=np.int32))
             if return_samples:
                 res.u_norm = torch.empty((M * n, H, d), dtype=torch.float32, device=self.device)
+            if elites is not None:
+                res.elite_index = np.empty((M, elites), dtype=np.int64)
+                res.elite_cost = np.empty((M, elites))
             for idx, tidx, sub in ((ic, tc, rc_), (iw, tw, rw_)):
                 res.u[idx], res.plan[idx], res.cost[idx], res.flags[idx] = sub.u, sub.plan, sub.cost, sub.flags
                 res.index[idx] = idx * n + (sub.index - np.arange(len(idx)) * n)
+                if elites is not None:
+                    res.elite_cost[idx] = sub.elite_cost
+                    res.elite_index[idx] = (idx * n)[:, None] + (sub.elite_index - (np.arange(len(idx)) * n)[:, None])
                 if return_samples:
                     res.u_norm.view(M, n, H, d).index_copy_(0, tidx, sub.u_norm.view(len(idx), n, H, d))
         if K is not None:
@@ -871,23 +902,26 @@ class DiffusionMPC:
         return res
 
     def batch_priors(self):
-        """The normalised priors [M, H, d] the next mpc_step_batch(warm_start=K) starts from (device), or None."""
+        """The normalised priors the next mpc_step_batch(warm_start=K) starts from (device), as stored: [M, H, d], or
+        [M, n, H, d] after a call with elites; or None."""
         return getattr(self, "_batch_priors", None)
 
     def set_batch_priors(self, priors):
-        """Replace mpc_step_batch's prior set: normalised plans [M, H, d] (copied to the device), or None."""
+        """Replace mpc_step_batch's prior set: normalised plans [M, H, d], or one per candidate [M, n, H, d] (copied to
+        the device), or None."""
         if priors is not None:
             H, d = self.spec.horizon, self.spec.state_dim
             priors = torch.as_tensor(priors, dtype=torch.float32)
-            if priors.dim() != 3 or tuple(priors.shape[1:]) != (H, d):
-                raise ValueError(f"priors must be [M, {H}, {d}], got {tuple(priors.shape)}")
+            if priors.dim() not in (3, 4) or tuple(priors.shape[-2:]) != (H, d) or 0 in priors.shape:
+                raise ValueError(f"priors must be [M, {H}, {d}] or [M, n, {H}, {d}], got {tuple(priors.shape)}")
             priors = priors.to(self.device).contiguous().clone()
         self._batch_priors = priors
 
     def _batch_step_call(self, x, t_start, priors, noise, system, n, w, sample_fn, n_wo_noise, ddim_steps, clamp_x0,
-                         seed, select, decimals, clip_rule, grouped, return_samples):
+                         seed, select, decimals, clip_rule, grouped, return_samples, elites=None):
         """One mpcd_mpc_step_batch call on the states x [M, n_x] (checked by mpc_step_batch): (BatchStepResult, whether
-        the call returned MPCD_ENONFINITE). priors: device [M, H, d] read when t_start > 0 and refreshed, or None."""
+        the call returned MPCD_ENONFINITE). priors: device [M, H, d] read when t_start > 0 and refreshed, or None.
+        elites=k: mpcd_mpc_step_batch_elite, priors [M, n, H, d]."""
         x = np.ascontiguousarray(x)
         M = x.shape[0]
         H, d, B, dev = self.spec.horizon, self.spec.state_dim, M * n, self.device
@@ -916,14 +950,24 @@ class DiffusionMPC:
         u = np.empty((M, d), dtype=np.float64)
         plan = np.empty((M, H, d), dtype=np.float32)
         a.x_host = x.ctypes.data
-        a.priors = priors.data_ptr() if priors is not None else None
         a.result_host, a.u_host, a.plan_host = rec.ctypes.data, u.ctypes.data, plan.ctypes.data
         a.u_norm = u_norm.data_ptr() if u_norm is not None else None
-        rc = self._lib.mpcd_mpc_step_batch(self._ctx, ctypes.byref(a), self._stream())
+        if elites is None:
+            a.priors = priors.data_ptr() if priors is not None else None
+            rc = self._lib.mpcd_mpc_step_batch(self._ctx, ctypes.byref(a), self._stream())
+        else:
+            e = N.BatchEliteArgs()
+            e.k = elites
+            e.priors = priors.data_ptr() if priors is not None else None
+            best = np.empty((M, elites), dtype=_BEST)
+            e.elites_host = best.ctypes.data
+            rc = self._lib.mpcd_mpc_step_batch_elite(self._ctx, ctypes.byref(a), ctypes.byref(e), self._stream())
         if rc != N.MPCD_ENONFINITE:
             N.check(rc, "mpcd_mpc_step_batch")
         res = BatchStepResult(u=u, plan=plan, cost=rec["cost"].copy(), index=rec["index"].copy(),
                               flags=rec["flags"].copy(), u_norm=u_norm)
+        if elites is not None:
+            res.elite_index, res.elite_cost = best["index"].copy(), best["cost"].copy()
         return res, rc == N.MPCD_ENONFINITE
 
     def mpc_step(self, x0, system: System, n_samples, w=0.01, sample_fn="ddpm_cfg", n_wo_noise=0, ddim_steps=None,
