@@ -136,7 +136,21 @@ typedef struct {
 /* The sampler's in-kernel noise stream (Philox4x32-10 keyed by seed, global candidate index, slice,
  * element quad) for candidates [global_offset, global_offset + n_cand): out dev [n_slices][n_cand][flat]
  * fp32, slice 0 = x_T, slice k = the draw of denoise step k (what `noise` would have to hold to replay
- * a Philox run in injected-noise mode). flat = H*d, a multiple of 4. */
+ * a Philox run in injected-noise mode). flat = H*d, a multiple of 4.
+ *
+ * The stream, for replaying it elsewhere (tests/_philox_ref.py is a numpy implementation, held to Random123's known
+ * answers; tests/test_gpu_philox.py holds every kernel to it): elements 4q .. 4q + 3 of candidate c (global index:
+ * global_offset + its index in the call) in slice k are made from the four 32-bit words r0 .. r3 of
+ *   Philox4x32-10(counter = (q, c & 0xffffffff, c >> 32, k), key = (seed & 0xffffffff, seed >> 32))
+ * (counter and key words in Random123's order, ten rounds). Uniforms, in fp32: u0 = ((float)r0 + 1) * 2^-32 and
+ * u2 = ((float)r2 + 1) * 2^-32 in (0, 1] (the + 1 keeps the logarithm finite), u1 = (float)r1 * 2^-32 and
+ * u3 = (float)r3 * 2^-32 in [0, 1] (no + 1), each conversion rounding to nearest even. Box-Muller:
+ *   z[4q + 0] = sqrt(-2 ln u0) cos(2 pi u1), z[4q + 1] = sqrt(-2 ln u0) sin(2 pi u1),
+ *   z[4q + 2] = sqrt(-2 ln u2) cos(2 pi u3), z[4q + 3] = sqrt(-2 ln u2) sin(2 pi u3),
+ * evaluated in fp32 with the fast logarithm, sine and cosine: within 1.8e-6 of the same transform in fp64
+ * (profiles/philox_reference.txt), |z| <= sqrt(64 ln 2) = 6.66, u0 == 1 gives zeros.
+ * MPCD_EINVAL (nothing written): out NULL, n_cand < 1, n_slices < 1, flat < 4 or not a multiple of 4,
+ * global_offset < 0. */
 int mpcd_philox_noise(uint64_t seed, int64_t global_offset, int64_t n_cand, int32_t n_slices, int32_t flat,
                       float *out, void *hip_stream);
 
