@@ -324,6 +324,60 @@ int mpcd_control_step(mpcd_ctx *ctx, const mpcd_system_desc *sys, double *x_dev,
                       const float *umax_host, const int32_t *flags_dev, int32_t select_first, int32_t decimals,
                       double *u_applied, int64_t *best_index, double *best_cost, void *hip_stream);
 
+/* ---- State constraints: rollout violation and feasibility-first ranking (single rank). Every selection above ranks
+ * by cost alone; these three entry points let a caller keep the plant inside a box of admissible states. They compose
+ * with the calls above (mpcd_elite_priors and mpcd_shift_plans consume the ranked list unchanged); the one-call tails
+ * (mpcd_mpc_step*, mpcd_closed_loop, mpcd_mpc_step_batch*) do not take a box.
+ *
+ * State box: component i < n_x of a state is admissible in [lo[i], hi[i]]; -inf / +inf mean unbounded; entries >= n_x
+ * are ignored.
+ *
+ * Violation of a candidate, in fp64:
+ *     V = max(0, max over the visited states x and i < n_x of max(lo[i] - x[i], x[i] - hi[i]))
+ * The visited states are exactly the states the dynamics step produces inside that candidate's cost evaluation:
+ * MPCD_COST_CANONICAL x_1 .. x_H; MPCD_COST_CALMPC x_1 .. x_{H-2} (calMPCCost's loop applies u_0 .. u_{H-3}: the quirk
+ * is kept, so the cost and the violation speak of the same trajectory). The start state is not tested: the caller
+ * knows it. An excess that is NaN (either difference is: a NaN state, inf - inf) makes V = +inf. A maximum does not
+ * depend on the order of its operands, so V is reproducible bit for bit where the states are.
+ *
+ * Feasibility-first order with tolerance tol >= 0: a candidate is feasible iff V <= tol; every feasible candidate ranks
+ * before every infeasible one; feasible candidates are ordered by (cost, index), infeasible ones by (V, cost, index);
+ * a NaN cost ranks and is reported as +inf, as in mpcd_topk. This is ONE strict lexicographic order on (g, cost, index)
+ * with g = V <= tol ? 0 : V. */
+typedef struct { double lo[12], hi[12]; } mpcd_state_box;
+
+/* mpcd_rollout_cost_grouped plus the box: cost_out [batch] is bit for bit what mpcd_rollout_cost_grouped writes (the
+ * same cost function, visited by the bounds test), viol_out [batch] each candidate's V. MPCD_EINVAL:
+ * mpcd_rollout_cost_grouped's cases; box or viol_out NULL; a NaN bound; lo[i] > hi[i] for some i < n_x. */
+int mpcd_rollout_cost_box(mpcd_ctx *ctx, const mpcd_system_desc *sys, const double *x0_dev, int64_t group,
+                          const float *u_norm, const float *umin_host, const float *umax_host, int64_t batch,
+                          int32_t horizon, const int32_t *flags_dev, const mpcd_state_box *box, double *cost_out,
+                          double *viol_out, void *hip_stream);
+
+/* mpcd_topk in the feasibility-first order: for m < n_groups, out_dev[m][0..k) = the k first of group m's candidates,
+ * {cost (NaN -> +inf), index_offset + position}; viol_out_dev[m][r] (or NULL) = that entry's V as computed (NaN -> +inf;
+ * not g); n_feasible_dev[m] (or NULL) = the number of candidates of the WHOLE group with V <= tol: 0 means "no
+ * admissible plan; entry 0 is the least violating one". One launch, one workgroup per group; every cost and violation
+ * is read from memory once. cost, viol dev fp64 [n_groups * group]. MPCD_EINVAL: mpcd_topk's cases; viol NULL; tol
+ * negative or NaN. */
+int mpcd_topk_feasible(mpcd_ctx *ctx, const double *cost, const double *viol, int64_t n_groups, int64_t group, int32_t k,
+                       double tol, int64_t index_offset, mpcd_best *out_dev /* [n_groups][k] */,
+                       double *viol_out_dev /* [n_groups][k] or NULL */, int64_t *n_feasible_dev /* [n_groups] or NULL */,
+                       void *hip_stream);
+
+/* mpcd_control_step with the selection supplied: state m applies candidate picks_dev[m * pick_stride].index -
+ * index_offset of u_norm [batch][H][n_u] (pick_stride = k walks entry 0 of a ranked [n_states][k] list): its u[0]
+ * unnormalised with flags_dev[m] and rounded to `decimals` places, then x_dev[m] <- f(x_dev[m], u0) in place;
+ * best_index[m] = the pick's index as given, best_cost[m] = the pick's cost (mpcd_topk's reporting: NaN -> +inf). A pick
+ * outside [0, batch) touches no memory through it: x_dev[m] stays, u_applied[m] = NaN, best_index[m] = -1,
+ * best_cost[m] = +inf. MPCD_EINVAL: a NULL pointer, n_states / batch / horizon / pick_stride < 1, decimals > 15, a bad
+ * system descriptor. */
+int mpcd_control_step_picked(mpcd_ctx *ctx, const mpcd_system_desc *sys, double *x_dev, int64_t n_states,
+                             const float *u_norm, int64_t batch, int32_t horizon, const mpcd_best *picks_dev,
+                             int64_t pick_stride, int64_t index_offset, const float *umin_host, const float *umax_host,
+                             const int32_t *flags_dev, int32_t decimals, double *u_applied, int64_t *best_index,
+                             double *best_cost, void *hip_stream);
+
 /* ---- The whole closed loop in one call. mpcd_closed_loop enqueues, on hip_stream and without a host synchronisation,
  * what DiffusionMPC.closed_loop composes from the entry points above: one mpcd_normalize_states launch for iteration
  * 0, then per iteration the sampler and ONE launch (closed_loop_tail_kernel, csrc/rollout.hip) for everything else:

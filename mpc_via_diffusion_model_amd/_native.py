@@ -52,6 +52,10 @@ class Best(ctypes.Structure):
     _fields_ = [("cost", ctypes.c_double), ("index", ctypes.c_int64)]
 
 
+class StateBox(ctypes.Structure):
+    _fields_ = [("lo", ctypes.c_double * 12), ("hi", ctypes.c_double * 12)]
+
+
 class StepArgs(ctypes.Structure):
     _fields_ = [("sys", ctypes.POINTER(SystemDesc)), ("x0", ctypes.c_void_p), ("ctx_min", ctypes.c_void_p),
                 ("ctx_max", ctypes.c_void_p), ("act_min", ctypes.c_void_p), ("act_max", ctypes.c_void_p),
@@ -152,6 +156,17 @@ EXPORTS = {
                            ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                            ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                            ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "mpcd_rollout_cost_box": ([ctypes.c_void_p, ctypes.POINTER(SystemDesc), ctypes.c_void_p, ctypes.c_int64,
+                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                               ctypes.c_void_p, ctypes.POINTER(StateBox), ctypes.c_void_p, ctypes.c_void_p,
+                               ctypes.c_void_p], ctypes.c_int),
+    "mpcd_topk_feasible": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                            ctypes.c_int32, ctypes.c_double, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                            ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "mpcd_control_step_picked": ([ctypes.c_void_p, ctypes.POINTER(SystemDesc), ctypes.c_void_p, ctypes.c_int64,
+                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "mpcd_closed_loop": ([ctypes.c_void_p, ctypes.POINTER(ClosedLoopArgs), ctypes.c_void_p], ctypes.c_int),
     "mpcd_mpc_step_batch": ([ctypes.c_void_p, ctypes.POINTER(BatchStepArgs), ctypes.c_void_p], ctypes.c_int),
     "mpcd_mpc_step_batch_elite": ([ctypes.c_void_p, ctypes.POINTER(BatchStepArgs), ctypes.POINTER(BatchEliteArgs),

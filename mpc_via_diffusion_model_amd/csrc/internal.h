@@ -235,5 +235,19 @@ hipError_t launch_topk(const double *cost, int64_t n_groups, int64_t group, int 
 // out[m * group + j][h] = rows[elites[m][j % k].index - offset][min(h + shift, H - 1)]; rows / out [n_groups * group][H][d]
 hipError_t launch_elite_priors(const float *rows, int64_t n_groups, int64_t group, int H, int d, const mpcd_best *elites,
                                int k, int64_t offset, int shift, float *out, hipStream_t stream);
+// State constraints (mpcd.h). launch_rollout_cost_box (rollout.hip): launch_rollout_cost of a grouped call that also
+// writes each candidate's violation of `box`; the costs are the grouped call's bits. launch_topk_feasible (elite.hip):
+// launch_topk in the feasibility-first order; viol_out [n_groups][k] and n_feasible [n_groups] may be null.
+// launch_control_step_picked (rollout.hip): launch_control_step with the selection supplied, state m applying candidate
+// picks[m * pick_stride].index - offset of u_norm [batch][H][n_u].
+hipError_t launch_rollout_cost_box(const mpcd_system_desc &d, const double *x0_dev, int64_t group, const float *u_norm,
+                                   const float *umin_host, const float *umax_host, const int *flags_dev, int64_t batch,
+                                   int H, const mpcd_state_box &box, double *cost, double *viol, hipStream_t stream);
+hipError_t launch_topk_feasible(const double *cost, const double *viol, int64_t n_groups, int64_t group, int k, double tol,
+                                int64_t offset, mpcd_best *out, double *viol_out, int64_t *n_feasible, hipStream_t stream);
+hipError_t launch_control_step_picked(const mpcd_system_desc &d, double *x_dev, int64_t M, const float *u_norm,
+                                      int64_t batch, int H, const mpcd_best *picks, int64_t pick_stride, int64_t offset,
+                                      const float *umin_host, const float *umax_host, const int *flags_dev, int decimals,
+                                      double *u_applied, int64_t *best_idx, double *best_cost, hipStream_t stream);
 // out[r * n + j][:] = rows[r][:] for j < n (the per-candidate rows of iteration 0 when the loop is not grouped)
 hipError_t launch_repeat_rows(const float *rows, int64_t n_rows, int64_t n, int row_len, float *out, hipStream_t stream);

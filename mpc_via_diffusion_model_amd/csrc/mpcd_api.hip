@@ -1196,6 +1196,48 @@ int mpcd_control_step(mpcd_ctx *c, const mpcd_system_desc *sys, double *x, int64
     return MPCD_OK;
 }
 
+// ---- State constraints (mpcd.h): the box rollout, the feasibility-first ranking, the control step on a supplied pick
+int mpcd_rollout_cost_box(mpcd_ctx *c, const mpcd_system_desc *sys, const double *x0_dev, int64_t group,
+                          const float *u_norm, const float *umin, const float *umax, int64_t batch, int32_t horizon,
+                          const int32_t *flags, const mpcd_state_box *box, double *cost, double *viol, void *stream_ptr)
+{
+    if (!c || !sys || !x0_dev || !u_norm || !umin || !umax || !flags || !box || !cost || !viol)
+        return fail(MPCD_EINVAL, "mpcd_rollout_cost_box: null argument");
+    if (batch < 1 || horizon < 2 || group < 1 || batch % group)
+        return fail(MPCD_EINVAL, "mpcd_rollout_cost_box: batch/group/horizon");
+    int rc = check_system(sys, horizon);
+    if (rc) return rc;
+    for (int i = 0; i < 12; ++i)
+        if (box->lo[i] != box->lo[i] || box->hi[i] != box->hi[i])
+            return fail(MPCD_EINVAL, "mpcd_rollout_cost_box: bound %d is NaN (use -inf / +inf for unbounded)", i);
+    for (int i = 0; i < sys->n_x; ++i)
+        if (box->lo[i] > box->hi[i])
+            return fail(MPCD_EINVAL, "mpcd_rollout_cost_box: lo[%d] = %g > hi[%d] = %g", i, box->lo[i], i, box->hi[i]);
+    DEVICE_GUARD(c->device);
+    HIP_TRY(launch_rollout_cost_box(*sys, x0_dev, group, u_norm, umin, umax, flags, batch, horizon, *box, cost, viol,
+                                    static_cast<hipStream_t>(stream_ptr)));
+    return MPCD_OK;
+}
+
+int mpcd_control_step_picked(mpcd_ctx *c, const mpcd_system_desc *sys, double *x, int64_t n_states, const float *u_norm,
+                             int64_t batch, int32_t horizon, const mpcd_best *picks, int64_t pick_stride, int64_t offset,
+                             const float *umin, const float *umax, const int32_t *flags, int32_t decimals,
+                             double *u_applied, int64_t *best_index, double *best_cost, void *stream_ptr)
+{
+    if (!c || !sys || !x || !u_norm || !picks || !umin || !umax || !flags || !u_applied || !best_index || !best_cost)
+        return fail(MPCD_EINVAL, "mpcd_control_step_picked: null argument");
+    if (n_states < 1 || batch < 1 || horizon < 1 || pick_stride < 1)
+        return fail(MPCD_EINVAL, "mpcd_control_step_picked: n_states/batch/horizon/pick_stride");
+    if (decimals > 15) return fail(MPCD_EINVAL, "decimals > 15");
+    int rc = check_system(sys, horizon);
+    if (rc) return rc;
+    DEVICE_GUARD(c->device);
+    HIP_TRY(launch_control_step_picked(*sys, x, n_states, u_norm, batch, horizon, picks, pick_stride, offset, umin, umax,
+                                       flags, decimals, u_applied, best_index, best_cost,
+                                       static_cast<hipStream_t>(stream_ptr)));
+    return MPCD_OK;
+}
+
 // ---- What mpcd_closed_loop and mpcd_mpc_step_batch share. `fn` is the entry point's name in the messages.
 extern "C++" {
 namespace {
@@ -1566,6 +1608,19 @@ int mpcd_topk(mpcd_ctx *c, const double *cost, int64_t n_groups, int64_t group, 
     if (int rc = check_elite_k("mpcd_topk", n_groups, group, k)) return rc;
     DEVICE_GUARD(c->device);
     HIP_TRY(launch_topk(cost, n_groups, group, k, offset, out_dev, static_cast<hipStream_t>(stream_ptr)));
+    return MPCD_OK;
+}
+
+int mpcd_topk_feasible(mpcd_ctx *c, const double *cost, const double *viol, int64_t n_groups, int64_t group, int32_t k,
+                       double tol, int64_t offset, mpcd_best *out_dev, double *viol_out_dev, int64_t *n_feasible_dev,
+                       void *stream_ptr)
+{
+    if (!c || !cost || !viol || !out_dev) return fail(MPCD_EINVAL, "mpcd_topk_feasible: null argument");
+    if (int rc = check_elite_k("mpcd_topk_feasible", n_groups, group, k)) return rc;
+    if (!(tol >= 0.0)) return fail(MPCD_EINVAL, "mpcd_topk_feasible: tol %g is negative or NaN", tol);
+    DEVICE_GUARD(c->device);
+    HIP_TRY(launch_topk_feasible(cost, viol, n_groups, group, k, tol, offset, out_dev, viol_out_dev, n_feasible_dev,
+                                 static_cast<hipStream_t>(stream_ptr)));
     return MPCD_OK;
 }
 

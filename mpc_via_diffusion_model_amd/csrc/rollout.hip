@@ -267,8 +267,14 @@ __device__ __forceinline__ void stage_rows(const float *src, int64_t nvalid, int
 
 // The MPC cost of the normalised plan ur[H][nu] from the state x (overwritten), both cost kinds. The fp64 operations
 // and their order are the contract with the C oracle (-ffp-contract=off: no contraction changes a rounding).
-template <int SYS>
-__device__ __forceinline__ double candidate_cost(const SysK &S, const float *ur, bool clip, double *x, int H)
+// visit(xn) sees every state dyn_step produces, right after the step (canonical: x_1 .. x_H; calMPCCost: x_1 ..
+// x_{H-2}, its loop applies u_0 .. u_{H-3}); the default sees nothing and compiles to nothing.
+struct NoVisit {
+    __device__ __forceinline__ void operator()(const double *) const {}
+};
+template <int SYS, class Visit = NoVisit>
+__device__ __forceinline__ double candidate_cost(const SysK &S, const float *ur, bool clip, double *x, int H,
+                                                 Visit visit = Visit{})
 {
     constexpr int nx = SysDim<SYS>::NX, nu = SysDim<SYS>::NU;
     float mn[nu], mx[nu];
@@ -286,6 +292,7 @@ __device__ __forceinline__ double candidate_cost(const SysK &S, const float *ur,
         double ucur = u[0];
         for (int i = 1; i < H - 1; ++i) {
             dyn_step<SYS>(S, x, &ucur, xn);
+            visit(xn);
             const double un = (double)unnorm1(ur[i * nu], clip, mn[0], mx[0]);
             for (int j = 1; j < nx; ++j) J = J + S.Q[j] * (xn[j] * xn[j]);
             J = J + S.R[0] * (un * un);
@@ -299,6 +306,7 @@ __device__ __forceinline__ double candidate_cost(const SysK &S, const float *ur,
         for (int k = 0; k < H; ++k) {
             for (int i = 0; i < nu; ++i) u[i] = (double)unnorm1(ur[k * nu + i], clip, mn[i], mx[i]);
             dyn_step<SYS>(S, x, u, xn);
+            visit(xn);
             const double sx = k < H - 1 ? quadform<nx>(S.Q, xn, S.xr) : quadform<nx>(S.P, xn, S.xr);
             const double sv = quadform<nu>(S.R, u, zero);
             J = J + (sx + sv);
@@ -510,6 +518,60 @@ __global__ __launch_bounds__(RT_THREADS) void rollout_cost_kernel(const SysK S, 
     }
 }
 
+// ---- State constraints (mpcd.h "State constraints"): mpcd_rollout_cost_grouped that also reports each candidate's
+// violation of a state box, V = max(0, max over the visited states and i < n_x of max(lo[i] - x[i], x[i] - hi[i])); an
+// excess with a NaN difference (a NaN state, inf - inf) makes V = +inf. A maximum has no order, so V is reproducible
+// bit for bit where the states are. The box is a kernel argument of its own (scalar registers); the bounds loop is
+// over the compile-time NX, so nothing is indexed dynamically.
+struct BoxK {
+    double lo[12], hi[12];
+};
+// fmax drops a NaN operand, so the NaN excesses are collected apart (one unordered compare per component) and
+// finish() turns any into +inf: five fp64 instructions per component and step.
+template <int NX>
+struct BoxVisit {
+    const BoxK &box;
+    double &V;   // starts at 0.0
+    bool &bad;   // an excess was NaN
+    __device__ __forceinline__ void operator()(const double *xn) const
+    {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+            const double a = box.lo[i] - xn[i], b = xn[i] - box.hi[i];
+            bad |= __builtin_isunordered(a, b);
+            V = fmax(V, fmax(a, b));
+        }
+    }
+    __device__ __forceinline__ static double finish(double V, bool bad) { return bad ? (double)INFINITY : V + 0.0; }
+};
+// rollout_cost_kernel<SYS, false> of a grouped call (candidate b starts from x0_dev[b / group]) with the visitor: the
+// cost is the same candidate_cost, hence the same bits.
+template <int SYS>
+__global__ __launch_bounds__(RT_THREADS) void rollout_cost_box_kernel(const SysK S, const BoxK box, const float *u_norm,
+                                                                      const int *flags, const double *x0_dev,
+                                                                      int64_t group, int64_t batch, int H, double *cost,
+                                                                      double *viol)
+{
+    constexpr int nx = SysDim<SYS>::NX, nu = SysDim<SYS>::NU;
+    extern __shared__ float su[];  // [RT_THREADS][H*nu + 1]
+    const int row = H * nu, stride = row + 1;
+    const int64_t c0 = (int64_t)blockIdx.x * RT_THREADS;
+    stage_rows(u_norm + (size_t)c0 * row, min((int64_t)RT_THREADS, batch - c0), row, su);
+    __syncthreads();
+    const int64_t b = min(c0 + threadIdx.x, batch - 1);  // lanes past the batch recompute the last one
+    const bool clip = flags[b / group] == 1;
+    double x[nx];
+#pragma unroll
+    for (int i = 0; i < nx; ++i) x[i] = x0_dev[(b / group) * nx + i];
+    double V = 0.0;
+    bool bad = false;
+    const double J = candidate_cost<SYS>(S, su + (b - c0) * stride, clip, x, H, BoxVisit<nx>{box, V, bad});
+    if (c0 + threadIdx.x < batch) {
+        cost[b] = J;
+        viol[b] = BoxVisit<nx>::finish(V, bad);
+    }
+}
+
 // Per-group clip flags: flags[g] = the clip code above over x[g*group_elems, (g+1)*group_elems)
 // (LimitsNormalizer's rule applied to each plant state's own candidate batch). One workgroup per group:
 // every flag is written, so no memset is needed.
@@ -605,6 +667,48 @@ __global__ __launch_bounds__(CS_THREADS) void control_step_kernel(const SysK S, 
     for (int i = 0; i < nu; ++i) u_applied[m * nu + i] = u[i];
     best_idx[m] = idx;
     best_cost[m] = cost[idx];
+}
+
+// control_step_kernel with the selection supplied (mpcd_control_step_picked): one thread per plant state m applies
+// candidate picks[m * pick_stride].index - offset: its u0 unnormalised with flags[m] and rounded, the plant step in
+// place, best_idx = the pick's index as given, best_cost = the pick's cost. A pick outside [0, batch) reads nothing
+// through it: x_dev[m] stays, u_applied[m] = NaN, best_idx[m] = -1, best_cost[m] = +inf. Every lane computes a step
+// (an invalid one on row 0, a lane past n_states on the last state) and only the stores are conditional: the fp64 pow
+// and the dynamics inside a divergent branch cost the quadrotor tail a private segment.
+constexpr int CP_THREADS = 64;
+template <int SYS>
+__global__ __launch_bounds__(CP_THREADS) void control_step_picked_kernel(const SysK S, double *x_dev, int64_t n_states,
+                                                                         const float *u_norm, int64_t batch, int H,
+                                                                         const mpcd_best *picks, int64_t pick_stride,
+                                                                         int64_t offset, const int *flags, int decimals,
+                                                                         double *u_applied, int64_t *best_idx,
+                                                                         double *best_cost)
+{
+    constexpr int nx = SysDim<SYS>::NX, nu = SysDim<SYS>::NU;
+    const int64_t t = (int64_t)blockIdx.x * CP_THREADS + threadIdx.x;
+    const bool live = t < n_states;
+    const int64_t m = live ? t : n_states - 1;
+    const mpcd_best pick = picks[m * pick_stride];
+    const int64_t idx = (int64_t)((uint64_t)pick.index - (uint64_t)offset);
+    const bool ok = idx >= 0 && idx < batch;
+    const int64_t r = ok ? idx : 0;
+    const bool clip = flags[m] == 1;
+    double x[nx], xn[nx], u[nu];
+#pragma unroll
+    for (int i = 0; i < nx; ++i) x[i] = x_dev[m * nx + i];
+#pragma unroll
+    for (int i = 0; i < nu; ++i)
+        u[i] = rounded_action(u_norm[(size_t)r * H * nu + i], clip, S.umin[i], S.umax[i], decimals);
+    dyn_step<SYS>(S, x, u, xn);
+    if (!live) return;
+    if (ok) {
+#pragma unroll
+        for (int i = 0; i < nx; ++i) x_dev[m * nx + i] = xn[i];
+    }
+#pragma unroll
+    for (int i = 0; i < nu; ++i) u_applied[m * nu + i] = ok ? u[i] : (double)NAN;
+    best_idx[m] = ok ? pick.index : -1;
+    best_cost[m] = ok ? pick.cost : (double)INFINITY;
 }
 
 // Single-workgroup argmin: NaN -> +inf; ties -> lowest index.
@@ -1119,5 +1223,39 @@ hipError_t launch_control_step(const mpcd_system_desc &d, double *x_dev, int64_t
     return dispatch_system(d, [&](auto sys) {
         hipLaunchKernelGGL(control_step_kernel<decltype(sys)::value>, dim3((unsigned)M), dim3(CS_THREADS), 0, stream, S,
                            x_dev, group, u_norm, H, cost, flags_dev, select_first, decimals, u_applied, best_idx, best_cost);
+    });
+}
+
+hipError_t launch_rollout_cost_box(const mpcd_system_desc &d, const double *x0_dev, int64_t group, const float *u_norm,
+                                   const float *umin_host, const float *umax_host, const int *flags_dev, int64_t batch,
+                                   int H, const mpcd_state_box &box, double *cost, double *viol, hipStream_t stream)
+{
+    const int64_t wgs = (batch + RT_THREADS - 1) / RT_THREADS;
+    if (batch < 1 || group < 1 || wgs > 0x7fffffff) return hipErrorInvalidValue;
+    const SysK S = make_sysk(d, umin_host, umax_host);
+    BoxK bk;
+    for (int i = 0; i < 12; ++i) {  // entries >= n_x are ignored: the kernel never reads them
+        bk.lo[i] = i < d.n_x ? box.lo[i] : -INFINITY;
+        bk.hi[i] = i < d.n_x ? box.hi[i] : INFINITY;
+    }
+    const size_t lds = sizeof(float) * RT_THREADS * (H * d.n_u + 1);
+    return dispatch_system(d, [&](auto sys) {
+        hipLaunchKernelGGL(rollout_cost_box_kernel<decltype(sys)::value>, dim3((unsigned)wgs), dim3(RT_THREADS), lds, stream,
+                           S, bk, u_norm, flags_dev, x0_dev, group, batch, H, cost, viol);
+    });
+}
+
+hipError_t launch_control_step_picked(const mpcd_system_desc &d, double *x_dev, int64_t M, const float *u_norm,
+                                      int64_t batch, int H, const mpcd_best *picks, int64_t pick_stride, int64_t offset,
+                                      const float *umin_host, const float *umax_host, const int *flags_dev, int decimals,
+                                      double *u_applied, int64_t *best_idx, double *best_cost, hipStream_t stream)
+{
+    const int64_t wgs = (M + CP_THREADS - 1) / CP_THREADS;
+    if (M < 1 || batch < 1 || pick_stride < 1 || wgs > 0x7fffffff) return hipErrorInvalidValue;
+    const SysK S = make_sysk(d, umin_host, umax_host);
+    return dispatch_system(d, [&](auto sys) {
+        hipLaunchKernelGGL(control_step_picked_kernel<decltype(sys)::value>, dim3((unsigned)wgs), dim3(CP_THREADS), 0, stream,
+                           S, x_dev, M, u_norm, batch, H, picks, pick_stride, offset, flags_dev, decimals, u_applied,
+                           best_idx, best_cost);
     });
 }

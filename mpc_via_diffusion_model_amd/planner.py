@@ -114,6 +114,8 @@ class MPCResult:
     flags: int = 0          # mpcd_last_step_flags bits (native step): 1 clipped, 2 NaN in the samples
     elite_index: np.ndarray = None  # [k] int64 global indices of the k best candidates, best first (elites=k)
     elite_cost: np.ndarray = None   # [k] fp64 their costs, nondecreasing (a NaN cost is reported as +inf)
+    violation: float = None  # state_box=: the selected candidate's box violation V (0.0 = inside the box)
+    n_feasible: int = None   # state_box=: how many candidates have V <= viol_tol (0: the least violating was selected)
 
 
 @dataclass
@@ -123,6 +125,8 @@ class ClosedLoopResult:
     cost: np.ndarray        # [M, T] cost of the selected candidate at each step
     index: np.ndarray       # [M, T] global index of the selected candidate in that step's batch
     u_norm: torch.Tensor = None  # [M * n, H, d] the last iteration's normalised samples (native=True only)
+    violation: np.ndarray = None   # [M, T] state_box=: the selected candidate's box violation V at each step
+    n_feasible: np.ndarray = None  # [M, T] state_box=: the state's candidates with V <= viol_tol at each step
 
 
 @dataclass
@@ -608,9 +612,148 @@ class DiffusionMPC:
                 "mpcd_elite_priors")
         return out
 
+    # ------------------------------------------------------------------ state constraints
+    @staticmethod
+    def _state_box(state_box, n_x):
+        """(lo, hi) with None = unbounded (the whole side, or single entries) -> the mpcd_state_box of an n_x system"""
+        try:
+            lo, hi = state_box
+        except (TypeError, ValueError):
+            raise ValueError("state_box must be a pair (lo, hi) of per-component bounds, None = unbounded") from None
+        box = N.StateBox()
+        for side, fill, dst in ((lo, -np.inf, box.lo), (hi, np.inf, box.hi)):
+            vals = [None] * n_x if side is None else list(side)
+            if len(vals) != n_x:
+                raise ValueError(f"state_box bounds must have n_x = {n_x} entries each, got {len(vals)}")
+            for i in range(12):
+                dst[i] = fill if i >= n_x or vals[i] is None else float(vals[i])
+        for i in range(n_x):
+            if np.isnan(box.lo[i]) or np.isnan(box.hi[i]) or box.lo[i] > box.hi[i]:
+                raise ValueError(f"state_box component {i}: [{box.lo[i]}, {box.hi[i]}] is not an interval")
+        return box
+
+    @staticmethod
+    def _viol_tol(viol_tol):
+        tol = float(viol_tol)
+        if not tol >= 0.0:
+            raise ValueError(f"viol_tol = {viol_tol} must be >= 0")
+        return tol
+
+    def _rollout_cost_box_raw(self, desc, x_dev, group, u_norm, flags, box, cost, viol):
+        B, H, _ = u_norm.shape
+        N.check(self._lib.mpcd_rollout_cost_box(self._ctx, ctypes.byref(desc), ctypes.c_void_p(x_dev.data_ptr()), group,
+                                                ctypes.c_void_p(u_norm.data_ptr()), self.act_min.ctypes.data,
+                                                self.act_max.ctypes.data, B, H, ctypes.c_void_p(flags.data_ptr()),
+                                                ctypes.byref(box), ctypes.c_void_p(cost.data_ptr()),
+                                                ctypes.c_void_p(viol.data_ptr()), self._stream()), "mpcd_rollout_cost_box")
+
+    def rollout_cost_box(self, system: System, x0_states, u_norm, state_box, group=None, clip_flags=None):
+        """rollout_cost for M start states with a state box (mpcd_rollout_cost_box): (cost [B], violation [B]) device
+        float64 tensors. Candidate b of u_norm [B, H, d] starts from x0_states[b // group] ([M, n_x], or [n_x] for one
+        state; host values or a device float64 tensor); group defaults to B // M. cost is bit for bit what the rollout
+        without a box computes. violation[b] = max(0, the largest excess of any component of any state the candidate's
+        cost evaluation visits over state_box = (lo, hi)), None entries = unbounded; the start state is not tested; +inf
+        where an excess is NaN. clip_flags: device int32 [M] clip codes (one per state); default: LimitsNormalizer's
+        rule over each state's own candidates of u_norm."""
+        B, H, d = u_norm.shape
+        if d != system.n_u:
+            raise ValueError(f"system {system.name} has {system.n_u} inputs, samples have {d}")
+        if torch.is_tensor(x0_states):
+            x = x0_states.to(self.device, torch.float64)
+        else:
+            x = torch.from_numpy(np.ascontiguousarray(x0_states, dtype=np.float64)).to(self.device)
+        x = (x[None] if x.dim() == 1 else x).contiguous()
+        M = x.shape[0]
+        if x.dim() != 2 or x.shape[1] != system.n_x:
+            raise ValueError(f"x0_states must be [M, {system.n_x}], got {tuple(x.shape)}")
+        group = B // M if group is None else int(group)
+        if group < 1 or M * group != B:
+            raise ValueError(f"u_norm has {B} candidates: not {M} states x group={group}")
+        box = self._state_box(state_box, system.n_x)
+        u_norm = u_norm.contiguous()
+        if clip_flags is None:
+            clip_flags = torch.empty(M, dtype=torch.int32, device=self.device)
+            N.check(self._lib.mpcd_clip_flags(self._ctx, ctypes.c_void_p(u_norm.data_ptr()), M, group * H * d,
+                                              ctypes.c_void_p(clip_flags.data_ptr()), self._stream()), "mpcd_clip_flags")
+        elif clip_flags.dtype != torch.int32 or clip_flags.device != self.device or clip_flags.numel() != M:
+            raise ValueError(f"clip_flags must be {M} int32 codes on {self.device}")
+        cost = torch.empty(B, dtype=torch.float64, device=self.device)
+        viol = torch.empty(B, dtype=torch.float64, device=self.device)
+        self._rollout_cost_box_raw(system.desc(), x, group, u_norm, clip_flags, box, cost, viol)
+        return cost, viol
+
+    def _topk_feasible_raw(self, cost, viol, k, n_groups, tol, index_offset=0):
+        """mpcd_topk_feasible: (mpcd_best records as int64 [M, k, 2] (cost bits, index), violation [M, k], n_feasible [M])"""
+        for name, t in (("cost", cost), ("violation", viol)):
+            if t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous float64 tensor on {self.device}")
+        M = int(n_groups)
+        if M < 1 or cost.numel() < 1 or cost.numel() % M != 0 or viol.numel() != cost.numel():
+            raise ValueError(f"cost / violation have {cost.numel()} / {viol.numel()} entries: not n_groups={M} groups of "
+                             "equal size each")
+        group = cost.numel() // M
+        k = self._check_elites(k, group)
+        raw = torch.empty((M, k, 2), dtype=torch.int64, device=self.device)
+        vk = torch.empty((M, k), dtype=torch.float64, device=self.device)
+        nf = torch.empty(M, dtype=torch.int64, device=self.device)
+        N.check(self._lib.mpcd_topk_feasible(self._ctx, ctypes.c_void_p(cost.data_ptr()), ctypes.c_void_p(viol.data_ptr()),
+                                             M, group, k, self._viol_tol(tol), int(index_offset),
+                                             ctypes.c_void_p(raw.data_ptr()), ctypes.c_void_p(vk.data_ptr()),
+                                             ctypes.c_void_p(nf.data_ptr()), self._stream()), "mpcd_topk_feasible")
+        return raw, vk, nf
+
+    def topk_feasible(self, cost, violation, k, n_groups=1, tol=0.0, index_offset=0):
+        """topk in the feasibility-first order (mpcd_topk_feasible): (index [M, k] int64, cost [M, k], violation [M, k],
+        n_feasible [M] int64) device tensors. A candidate is feasible iff violation <= tol; every feasible candidate
+        ranks before every infeasible one; feasible ones by (cost, index), infeasible ones by (violation, cost, index);
+        NaN costs and violations rank and are reported as +inf. n_feasible counts the feasible candidates of the whole
+        group: where it is 0 there is no admissible plan and entry 0 is the least violating one."""
+        raw, vk, nf = self._topk_feasible_raw(cost, violation, k, n_groups, tol, index_offset)
+        return raw[..., 1].contiguous(), raw[..., 0].contiguous().view(torch.float64), vk, nf
+
+    def _control_step_picked_raw(self, desc, x, u_norm, raw, index_offset, flags, decimals, u_out, i_out, c_out):
+        B, H, _ = u_norm.shape
+        N.check(self._lib.mpcd_control_step_picked(
+            self._ctx, ctypes.byref(desc), ctypes.c_void_p(x.data_ptr()), raw.shape[0], ctypes.c_void_p(u_norm.data_ptr()),
+            B, H, ctypes.c_void_p(raw.data_ptr()), raw.shape[1], int(index_offset), self.act_min.ctypes.data,
+            self.act_max.ctypes.data, ctypes.c_void_p(flags.data_ptr()), -1 if decimals is None else int(decimals),
+            ctypes.c_void_p(u_out.data_ptr()), ctypes.c_void_p(i_out.data_ptr()), ctypes.c_void_p(c_out.data_ptr()),
+            self._stream()), "mpcd_control_step_picked")
+
+    def control_step_picked(self, system: System, x_states, u_norm, index, cost, clip_flags, decimals=4, index_offset=0):
+        """One control step with the selection supplied (mpcd_control_step_picked): state m applies candidate index[m] -
+        index_offset of u_norm [B, H, d] - its first action unnormalised with clip_flags[m] and rounded to `decimals`
+        places (None: not rounded) - and x_states (device float64 [M, n_x]) is stepped IN PLACE. index [M] int64 and
+        cost [M] float64 are device tensors, e.g. column 0 of topk_feasible. Returns (u_applied [M, n_u], best_index [M],
+        best_cost [M]) device tensors. An index outside the batch leaves its state alone: u_applied NaN, best_index -1,
+        best_cost +inf."""
+        B, H, d = u_norm.shape
+        if (not torch.is_tensor(x_states) or x_states.dtype != torch.float64 or x_states.device != self.device
+                or x_states.dim() != 2 or x_states.shape[1] != system.n_x or not x_states.is_contiguous()):
+            raise ValueError(f"x_states must be a contiguous float64 [M, {system.n_x}] tensor on {self.device}")
+        M = x_states.shape[0]
+        if d != system.n_u:
+            raise ValueError(f"system {system.name} has {system.n_u} inputs, samples have {d}")
+        if index.dtype != torch.int64 or index.device != self.device or index.numel() != M:
+            raise ValueError(f"index must be {M} int64 entries on {self.device}")
+        if cost.dtype != torch.float64 or cost.device != self.device or cost.numel() != M:
+            raise ValueError(f"cost must be {M} float64 entries on {self.device}")
+        if clip_flags.dtype != torch.int32 or clip_flags.device != self.device or clip_flags.numel() != M:
+            raise ValueError(f"clip_flags must be {M} int32 codes on {self.device}")
+        raw = torch.empty((M, 1, 2), dtype=torch.int64, device=self.device)
+        raw[:, 0, 0] = cost.reshape(M).view(torch.int64)
+        raw[:, 0, 1] = index.reshape(M)
+        u_out = torch.empty((M, d), dtype=torch.float64, device=self.device)
+        i_out = torch.empty(M, dtype=torch.int64, device=self.device)
+        c_out = torch.empty(M, dtype=torch.float64, device=self.device)
+        self._control_step_picked_raw(system.desc(), x_states, u_norm.contiguous(), raw, index_offset, clip_flags, decimals,
+                                      u_out, i_out, c_out)
+        return u_out, i_out, c_out
+
     def closed_loop(self, x0_states, system: System, iterations, n_samples=1, w=0.01, sample_fn="ddpm_cfg",
                     n_wo_noise=0, ddim_steps=None, clamp_x0=False, select="argmin", decimals=4, seed=0, noise=None,
-                    clip_rule="chain", grouped=False, warm_start=None, native=False, elites=None):
+                    clip_rule="chain", grouped=False, warm_start=None, native=False, elites=None, state_box=None,
+                    viol_tol=0.0):
         """Closed-loop diffusion MPC for M plant states at once, resident on the device.
         The reference runs one initial state at a time on the host (Cart_Diffusion_inference.py:405-512:
         normalize_condition -> run_CFG -> unnormalize -> u0 = round(u[0], 4) -> x = f(x, u0), repeated
@@ -646,8 +789,23 @@ class DiffusionMPC:
         step each state's k best plans are ranked on the device (mpcd_topk) and candidate j of the state is seeded from
         elite j % k, moved one horizon point ahead (mpcd_elite_priors): the next iteration samples from [M * n, H, d]
         priors, one per candidate, instead of one per state. elites=1 computes what warm_start alone computes. The
-        fused tail of native=True writes one prior per state: elites there raises ValueError."""
+        fused tail of native=True writes one prior per state: elites there raises ValueError.
+        state_box=(lo, hi) (None entries = unbounded; native=False, select="argmin"), viol_tol >= 0: feasibility-first
+        selection. Per iteration, after the sampler and the clip flags: mpcd_rollout_cost_box (cost and box
+        violation of every candidate), mpcd_topk_feasible with k = elites or 1, mpcd_control_step_picked on entry 0, and
+        the next priors from the same ranked list (shift_plans on entry 0's index, or elite_priors: the elites are
+        feasibility-first too). The result carries violation / n_feasible [M, T]: where n_feasible is 0 no candidate
+        stayed in the box and the least violating one was applied. The fused tail of native=True takes no box: it
+        raises ValueError, as does select="first"."""
         K = None if warm_start is None else int(warm_start)
+        box = None
+        if state_box is not None:
+            if native:
+                raise ValueError("state_box is not available with native=True: folding the constraint into "
+                                 "mpcd_closed_loop's fused tail is the follow-up; use native=False")
+            if select != "argmin":
+                raise ValueError("state_box ranks candidates feasibility-first: it needs select='argmin'")
+            box, tol = self._state_box(state_box, system.n_x), self._viol_tol(viol_tol)
         if elites is not None:
             if K is None:
                 raise ValueError("elites needs warm_start=K: the elite set seeds the warm-start priors")
@@ -691,6 +849,10 @@ class DiffusionMPC:
         priors = None
         if K is not None:  # one prior per state, or (elites) one per candidate
             priors = torch.empty((M if elites is None else B, H, d), dtype=torch.float32, device=dev)
+        if box is not None:
+            viol = torch.empty(B, dtype=torch.float64, device=dev)
+            vs = torch.empty((T, M), dtype=torch.float64, device=dev)
+            nfs = torch.empty((T, M), dtype=torch.int64, device=dev)
         xs[0] = x
         for it in range(T):
             warm = {}
@@ -708,6 +870,17 @@ class DiffusionMPC:
                 N.check(self._lib.mpcd_clip_flags(self._ctx, ptr(absmax), M, n, ptr(flags), st), "mpcd_clip_flags")
             else:
                 N.check(self._lib.mpcd_clip_flags(self._ctx, ptr(u_norm), M, n * H * d, ptr(flags), st), "mpcd_clip_flags")
+            if box is not None:  # feasibility-first: one ranked list serves the selection and the next priors
+                self._rollout_cost_box_raw(desc, x, n, u_norm, flags, box, cost, viol)
+                raw, vk, nf = self._topk_feasible_raw(cost, viol, elites or 1, M, tol)
+                self._control_step_picked_raw(desc, x, u_norm, raw, 0, flags, decimals, us[it], ix[it], cs[it])
+                if elites is not None:
+                    self._elite_priors_raw(u_norm, raw, n, True, 0, priors)
+                elif K is not None:
+                    self.shift_plans(u_norm, ix[it], 0, out=priors)
+                vs[it], nfs[it] = vk[:, 0], nf
+                xs[it + 1] = x
+                continue
             N.check(self._lib.mpcd_rollout_cost_grouped(self._ctx, ctypes.byref(desc), ptr(x), n, ptr(u_norm),
                                                         self.act_min.ctypes.data, self.act_max.ctypes.data, B, H,
                                                         ptr(flags), ptr(cost), st), "mpcd_rollout_cost_grouped")
@@ -720,8 +893,11 @@ class DiffusionMPC:
             elif K is not None:
                 self.shift_plans(u_norm, ix[it], 0, out=priors)
             xs[it + 1] = x
-        return ClosedLoopResult(x=xs.transpose(0, 1).cpu().numpy(), u=us.transpose(0, 1).cpu().numpy(),
-                                cost=cs.t().cpu().numpy(), index=ix.t().cpu().numpy())
+        res = ClosedLoopResult(x=xs.transpose(0, 1).cpu().numpy(), u=us.transpose(0, 1).cpu().numpy(),
+                               cost=cs.t().cpu().numpy(), index=ix.t().cpu().numpy())
+        if box is not None:
+            res.violation, res.n_feasible = vs.t().cpu().numpy(), nfs.t().cpu().numpy()
+        return res
 
     def _closed_loop_native(self, x0, system, T, n, w, sample_fn, n_wo_noise, ddim_steps, clamp_x0, select, decimals,
                             seed, noise, clip_rule, grouped, K):
@@ -778,7 +954,7 @@ class DiffusionMPC:
     def mpc_step_batch(self, x_states, system: System, n_samples, w=0.01, sample_fn="ddpm_cfg", n_wo_noise=0,
                        ddim_steps=None, clamp_x0=False, seed=0, noise=None, select="argmin", decimals=4,
                        clip_rule="chain", grouped=False, warm_start=None, reset=None, return_samples=False,
-                       allow_nonfinite=False, elites=None):
+                       allow_nonfinite=False, elites=None, state_box=None):
         """One control step for M plant states that arrive from OUTSIDE (a vectorised simulator, a plant with model
         mismatch, a fleet of devices): ONE library call (mpcd_mpc_step_batch) - one upload of the [M, n_x] fp64
         states, the sampler over M * n_samples candidates, one fused launch (batch_step_tail_kernel) for each state's
@@ -808,7 +984,13 @@ class DiffusionMPC:
         [M, k] (topk()'s order and cost reporting; column 0 is `index`). The first such call, and any after M or
         n_samples changed, samples cold. A stored [M, H, d] set seeds every candidate of a state from its one prior; a
         call without elites after one with them starts from row 0 of each state, the winner's (as warm_prior() does).
-        elites=1 computes what warm_start alone computes."""
+        elites=1 computes what warm_start alone computes.
+        state_box: raises ValueError. The fused tail selects by cost alone; state constraints are available on the
+        composed paths (mpc_step and closed_loop with native=False)."""
+        if state_box is not None:
+            raise ValueError("mpc_step_batch takes no state_box: folding the constraint into the fused tail "
+                             "(mpcd_mpc_step_batch) is the follow-up; use closed_loop(native=False) or the composed calls "
+                             "rollout_cost_box / topk_feasible / control_step_picked")
         K = None if warm_start is None else int(warm_start)
         if elites is not None:
             if K is None:
@@ -972,7 +1154,7 @@ class DiffusionMPC:
 
     def mpc_step(self, x0, system: System, n_samples, w=0.01, sample_fn="ddpm_cfg", n_wo_noise=0, ddim_steps=None,
                  clamp_x0=False, seed=0, noise=None, group=None, comm=None, native=None, clip_rule="chain",
-                 warm_start=None, prior=None, elites=None):
+                 warm_start=None, prior=None, elites=None, state_box=None, viol_tol=0.0):
         """One control step: sample n_samples candidates on this rank (weak scaling: every rank adds
         n_samples), roll out + cost them, all-gather costs, pick the global argmin, broadcast it.
         comm: a distributed.NativeComm (the exchange inside libmpcd.so over RCCL) or None
@@ -999,13 +1181,30 @@ class DiffusionMPC:
         winner) and warm_prior() returns row 0, the best plan shifted. A stored prior of one row (from a call without
         elites) seeds every candidate; prior= may be [H, d] or [n_samples, H, d]. elites=1 computes what warm_start
         alone computes. ValueError: elites without warm_start, with native=False or on several ranks, or stored priors
-        whose row count is neither 1 nor n_samples (call reset_warm_start() after changing n_samples)."""
+        whose row count is neither 1 nor n_samples (call reset_warm_start() after changing n_samples).
+        state_box=(lo, hi) (None entries = unbounded), viol_tol >= 0: feasibility-first selection on the
+        composed step, single rank (native then defaults to False): mpcd_rollout_cost_box gives every candidate's cost
+        and box violation, and the winner is entry 0 of mpcd_topk_feasible - the cheapest candidate whose predicted
+        states stay in the box, or, when none does, the least violating one. The result carries violation and
+        n_feasible. ValueError with native=True, warm_start / prior / elites, a comm or several ranks: the fused step
+        and the multi-rank selection with a box are the follow-up."""
         if clip_rule not in _CLIP_RULES:
             raise ValueError(f"clip_rule must be one of {sorted(_CLIP_RULES)}")
         if comm is not None:
             rank, size = comm.rank, comm.size
         else:
             rank, size = D.world(group)
+        box = None
+        if state_box is not None:
+            if native:
+                raise ValueError("state_box is not available with native=True: folding the constraint into the fused step "
+                                 "(mpcd_mpc_step) is the follow-up; leave native unset or False")
+            if warm_start is not None or prior is not None or elites is not None:
+                raise ValueError("state_box with warm_start / prior / elites needs the native step, which takes no box "
+                                 "yet (the follow-up); closed_loop(native=False) combines them")
+            if comm is not None or size > 1:
+                raise ValueError("state_box is single-rank: the multi-rank feasibility-first selection is the follow-up")
+            box, tol, native = self._state_box(state_box, system.n_x), self._viol_tol(viol_tol), False
         if native is None:
             native = comm is not None or size == 1
         if elites is not None:
@@ -1037,6 +1236,13 @@ class DiffusionMPC:
             flag = self.clip_flag(absmax if absmax is not None else u_norm)
             if size > 1:
                 flag = comm.any_flag(flag) if comm else D.any_flag(flag, group)
+        if box is not None:
+            cost_local, viol = self.rollout_cost_box(system, x0, u_norm, state_box, clip_flags=flag)
+            raw, vk, nf = self._topk_feasible_raw(cost_local, viol, 1, 1, tol)
+            idx, best = int(raw[0, 0, 1]), float(raw[0, 0, 0:1].view(torch.float64))
+            u_host = self.unnormalize_states(u_norm[idx][None], flag)[0].cpu().numpy()
+            return MPCResult(u0=u_host[0].copy(), u_best=u_host, best_cost=best, best_index=idx, costs=cost_local,
+                             u_norm=u_norm, violation=float(vk[0, 0]), n_feasible=int(nf[0]))
         cost_local = self.rollout_cost(system, x0, u_norm, flag)
         if comm is not None:
             idx, best, row, costs = comm.select(cost_local, u_norm)
