@@ -23,7 +23,8 @@
 // 1.084 ms at cfg2 (0.986x), 4.246 vs 4.313 ms at 16,384 candidates (0.984x) - a small gain, far from the 0.90x hoped
 // for: the two waves of a SIMD run each layer in lock step between the same workgroup barriers (MFMA busy 0.34 of
 // the shader cycles per SIMD, as before), so the matrix pipe's idle time is mostly shared, not filled. It is the
-// default wherever rw32 was.
+// default wherever rw32 was. It has an LDS layout of its own (Lds8, below) that keeps the last three k-chunks of Linear
+// 8's weights in LDS for the whole launch (profiles/rw8_l8_lds_ab.txt: kernel 0.980x).
 #include <hip/hip_runtime.h>
 
 #include "mlp_x3.h"
@@ -85,6 +86,60 @@ MPCD_DEV f32x4 mfma_agpr1(const u32x4 &w, const u32x4 &x, f32x4 acc)
     return acc;
 }
 
+// LDS layout of the 8-wave form: Lds3's buffers, strides and tables, with storage shared between live ranges that never
+// meet, and the bytes that frees given to W8L, where the trailing KL k-chunks of Linear 8's weights (all N / 16 n-tiles,
+// three planes, 1 KB per fragment as the pack stores it: 64 lanes x 16 B, so a ds_read_b128 of lane * 16 is
+// conflict-free) stay for the whole launch. Linear 8 was the one layer whose own fragments were still being loaded from
+// L2 while it ran, each of them twice per CU (waves w and w + 4 hold the same n-tile).
+//  - S1 lies inside C0, behind the noise hand-over block (NZT x 4 KB). Both bases are multiples of 256 B, as in Lds3:
+//    bank and swizzle of every access are unchanged. S1 is written by the update (x planes, behind the final layer's
+//    barrier), Linear 1's and Linear 11's epilogues, and read by Linear 0, 2 and 12. C0 is written by Linear 5's and
+//    Linear 7's epilogues and, in the hand-over block only, by waves 4-7 during Linear 10; it is read by Linear 6,
+//    Linear 8 and take_noise (before the final layer's barrier). In step order: S1 [update, L0, L1, L2], C0 [L5 .. L8],
+//    hand-over block [L10 .. take_noise], S1 [L11, L12, update]. Linear 2's reads end before Linear 3's barrier and
+//    Linear 5's epilogue starts behind Linear 5's (two barriers between); Linear 8's reads end before Linear 9's
+//    barrier and Linear 11's epilogue starts behind Linear 11's (two between); the step boundary lies inside S1's own
+//    range. The hand-over block is not part of S1, so its range may overlap S1's.
+//  - XB (fp32 x) where XREG holds is written and read only before the step loop (x_T -> load_xr): it lies in T1, first
+//    written by Linear 0's epilogue behind the loop's first barrier, which load_xr's reads precede.
+template <int D0, int NB, int ROWS>
+struct Lds8 : Lds3<D0, NB, ROWS> {
+    using B3 = Lds3<D0, NB, ROWS>;
+    static constexpr int NZT = (D0 / 16 + 3) / 4;                            // MlpRw::NZT at W = 8
+    static constexpr bool XREG = NZT * (NB == 2 ? 1 : ROWS / 16) == 1;        // MlpRw::XREG at W = 8
+    static constexpr int PL = B3::PL, PL2 = B3::PL2;
+    static constexpr int T1 = 0;
+    static constexpr int C1 = T1 + 3 * PL;
+    static constexpr int C0 = C1 + 3 * PL;
+    static constexpr int S1 = C0 + NZT * 4096;
+    static_assert(S1 % 256 == 0 && C0 % 256 == 0 && S1 + 3 * PL <= C0 + 3 * PL2, "S1 inside C0, behind the noise block");
+    static constexpr int XB = XREG ? T1 : C0 + 3 * PL2;
+    static_assert(B3::CPW * B3::SX * 4 <= 3 * PL, "the fp32 x_T fits T1");
+    static constexpr int TPC = C0 + 3 * PL2 + (XREG ? 0 : B3::CPW * B3::SX * 4);
+    static constexpr int TPU = TPC + COND_TOTAL * 4;
+    static constexpr int BIC = TPU + COND_TOTAL * 4;
+    static constexpr int CPS = BIC + COND_TOTAL * 4;
+    static constexpr int BI = CPS + COND_TOTAL * 4;
+    static constexpr int AMX = BI + Arch<D0>::btotal() * 4;
+    static constexpr int W8L = (AMX + ROWS * 4 + 255) / 256 * 256;
+    // Linear 8: k-chunks KS .. KC8 - 1 resident. All or nothing at three k-chunks: the k-chunks that stay streamed are
+    // all in registers when the layer starts, and 256 registers per wave hold five of them, not six.
+    static constexpr int KC8 = Arch<D0>::K[8] / 32, NT8 = Arch<D0>::N[8] / 16, CHUNK = NT8 * 3 * 1024;
+    static constexpr int KL = (160 * 1024 - W8L) / CHUNK >= 3 ? 3 : 0;
+    static constexpr int KS = KC8 - KL;
+    static constexpr int total = W8L + KL * CHUNK;
+    static_assert(total <= 160 * 1024, "LDS budget (160 KiB per CU)");
+
+    static constexpr int in_off(int l) {
+        constexpr int t[NLAYER] = {S1, T1, S1, T1, C1 + 128, T1, C0 + 256, T1, C0, T1, C1, T1, S1, T1};
+        return t[l];
+    }
+    static constexpr int out_off(int l) {
+        constexpr int t[NLAYER] = {T1, S1, T1, C1 + 128, T1, C0 + 256, T1, C0, T1, C1, T1, S1, T1, 0};
+        return t[l];
+    }
+};
+
 // W = 4: one wave per SIMD (rw32 / rw16). W = 8: two per SIMD, 32 rows (rw32x8), the same sums in the same
 // order; only which wave computes a pass, and when, differs.
 // GRP: the grouped-context form (mlp_rw_grouped_kernel; see cand_span), a CTX instantiation of its own.
@@ -109,7 +164,8 @@ struct MlpRw {
     static_assert(W == 8 || NRG == RES_G);
     static constexpr int NCT = R / 16;  // 16-row column tiles
     using A = Arch<D0>;
-    using L = Lds3<D0, NB, R>;
+    // W = 8: a layout of its own (Lds8), with Linear 8's last KL k-chunks of weights resident in LDS
+    using L = std::conditional_t<W == 8, Lds8<D0, NB, R>, Lds3<D0, NB, R>>;
     static constexpr int CPW = L::CPW;
     static constexpr int QUADS = D0 / 4;
 
@@ -513,6 +569,11 @@ struct MlpRw {
     // 8-wave form only where that is one quad per lane, else the fp32 copy in LDS (the same values: 256 registers per
     // wave do not hold 2-4 quads beside the final layer's operands)
     static constexpr bool XREG = W == 4 || (D0 / 16 + 3) / 4 * XG == 1;
+    // Linear 8's k-chunks KS8 .. resident in LDS (Lds8::W8L); KL8 == 0: all eight streamed, as at W = 4
+    static constexpr int KL8 = [] { if constexpr (W == 8) return L::KL; else return 0; }();
+    static constexpr int KS8 = A::K[8] / 32 - KL8;
+    static constexpr bool lds8_agrees() { if constexpr (W == 8) return L::NZT == NZT && L::XREG == XREG; else return true; }
+    static_assert(lds8_agrees(), "Lds8 places the noise block and XB by these");
     static MPCD_DEV bool x_lane(int j, int wave, int col)
     {
         return upd_wave(wave) && (D0 / 16 % 4 == 0 || wave + 4 * j < D0 / 16) && !(R == 16 && NB == 2 && col >= 8);
@@ -609,7 +670,9 @@ struct MlpRw {
 #pragma unroll
             for (int j = 0; j < T; ++j)
                 if (NT % 4 == 0 || wave + 4 * j < NT) acc[j][c] = mfma_x3(f.v[j][0], xf[c], acc[j][c]);
+#ifndef MPCD_PROF_L8  // that build keeps rows 28 / 29 for Linear 8's halves
         prof_mark(tacc, tmark, 28, acc[0][1]);  // profile: the final layer's operand reads and MFMAs ("-" row)
+#endif
         if (R == 16 && NB == 2) {
             // column c holds candidate c & 7's context row (c < 8) or masked row (c >= 8): bring the masked
             // row's eps next to the context row's (DPP row_ror:8 swaps the two halves of each 16-lane row)
@@ -697,7 +760,9 @@ struct MlpRw {
                 }
             }
         }
+#ifndef MPCD_PROF_L8
         prof_mark(tacc, tmark, 29, am[0]);  // profile: the update, the stores
+#endif
     }
 
     // noise of step s (slice s+1) for this lane's quads, fetched one step ahead of use
@@ -819,6 +884,23 @@ struct MlpRw {
 
         Res res;
         load_res(res, wp, wave, lane);
+        // Linear 8's resident k-chunks, pack -> W8L, once per launch: fragment f = ((kc - KS8) NT + nt) 3 + plane, 1 KB
+        // each as the pack holds it, fragment i * 8 + wave by wave `wave` (past the last one: the last one again, the
+        // same bytes). Ordered before every read by the barrier below.
+        if constexpr (KL8 > 0) {
+            constexpr int NT = A::N[8] / 16, KC = A::K[8] / 32, NF = KL8 * NT * 3, NI = (NF + W - 1) / W;
+            const __amdgpu_buffer_rsrc_t rs = pack_rsrc(wp);
+            u32x4 st[NI];
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const int f = min(i * W + wave, NF - 1), kc = KS8 + f / (NT * 3), nt = f / 3 % NT, pl = f % 3;
+                const int soff = __builtin_amdgcn_readfirstlane(woffx<D0>(8) * 4 + ((nt * KC + kc) * 3 + pl) * 1024);
+                st[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, soff, 0));
+            }
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+                *reinterpret_cast<u32x4 *>(lds + L::W8L + min(i * W + wave, NF - 1) * 1024 + lane * 16) = st[i];
+        }
         for (int l = 0; l < NLAYER; ++l)
             for (int i = threadIdx.x; i < A::N[l]; i += NTH) bi[A::boff(l) + i] = wp[woffx<D0>(l) + wfl<D0>(l) + i];
         for (int j = 0; j < 6; ++j)
@@ -996,7 +1078,15 @@ struct MlpRw {
                 // stand whole. Its first W8P k-chunks are issued in the MFMA slots of Linear 7's second pass (Linear 7's
                 // own streamed Tail in Linear 6's slots), k-chunk c >= W8P in the MFMA slots of k-chunk c - W8P + 1 of
                 // Linear 8 itself (into registers its first chunks have left), Linear 9's in the slots of k-chunk 6.
-                constexpr int W8P = 4, KC8 = A::K[8] / 32, S9 = 6 * 6, S7 = 5 * 6, W8S = 12, NTL = (NRG - NAG) * 3;
+                // KL8 > 0: k-chunks KS8 .. are resident in LDS (Lds8::W8L). The KS8 streamed ones are then all issued in
+                // Linear 7's slots and waited for in front of Linear 8's barrier: no load of Linear 8's own and no
+                // vector-memory wait stands inside the layer. The resident ones are read one k-chunk ahead into a ring of
+                // two (r8), plane 2, 1, 0 (the order the products take them) in the first three MFMA slots of the k-chunk
+                // before, behind that k-chunk's operand reads: LDS reads return in order, so each product waits on a
+                // counted lgkmcnt.
+                constexpr int W8P = KL8 > 0 ? KS8 : 4, KC8 = A::K[8] / 32, S9 = 6 * 6, S7 = 5 * 6;
+                constexpr int W8S = KL8 > 0 ? KS8 * 3 : 12, NTL = (NRG - NAG) * 3;
+                static_assert(S7 + W8S <= 8 * 6, "Linear 7's MFMA slots");
                 static_assert(NFRAG<8> == KC8 * 3 && NFRAG<9> == 6 && W8P >= 2);
                 layer_res<0>(res, tail, none, hd, lds, wave, lane);
                 hd = pre_of<6>(lds, wave, lane);
@@ -1010,13 +1100,38 @@ struct MlpRw {
                 for (int f = W8S; f < W8P * 3; ++f) load_ws1<8>(w8, ws, wave, lane16, f);
                 sp = load_plan(p.plan, s + 1 < p.n_steps ? s + 1 : s);
                 hd = pre_of<8>(lds, wave, lane);
+                if constexpr (KL8 > 0) __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) lgkmcnt(0): Linear 8's streamed k-chunks
                 bar();
+                u32x4 r8[2][3];
+                const char *w8l = nullptr;
+                if constexpr (KL8 > 0) w8l = lds + L::W8L + nt_of<8>(wave, 0) * 3 * 1024 + lane * 16;
+#ifdef MPCD_PROF_L8
+                uint64_t t8 = tprev;  // profile: Linear 8 from its barrier to k-chunk 3's / on to k-chunk 7's last product
+#endif
                 auto stream8 = [&](int k) {
                     const int kc = k / 6, m = k % 6;
-                    if (kc >= 1 && kc + W8P - 1 < KC8 && m < 3) load_ws1<8>(w8, ws, wave, lane16, (kc + W8P - 1) * 3 + m);
+#ifdef MPCD_PROF_L8
+                    if (k == 4 * 6 - 1 || k == KC8 * 6 - 1) {
+                        asm volatile("" ::: "memory");
+                        const uint64_t t = prof_now();
+                        tacc[k == KC8 * 6 - 1 ? 29 : 28] += t - t8;
+                        t8 = t;
+                    }
+#endif
+                    if constexpr (KL8 > 0) {
+                        if (kc + 1 >= KS8 && kc + 1 < KC8 && m < 3)
+                            r8[(kc + 1) & 1][2 - m] = *reinterpret_cast<const u32x4 *>(
+                                w8l + ((kc + 1 - KS8) * (A::N[8] / 16) * 3 + 2 - m) * 1024);
+                    } else {
+                        if (kc >= 1 && kc + W8P - 1 < KC8 && m < 3) load_ws1<8>(w8, ws, wave, lane16, (kc + W8P - 1) * 3 + m);
+                    }
                     if (k >= S9 && k < S9 + NFRAG<9>) load_ws1<9>(w9, ws, wave, lane16, k - S9);
                 };
-                layer<8, KC8 * 6>(w8, stream8, hd, lds, wave, lane);
+                hidden_ilv<8, KC8 * 6>(
+                    [&](int j, int kc, int m, const u32x4 (&x)[3], f32x4 acc) {
+                        return mfma_bf(kc < KS8 ? w8.v[j][kc][wpl(m)] : r8[kc & 1][wpl(m)], x[xpl(m)], acc);
+                    },
+                    stream8, hd, lds, wave, lane);
                 load_ws<10>(w10, ws, wave, lane16);
                 hd = pre_of<9>(lds, wave, lane);
                 bar();
@@ -1156,7 +1271,7 @@ __global__ __launch_bounds__(64 * W, 1) void mlp_rw_grouped_kernel(const MlpSamp
 template <int D0, int SMODE, bool CTX, int R, int W, bool GRP = false>
 hipError_t launch_rw_r(const MlpSampleArgs &a, hipStream_t stream)
 {
-    using L = Lds3<D0, MlpRw<D0, SMODE, CTX, R, W>::NB, R>;
+    using L = typename MlpRw<D0, SMODE, CTX, R, W>::L;
     static_assert(L::total <= 160 * 1024, "LDS budget (160 KiB per CU)");
     int64_t blocks;
     int32_t group_wgs;

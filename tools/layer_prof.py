@@ -2,7 +2,9 @@
 
   python -m mpc_via_diffusion_model_amd.build prof MPCD_PROF_LAYERS      # here
   MPCD_LIB=mpc_via_diffusion_model_amd/libmpcd_prof.so python tools/layer_prof.py   # GPU box
-Prints cycles per step (work / barrier wait) for each segment, averaged over 32 waves of 8 WGs."""
+Prints cycles per step (work / barrier wait) for each segment, averaged over 32 waves of 8 WGs.
+Built with MPCD_PROF_L8 as well (DTYPE=f32x3, the 8-wave kernel), the "-" row is Linear 8 split in two: work = its
+barrier to k-chunk 3's last product, wait = from there to k-chunk 7's (the final layer's two marks are not taken)."""
 import ctypes
 import os
 import sys

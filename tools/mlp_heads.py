@@ -12,6 +12,10 @@ youngest vector load before it (in program text, around the loop's back edge) is
 The compiler lays the step out as more s_barrier instructions than a wave executes (waves 4-7 get a path of their own
 through the 32-wide layers); barriers_per_step() counts them along the paths. tests/test_mlp_rw_heads.py asserts on
 both.
+
+A second table (segments()) lists, per barrier-to-barrier segment of a step, the vector loads and MFMAs issued and
+every s_waitcnt vmcnt with its count and the MFMAs in front of it: a fragment load or a vector-memory wait inside a
+layer shows there (tests/test_mlp_rw_l8_lds.py: Linear 8 has neither for its own weights).
 """
 import os
 import re
@@ -263,6 +267,61 @@ def heads(loop):
     return out
 
 
+def segments(loop):
+    """One dict per barrier-to-barrier segment of a step, in the order a wave with a tile in every layer runs them
+    (segment k is Linear k's, the last one the final layer's and the update's): from the loop's first instruction to the
+    first barrier, then from each barrier along the path with the most MFMAs to the next barrier (the other paths are
+    those of waves without a tile). Per segment: vload, the vector loads issued; mfma, the MFMAs; vm_waits, every
+    s_waitcnt with a vmcnt in the segment as (MFMAs issued before it, its count, vector loads issued in the segment
+    before it)."""
+    inst = loop.inst
+
+    def walk(starts):
+        best, ends = {}, []  # an instruction is walked again only by a path that brings more MFMAs to it
+        stack = [(s, dict(vload=0, mfma=0, vm_waits=[])) for s in starts]
+        while stack:
+            k, g = stack.pop()
+            while True:
+                t = inst[k]
+                if t.startswith("s_barrier"):
+                    ends.append((k, g))
+                    break
+                if best.get(k, -1) >= g["mfma"] or g["mfma"] > len(inst):  # the bound: an inner loop with MFMAs
+                    break
+                best[k] = g["mfma"]
+                if _is_vload(t):
+                    g["vload"] += 1
+                elif t.startswith("v_mfma"):
+                    g["mfma"] += 1
+                elif t.startswith("s_waitcnt") and "vmcnt" in _wait(t):
+                    g["vm_waits"] = g["vm_waits"] + [(g["mfma"], _wait(t)["vmcnt"], g["vload"])]
+                nx = loop.succ[k]
+                if not nx:
+                    break
+                for s in nx[1:]:
+                    stack.append((s, dict(g)))
+                k = nx[0]
+        return max(ends, key=lambda e: e[1]["mfma"]) if ends else None
+
+    first = walk([0])
+    out, b = [], first[0] if first else None
+    while b is not None and b not in [s["barrier"] for s in out]:
+        end = walk(loop.succ[b])  # the last segment runs round the back edge to the step's first barrier
+        if end is None:
+            break
+        nb, g = end
+        out.append(dict(g, barrier=b))
+        b = nb
+    return out
+
+
+def segment_report(loop):
+    rows = ["segment  barrier@  vload  mfma  vmcnt waits as (MFMAs before it, count, loads of the segment before it)"]
+    for k, g in enumerate(segments(loop)):
+        rows.append(f"{k:7d}  {g['barrier']:8d}  {g['vload']:5d}  {g['mfma']:4d}  " + " ".join(f"({m},{c},{v})" for m, c, v in g["vm_waits"]))
+    return "\n".join(rows)
+
+
 def report(loop):
     hs = heads(loop)
     lo, hi = loop.barriers_per_step()
@@ -305,7 +364,9 @@ def main():
     else:
         with tempfile.TemporaryDirectory() as d:
             lines = open(compile_asm(os.path.join(d, "mlp_rw.s"))).read().splitlines()
-    print(report(Loop(kernel_body(lines))))
+    loop = Loop(kernel_body(lines))
+    print(report(loop))
+    print(segment_report(loop))
 
 
 if __name__ == "__main__":
