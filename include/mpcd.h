@@ -326,8 +326,9 @@ int mpcd_control_step(mpcd_ctx *ctx, const mpcd_system_desc *sys, double *x_dev,
 
 /* ---- State constraints: rollout violation and feasibility-first ranking (single rank). Every selection above ranks
  * by cost alone; these three entry points let a caller keep the plant inside a box of admissible states. They compose
- * with the calls above (mpcd_elite_priors and mpcd_shift_plans consume the ranked list unchanged); the one-call tails
- * (mpcd_mpc_step*, mpcd_closed_loop, mpcd_mpc_step_batch*) do not take a box.
+ * with the calls above (mpcd_elite_priors and mpcd_shift_plans consume the ranked list unchanged). Of the one-call
+ * tails the batched external step takes a box (mpcd_mpc_step_batch_box below: the same violation and the same order,
+ * computed inside its one tail launch); mpcd_mpc_step* and mpcd_closed_loop do not.
  *
  * State box: component i < n_x of a state is admissible in [lo[i], hi[i]]; -inf / +inf mean unbounded; entries >= n_x
  * are ignored.
@@ -449,7 +450,8 @@ int mpcd_closed_loop(mpcd_ctx *ctx, const mpcd_closed_loop_args *args, void *hip
 typedef struct {
     double cost;      /* the selected candidate's cost as computed (a NaN stays one) */
     int64_t index;    /* its global index in this call's batch: m * group + j */
-    int32_t flags;    /* per state: MPCD_STEP_CLIPPED | MPCD_STEP_NAN_SAMPLES | MPCD_STEP_NONFINITE_WINNER */
+    int32_t flags;    /* per state: MPCD_STEP_CLIPPED | MPCD_STEP_NAN_SAMPLES | MPCD_STEP_NONFINITE_WINNER
+                         (| MPCD_STEP_INFEASIBLE from mpcd_mpc_step_batch_box) */
     int32_t reserved; /* 0 */
 } mpcd_state_result;
 
@@ -509,6 +511,44 @@ typedef struct {
  * the per-state counters are the same self-resetting ones. */
 int mpcd_mpc_step_batch_elite(mpcd_ctx *ctx, const mpcd_batch_step_args *args, const mpcd_batch_elite_args *elite,
                               void *hip_stream);
+
+/* mpcd_mpc_step_batch / mpcd_mpc_step_batch_elite with a state box ("State constraints" above): the same call - one
+ * state upload, the sampler, ONE tail launch (batch_step_box_tail_kernel, csrc/rollout.hip), with elites the one
+ * mpcd_elite_priors launch, one download, one synchronisation. Inside the tail every candidate's rollout also reports
+ * its violation V of the box, and the selection and the elite ranking follow the feasibility-first order with `tol`;
+ * no cost array and no violation array goes through memory.
+ * The call returns everything mpcd_mpc_step_batch returns (elite == NULL) or mpcd_mpc_step_batch_elite returns (elite
+ * given), computed the same way; the one difference is the order. result_host[m].cost stays the selected candidate's
+ * cost as computed; elite costs are reported as mpcd_topk_feasible reports them (NaN -> +inf) and
+ * elites_host[m][0].index == result_host[m].index. For the same samples, states, clip flags and box, the index, cost, V
+ * and n_feasible of every state, elite_viol_host and the ranked lists are bit for bit entry 0 (entries 0..k) of
+ * mpcd_rollout_cost_box followed by mpcd_topk_feasible(k, tol); u0 and the plan are what mpcd_control_step_picked
+ * applies for that pick; the next priors are mpcd_shift_plans on entry 0 (elite == NULL, args->priors) or
+ * mpcd_elite_priors(shift = 1) on the ranked list (elite->priors).
+ * An all-infinite box with tol = 0 gives mpcd_mpc_step_batch's / _elite's results bit for bit: V = 0 then, except that
+ * a NaN state gives V = +inf, and such a candidate's cost is +inf in the order already, so the ranking does not move.
+ * Flags: MPCD_STEP_CLIPPED, MPCD_STEP_NAN_SAMPLES and MPCD_STEP_NONFINITE_WINNER as above (MPCD_ENONFINITE is returned
+ * as above); MPCD_STEP_INFEASIBLE is set exactly when n_feasible_host[m] == 0: no candidate of the state has V <= tol
+ * and the selected plan is the least violating one. It is a per-state flag, not an error return: the caller decides
+ * whether to apply that plan.
+ * MPCD_EINVAL: the underlying call's cases; box, box->box, viol_host or n_feasible_host NULL; a NaN bound or lo[i] >
+ * hi[i] for some i < n_x (mpcd_rollout_cost_box's rules); tol negative or NaN; a non-zero reserved field;
+ * args->select_first != 0 (ranking needs costs); elite_viol_host without elite. MPCD_EUNSUP: the underlying call's. */
+enum { MPCD_STEP_INFEASIBLE = 16 };
+typedef struct {
+    const mpcd_state_box *box;   /* host; mpcd_rollout_cost_box's rules */
+    double tol;                  /* mpcd_topk_feasible's tol: a candidate is feasible iff V <= tol */
+    double *viol_host;           /* host [M]: the selected candidate's V as computed (NaN -> +inf) */
+    int64_t *n_feasible_host;    /* host [M]: candidates of the whole group with V <= tol */
+    double *elite_viol_host;     /* host [M][k] or NULL: V of each elite (with elite != NULL) */
+    int32_t reserved, reserved2; /* 0 */
+} mpcd_batch_box_args;
+/* The partial lists, their violations and counts and the larger result block belong to the same context workspace as
+ * mpcd_mpc_step_batch's (which does not grow for the two calls above); the per-state counters are the same
+ * self-resetting ones, so the three calls may alternate on one context. */
+int mpcd_mpc_step_batch_box(mpcd_ctx *ctx, const mpcd_batch_step_args *args,
+                            const mpcd_batch_elite_args *elite /* NULL: winner only */, const mpcd_batch_box_args *box,
+                            void *hip_stream);
 
 /* ---- Candidate-batch data parallelism over RCCL / xGMI. One process per GPU, one
  * communicator per context; rank r owns global candidates [r*B_local, (r+1)*B_local). The reference has

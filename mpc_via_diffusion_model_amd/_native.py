@@ -24,6 +24,7 @@ MPCD_CLIP_CHAIN, MPCD_CLIP_FINAL, MPCD_CLIP_NONE = 0, 1, 2
 _STATUS = {-1: "EINVAL", -2: "EHIP", -3: "ESTATE", -4: "ENOMEM", -5: "EUNSUP", -6: "ENONFINITE"}
 MPCD_ENONFINITE = -6
 MPCD_STEP_CLIPPED, MPCD_STEP_NAN_SAMPLES, MPCD_STEP_NONFINITE_WINNER, MPCD_STEP_F32X3_RERUN = 1, 2, 4, 8
+MPCD_STEP_INFEASIBLE = 16  # mpcd_mpc_step_batch_box: no candidate of the state has V <= tol
 
 
 class NetDesc(ctypes.Structure):
@@ -96,6 +97,12 @@ class BatchStepArgs(ctypes.Structure):
 class BatchEliteArgs(ctypes.Structure):
     _fields_ = [("k", ctypes.c_int32), ("reserved", ctypes.c_int32), ("priors", ctypes.c_void_p),
                 ("elites_host", ctypes.c_void_p)]
+
+
+class BatchBoxArgs(ctypes.Structure):
+    _fields_ = [("box", ctypes.POINTER(StateBox)), ("tol", ctypes.c_double), ("viol_host", ctypes.c_void_p),
+                ("n_feasible_host", ctypes.c_void_p), ("elite_viol_host", ctypes.c_void_p), ("reserved", ctypes.c_int32),
+                ("reserved2", ctypes.c_int32)]
 
 
 class TrainCfg(ctypes.Structure):
@@ -171,6 +178,8 @@ EXPORTS = {
     "mpcd_mpc_step_batch": ([ctypes.c_void_p, ctypes.POINTER(BatchStepArgs), ctypes.c_void_p], ctypes.c_int),
     "mpcd_mpc_step_batch_elite": ([ctypes.c_void_p, ctypes.POINTER(BatchStepArgs), ctypes.POINTER(BatchEliteArgs),
                                    ctypes.c_void_p], ctypes.c_int),
+    "mpcd_mpc_step_batch_box": ([ctypes.c_void_p, ctypes.POINTER(BatchStepArgs), ctypes.POINTER(BatchEliteArgs),
+                                 ctypes.POINTER(BatchBoxArgs), ctypes.c_void_p], ctypes.c_int),
     "mpcd_comm_unique_id": ([ctypes.c_void_p], ctypes.c_int),
     "mpcd_comm_init": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p], ctypes.c_int),
     "mpcd_philox_noise": ([ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,

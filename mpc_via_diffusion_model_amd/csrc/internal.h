@@ -221,6 +221,19 @@ struct BatchEliteTail : BatchStepTail {
 };
 hipError_t launch_batch_elite_tail(const mpcd_system_desc &d, const float *umin_host, const float *umax_host,
                                    const BatchEliteTail &t, hipStream_t stream);
+// The same step with a state box (rollout.hip batch_step_box_tail_kernel, mpcd_mpc_step_batch_box): selection and
+// ranking in the feasibility-first order of mpcd.h's "State constraints" with tolerance tol. k = 1 without elites
+// (prior_out may then be set, as in BatchStepTail); the k ranked entries are always written. After the plans the result
+// block holds, in this order, the selected candidate's V double [n_states] at viol_off, n_feasible int64 [n_states] at
+// nfeas_off, the entries mpcd_best [n_states][k] at elite_off and their V double [n_states][k] at eviol_off. part_viol
+// [n_states][ceil(group / kRolloutBlock)][k] rides with part_elite, part_nfeas holds one count per workgroup.
+struct BatchBoxTail : BatchEliteTail {
+    double *part_viol;
+    int64_t *part_nfeas;
+    int64_t viol_off, nfeas_off, eviol_off;
+};
+hipError_t launch_batch_box_tail(const mpcd_system_desc &d, const float *umin_host, const float *umax_host,
+                                 const mpcd_state_box &box, double tol, const BatchBoxTail &t, hipStream_t stream);
 // Elite sets (elite.hip). launch_topk: out[m][0..k) = the k best of cost[m * group, (m + 1) * group), best first, in
 // rollout.hip's better() order, index = offset + position in cost[]; 1 <= k <= min(group, MPCD_MAX_ELITES).
 // mirror (n_groups == 1 only): the entries also written to mapped host memory, then *host_flag = host_seq after a

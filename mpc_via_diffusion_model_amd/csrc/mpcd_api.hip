@@ -1197,6 +1197,17 @@ int mpcd_control_step(mpcd_ctx *c, const mpcd_system_desc *sys, double *x, int64
 }
 
 // ---- State constraints (mpcd.h): the box rollout, the feasibility-first ranking, the control step on a supplied pick
+// The box rules of every call that takes one: no NaN bound, lo <= hi for the system's components
+static int check_state_box(const char *fn, const mpcd_state_box *box, int n_x)
+{
+    for (int i = 0; i < 12; ++i)
+        if (box->lo[i] != box->lo[i] || box->hi[i] != box->hi[i])
+            return fail(MPCD_EINVAL, "%s: bound %d is NaN (use -inf / +inf for unbounded)", fn, i);
+    for (int i = 0; i < n_x; ++i)
+        if (box->lo[i] > box->hi[i])
+            return fail(MPCD_EINVAL, "%s: lo[%d] = %g > hi[%d] = %g", fn, i, box->lo[i], i, box->hi[i]);
+    return MPCD_OK;
+}
 int mpcd_rollout_cost_box(mpcd_ctx *c, const mpcd_system_desc *sys, const double *x0_dev, int64_t group,
                           const float *u_norm, const float *umin, const float *umax, int64_t batch, int32_t horizon,
                           const int32_t *flags, const mpcd_state_box *box, double *cost, double *viol, void *stream_ptr)
@@ -1207,12 +1218,7 @@ int mpcd_rollout_cost_box(mpcd_ctx *c, const mpcd_system_desc *sys, const double
         return fail(MPCD_EINVAL, "mpcd_rollout_cost_box: batch/group/horizon");
     int rc = check_system(sys, horizon);
     if (rc) return rc;
-    for (int i = 0; i < 12; ++i)
-        if (box->lo[i] != box->lo[i] || box->hi[i] != box->hi[i])
-            return fail(MPCD_EINVAL, "mpcd_rollout_cost_box: bound %d is NaN (use -inf / +inf for unbounded)", i);
-    for (int i = 0; i < sys->n_x; ++i)
-        if (box->lo[i] > box->hi[i])
-            return fail(MPCD_EINVAL, "mpcd_rollout_cost_box: lo[%d] = %g > hi[%d] = %g", i, box->lo[i], i, box->hi[i]);
+    if ((rc = check_state_box("mpcd_rollout_cost_box", box, sys->n_x))) return rc;
     DEVICE_GUARD(c->device);
     HIP_TRY(launch_rollout_cost_box(*sys, x0_dev, group, u_norm, umin, umax, flags, batch, horizon, *box, cost, viol,
                                     static_cast<hipStream_t>(stream_ptr)));
@@ -1427,13 +1433,24 @@ int mpcd_closed_loop(mpcd_ctx *c, const mpcd_closed_loop_args *a, void *stream_p
 }
 
 // mpcd_mpc_step_batch and, ELITE, mpcd_mpc_step_batch_elite (e: its own arguments, else null): one host body. The
-// elite parts are compiled out of the plain call, which runs the statements it always ran.
+// elite parts are compiled out of the plain call, which runs the statements it always ran. BOX:
+// mpcd_mpc_step_batch_box (bx: its own arguments), with or without elites; its parts are compiled out of the other two.
 extern "C++" {
-template <bool ELITE>
-static int batch_step_impl(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpcd_batch_elite_args *e, void *stream_ptr)
+template <bool ELITE, bool BOX = false>
+static int batch_step_impl(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpcd_batch_elite_args *e, void *stream_ptr,
+                           const mpcd_batch_box_args *bx = nullptr)
 {
-    constexpr const char *fn = ELITE ? "mpcd_mpc_step_batch_elite" : "mpcd_mpc_step_batch";
+    constexpr const char *fn = BOX ? "mpcd_mpc_step_batch_box" : ELITE ? "mpcd_mpc_step_batch_elite" : "mpcd_mpc_step_batch";
     if (!c || !a) return fail(MPCD_EINVAL, "null argument");
+    if constexpr (BOX) {
+        if (!bx || !bx->box || !bx->viol_host || !bx->n_feasible_host) return fail(MPCD_EINVAL, "%s: null argument (box)", fn);
+        if (bx->reserved || bx->reserved2)
+            return fail(MPCD_EINVAL, "%s: box reserved %d / %d != 0", fn, bx->reserved, bx->reserved2);
+        if (!(bx->tol >= 0.0)) return fail(MPCD_EINVAL, "%s: tol %g is negative or NaN", fn, bx->tol);
+        if (!ELITE && bx->elite_viol_host) return fail(MPCD_EINVAL, "%s: elite_viol_host without elite", fn);
+        if (a->select_first)
+            return fail(MPCD_EINVAL, "%s: select_first != 0 (the feasibility-first ranking needs the costs)", fn);
+    }
     if constexpr (ELITE) {
         if (!e) return fail(MPCD_EINVAL, "%s: null argument (elite)", fn);
     }
@@ -1456,6 +1473,9 @@ static int batch_step_impl(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpc
     if (rc) return rc;
     mpcd_sample_args s;
     if ((rc = tail_sample_args(c, a, fn, (ELITE ? e->priors : a->priors) != nullptr, g.B, s))) return rc;
+    if constexpr (BOX) {
+        if ((rc = check_state_box(fn, bx->box, g.nx))) return rc;
+    }
     const int nu = g.nu, nx = g.nx, row = g.row;
     const int64_t M = g.M, n = g.n, B = g.B;
     hipStream_t st = static_cast<hipStream_t>(stream_ptr);
@@ -1467,9 +1487,15 @@ static int batch_step_impl(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpc
     const int64_t rec_stride = batch_step_rec_stride(nu);
     const size_t plan_off = ((size_t)(M * rec_stride) + 255) & ~(size_t)255;
     // ELITE: the elites mpcd_best [M][k] follow the plans
-    const int64_t k = ELITE ? e->k : 0;
-    const size_t elite_off = (plan_off + sizeof(float) * M * row + 255) & ~(size_t)255;
-    const size_t res_bytes = ELITE ? elite_off + sizeof(mpcd_best) * M * k : plan_off + sizeof(float) * M * row;
+    const int64_t k = ELITE ? e->k : BOX ? 1 : 0;  // BOX without elites: a ranked list of one
+    // BOX: the selected candidates' V [M] and n_feasible [M] follow the plans, then the entries and their V [M][k]
+    const size_t viol_off = (plan_off + sizeof(float) * M * row + 255) & ~(size_t)255;
+    const size_t nfeas_off = (viol_off + sizeof(double) * M + 255) & ~(size_t)255;
+    const size_t elite_off = BOX ? (nfeas_off + sizeof(int64_t) * M + 255) & ~(size_t)255 : viol_off;
+    const size_t eviol_off = (elite_off + sizeof(mpcd_best) * M * k + 255) & ~(size_t)255;
+    const size_t res_bytes = BOX     ? eviol_off + sizeof(double) * M * k
+                             : ELITE ? elite_off + sizeof(mpcd_best) * M * k
+                                     : plan_off + sizeof(float) * M * row;
     const size_t x_bytes = sizeof(double) * M * nx;
     const bool repeat_priors = !ELITE && a->warm_t_start > 0 && !g.grouped;  // ELITE: one per candidate already
     const size_t o_x = carve(x_bytes), o_pc = carve(sizeof(double) * M * g.wps), o_pr = carve(sizeof(double) * M * g.wps),
@@ -1477,7 +1503,9 @@ static int batch_step_impl(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpc
                  o_amax = carve(g.chain_rule ? sizeof(float) * B : 0), o_ctx = carve(sizeof(float) * g.rows * nx),
                  o_ctx0 = carve(g.grouped ? 0 : sizeof(float) * M * nx),
                  o_prior = carve(repeat_priors ? sizeof(float) * B * row : 0),
-                 o_pe = carve(sizeof(mpcd_best) * M * g.wps * k);  // ELITE: the workgroups' ranked lists
+                 o_pe = carve(sizeof(mpcd_best) * M * g.wps * k),  // ELITE / BOX: the workgroups' ranked lists
+                 o_pv = carve(BOX ? sizeof(double) * M * g.wps * k : 0),  // BOX: their violations and feasible counts
+                 o_pn = carve(BOX ? sizeof(int64_t) * M * g.wps : 0);
     if ((rc = c->batch_ws.ensure(carve.off))) return rc;
     if ((rc = grow_counters(c->batch_cnt, M, st))) return rc;
     const size_t h_res = (x_bytes + 255) & ~(size_t)255, host_bytes = h_res + res_bytes;
@@ -1514,13 +1542,29 @@ static int batch_step_impl(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpc
     rc = sample_impl(c, &s, stream_ptr, nullptr, g.grouped ? n : 0, a->warm_t_start ? &warm : nullptr);
     if (rc) return rc;
 
-    std::conditional_t<ELITE, BatchEliteTail, BatchStepTail> t{};
+    std::conditional_t<BOX, BatchBoxTail, std::conditional_t<ELITE, BatchEliteTail, BatchStepTail>> t{};
     fill_tail_common(t, g, u_norm, amax, x_dev, a->select_first, a->decimals, reinterpret_cast<double *>(w + o_pc),
                      reinterpret_cast<double *>(w + o_pr), reinterpret_cast<int64_t *>(w + o_pi), c->batch_cnt.as<unsigned>());
     t.result = w + o_res;
     t.rec_stride = rec_stride;
     t.plan_off = (int64_t)plan_off;
-    if constexpr (ELITE) {
+    if constexpr (BOX) {
+        t.part_elite = reinterpret_cast<mpcd_best *>(w + o_pe);
+        t.part_viol = reinterpret_cast<double *>(w + o_pv);
+        t.part_nfeas = reinterpret_cast<int64_t *>(w + o_pn);
+        t.viol_off = (int64_t)viol_off;
+        t.nfeas_off = (int64_t)nfeas_off;
+        t.elite_off = (int64_t)elite_off;
+        t.eviol_off = (int64_t)eviol_off;
+        t.k = (int32_t)k;
+        if constexpr (!ELITE) t.prior_out = a->priors;  // written by the tail, as in the plain call
+        HIP_TRY(launch_batch_box_tail(*a->sys, a->act_min, a->act_max, *bx->box, bx->tol, t, st));
+        if constexpr (ELITE) {
+            if (e->priors)  // the next priors, from the ranked list where the tail left it
+                HIP_TRY(launch_elite_priors(u_norm, M, n, g.H, nu, reinterpret_cast<const mpcd_best *>(w + o_res + elite_off),
+                                            e->k, 0, 1, e->priors, st));
+        }
+    } else if constexpr (ELITE) {
         t.part_elite = reinterpret_cast<mpcd_best *>(w + o_pe);
         t.elite_off = (int64_t)elite_off;
         t.k = e->k;
@@ -1549,6 +1593,11 @@ static int batch_step_impl(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpc
     if constexpr (ELITE) {
         if (e->elites_host) memcpy(e->elites_host, hs + h_res + elite_off, sizeof(mpcd_best) * M * e->k);
     }
+    if constexpr (BOX) {
+        memcpy(bx->viol_host, hs + h_res + viol_off, sizeof(double) * M);
+        memcpy(bx->n_feasible_host, hs + h_res + nfeas_off, sizeof(int64_t) * M);
+        if (bx->elite_viol_host) memcpy(bx->elite_viol_host, hs + h_res + eviol_off, sizeof(double) * M * k);
+    }
     if (bad)
         return fail(MPCD_ENONFINITE, "%s: %lld of %lld states have no candidate with a finite cost "
                                      "(first: state %lld); the other states' results are valid",
@@ -1565,6 +1614,12 @@ int mpcd_mpc_step_batch(mpcd_ctx *c, const mpcd_batch_step_args *a, void *stream
 int mpcd_mpc_step_batch_elite(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpcd_batch_elite_args *e, void *stream_ptr)
 {
     return batch_step_impl<true>(c, a, e, stream_ptr);
+}
+
+int mpcd_mpc_step_batch_box(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpcd_batch_elite_args *e,
+                            const mpcd_batch_box_args *bx, void *stream_ptr)
+{
+    return e ? batch_step_impl<true, true>(c, a, e, stream_ptr, bx) : batch_step_impl<false, true>(c, a, nullptr, stream_ptr, bx);
 }
 
 int mpcd_unnormalize(mpcd_ctx *c, const float *x, int64_t n_rows, int32_t dim, const float *mn, const float *mx,

@@ -459,6 +459,95 @@ __device__ __forceinline__ void merge_lists(const mpcd_best *lists, int nlists, 
     }
 }
 
+// ---- The same ranked lists in the feasibility-first order (mpcd.h "State constraints"; elite.hip's tf_*), for the box
+// tail. An entry is (V, cost, index), V its violation as computed (NaN = +inf already); the order is lexicographic on
+// (g, cost, index) with g = V <= tol ? 0 : V recomputed wherever keys are compared, so a pick carries its V. A list is
+// k mpcd_best entries and, parallel to it, k violations.
+__device__ __forceinline__ double box_key(double V, double tol) { return V <= tol ? 0.0 : V; }
+__device__ __forceinline__ bool better3(double g, double v, int64_t i, double bg, double bv, int64_t bi)
+{
+    return i >= 0 && (bi < 0 || g < bg || (g == bg && (v < bv || (v == bv && i < bi))));
+}
+__device__ __forceinline__ bool after3(double g, double v, int64_t i, double pg, double pv, int64_t pi)
+{
+    return pi < 0 || g > pg || (g == pg && (v > pv || (v == pv && i > pi)));
+}
+__device__ __forceinline__ void wave_argmin3(double &V, double &v, int64_t &i, double tol)
+{
+    double g = box_key(V, tol);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const double oV = __shfl_xor(V, m);
+        const double ov = __shfl_xor(v, m);
+        const int64_t oi = __shfl_xor(i, m);
+        const double og = box_key(oV, tol);
+        if (better3(og, ov, oi, g, v, i)) { V = oV; g = og; v = ov; i = oi; }
+    }
+}
+__device__ __forceinline__ void load_entry3(const mpcd_best *e, const double *eV, double &V, double &v, int64_t &i)
+{
+    load_entry(e, v, i);
+    V = __builtin_nontemporal_load(eV);
+}
+// lane_best_after on the three keys: the pick is (pV, pv, pi), pi < 0: nothing picked yet
+__device__ __forceinline__ void lane_best_after3(const mpcd_best *lists, const double *viols, int nlists, int k, double tol,
+                                                 double pV, double pv, int64_t pi, double &lV, double &lv, int64_t &li)
+{
+    const double pg = box_key(pV, tol);
+    double lg = INFINITY;
+    lV = INFINITY;
+    lv = INFINITY;
+    li = -1;
+    for (int w = threadIdx.x; w < nlists; w += RT_THREADS) {
+        const mpcd_best *L = lists + (size_t)w * k;
+        const double *LV = viols + (size_t)w * k;
+        for (int e = 0; e < k; ++e) {
+            double eV, ev;
+            int64_t ei;
+            load_entry3(L + e, LV + e, eV, ev, ei);
+            if (ei < 0) break;
+            const double eg = box_key(eV, tol);
+            if (after3(eg, ev, ei, pg, pv, pi)) {
+                if (better3(eg, ev, ei, lg, lv, li)) { lV = eV; lg = eg; lv = ev; li = ei; }
+                break;
+            }
+        }
+    }
+}
+// merge_lists on the three keys: lane r < k leaves with entry r in (mV, mv, mi)
+__device__ __forceinline__ void merge_lists3(const mpcd_best *lists, const double *viols, int nlists, int k, double tol,
+                                             double &mV, double &mv, int64_t &mi)
+{
+    const bool one = nlists <= RT_THREADS;
+    double lV = INFINITY, lv = INFINITY;
+    int64_t li = -1;
+    int h = 0;
+    if (!one)
+        lane_best_after3(lists, viols, nlists, k, tol, 0.0, -INFINITY, -1, lV, lv, li);
+    else if ((int)threadIdx.x < nlists)
+        load_entry3(lists + (size_t)threadIdx.x * k, viols + (size_t)threadIdx.x * k, lV, lv, li);
+    mV = INFINITY;
+    mv = INFINITY;
+    mi = -1;
+    for (int r = 0; r < k; ++r) {
+        double wV = lV, wv = lv;
+        int64_t wi = li;
+        wave_argmin3(wV, wv, wi, tol);
+        if ((int)threadIdx.x == r) { mV = wV; mv = wv; mi = wi; }
+        if (wi >= 0 && li == wi) {
+            if (!one) {
+                lane_best_after3(lists, viols, nlists, k, tol, wV, wv, wi, lV, lv, li);
+            } else if (++h < k) {
+                load_entry3(lists + (size_t)threadIdx.x * k + h, viols + (size_t)threadIdx.x * k + h, lV, lv, li);
+            } else {
+                lV = INFINITY;
+                lv = INFINITY;
+                li = -1;
+            }
+        }
+    }
+}
+
 // x0_dev == nullptr: every candidate starts from S.x0; else candidate b starts from x0_dev[b / group]
 // (closed loop: one plant state per group of candidates). flags[b / group] is that group's clip flag
 // (group = batch for the single-state case: one global flag).
@@ -1013,6 +1102,127 @@ __global__ __launch_bounds__(RT_THREADS) void batch_step_elite_tail_kernel(const
     }
 }
 
+// The box and the tolerance of the box tail: a kernel argument of their own, as rollout_cost_box_kernel's box is
+struct BoxTolK {
+    BoxK box;
+    double tol;
+};
+// batch_step_elite_tail_kernel with a state box (mpcd_mpc_step_batch_box): the same front half with BoxVisit riding
+// candidate_cost, so a candidate's cost and violation are the bits rollout_cost_box_kernel writes; after it every lane
+// holds (V, cost, index). The workgroup's ranked list (min(k, its candidates) rounds of wave_argmin3; k = 1 without
+// elites) goes to part_elite[m][j][0..k) with each entry's V in part_viol[m][j][0..k), its count of real lanes with
+// V <= tol (ballot and popcount: lanes past the group are neither entrants nor counted) to part_nfeas[m][j], entry 0's
+// raw cost to part_raw. The state's last workgroup merges the lists on the three keys (merge_lists3), sums the counts
+// and writes: the record (MPCD_STEP_INFEASIBLE iff the sum is 0), u0, the selected candidate's V and n_feasible, the k
+// ranked entries with their V (bit for bit mpcd_topk_feasible over mpcd_rollout_cost_box), the plan and, with
+// prior_out (no elites), the next prior by shift_plan_kernel's rule. No cost or violation array goes through memory.
+template <int SYS>
+__global__ __launch_bounds__(RT_THREADS) void batch_step_box_tail_kernel(const SysK S, const BoxTolK C, const BatchBoxTail T)
+{
+    constexpr int nx = SysDim<SYS>::NX, nu = SysDim<SYS>::NU;
+    extern __shared__ float su[];  // [RT_THREADS][H*nu + 1]
+    const int H = T.H, row = H * nu, stride = row + 1, k = T.k;
+    const int wps = (int)((T.group + RT_THREADS - 1) / RT_THREADS);
+    const int64_t m = blockIdx.x / wps;
+    const int j = (int)(blockIdx.x - m * wps);
+    const int64_t base = m * T.group, end = base + T.group;
+    const int64_t c0 = base + (int64_t)j * RT_THREADS;
+    const int nc = (int)min((int64_t)RT_THREADS, end - c0);
+    stage_rows(T.u_norm + (size_t)c0 * row, nc, row, su);
+    const int code = state_clip_code(T.clip_src + (size_t)m * T.clip_per_state, T.clip_per_state);
+    __syncthreads();
+    const bool clip = code == 1;
+    const int64_t b = min(c0 + threadIdx.x, end - 1);  // lanes past the group recompute its last candidate
+    double x[nx];
+#pragma unroll
+    for (int i = 0; i < nx; ++i) x[i] = T.x_dev[m * nx + i];
+    double Vacc = 0.0;
+    bool bad = false;
+    const double J = candidate_cost<SYS>(S, su + (b - c0) * stride, clip, x, H, BoxVisit<nx>{C.box, Vacc, bad});
+    const double tol = C.tol;
+    const double V = BoxVisit<nx>::finish(Vacc, bad);  // never NaN: a NaN excess is +inf
+    const double v = isnan(J) ? INFINITY : J;
+    const bool real = (int)threadIdx.x < nc;
+    int64_t i = real ? b : -1;
+    int64_t nf = __popcll(__ballot(real && V <= tol));
+    double mV = INFINITY, mv = INFINITY, raw = J;  // lane r: entry r of the list
+    int64_t mi = -1;
+    const int rounds = min(k, nc);
+    for (int r = 0; r < rounds; ++r) {
+        double wV = V, wv = v;
+        int64_t wi = i;
+        wave_argmin3(wV, wv, wi, tol);  // RT_THREADS == one wave; every lane holds the result
+        if (r == 0) raw = __shfl(J, (int)(wi - c0));  // entry 0's cost as computed (a NaN stays one)
+        if ((int)threadIdx.x == r) { mV = wV; mv = wv; mi = wi; }
+        if (i == wi) i = -1;
+    }
+    const size_t p0 = (size_t)m * wps;
+    if (wps > 1) {
+        if ((int)threadIdx.x < k) {
+            T.part_elite[(p0 + j) * k + threadIdx.x] = mpcd_best{mv, mi};
+            T.part_viol[(p0 + j) * k + threadIdx.x] = mV;
+        }
+        __threadfence();
+    }
+    if (!last_arriver(
+            T.counters + m, wps,
+            [&] {
+                T.part_raw[p0 + j] = raw;
+                T.part_nfeas[p0 + j] = nf;
+            },
+            [&] {
+                if (wps > 1) {
+                    merge_lists3(T.part_elite + p0 * k, T.part_viol + p0 * k, wps, k, tol, mV, mv, mi);
+                    int64_t s = 0;
+                    for (int w = threadIdx.x; w < wps; w += RT_THREADS) s += __builtin_nontemporal_load(T.part_nfeas + p0 + w);
+#pragma unroll
+                    for (int q = 32; q >= 1; q >>= 1) s += __shfl_xor(s, q);
+                    nf = s;
+                }
+            }))
+        return;
+    const double V0 = __shfl(mV, 0);
+    i = __shfl(mi, 0);
+    if (i < 0) return;  // not reached: group >= 1 leaves an entrant in the state's first workgroup
+    // every lane computes the (wave-uniform) action and lane 0 stores it, as in closed_loop_tail_kernel
+    double u[nu];
+#pragma unroll
+    for (int e = 0; e < nu; ++e)
+        u[e] = rounded_action(T.u_norm[(size_t)i * row + e], clip, S.umin[e], S.umax[e], T.decimals);
+    const double raw_best = __builtin_nontemporal_load(T.part_raw + p0 + (i - base) / RT_THREADS);
+    if (threadIdx.x == 0) {
+        char *rec = T.result + m * T.rec_stride;
+        mpcd_state_result r;
+        r.cost = raw_best;
+        r.index = i;
+        r.flags = (code == 1 ? MPCD_STEP_CLIPPED : 0) | (code == 2 ? MPCD_STEP_NAN_SAMPLES : 0) |
+                  (isfinite(raw_best) ? 0 : MPCD_STEP_NONFINITE_WINNER) | (nf == 0 ? MPCD_STEP_INFEASIBLE : 0);
+        r.reserved = 0;
+        *reinterpret_cast<mpcd_state_result *>(rec) = r;
+        double *uo = reinterpret_cast<double *>(rec + sizeof(mpcd_state_result));
+#pragma unroll
+        for (int e = 0; e < nu; ++e) uo[e] = u[e];
+        reinterpret_cast<double *>(T.result + T.viol_off)[m] = V0;
+        reinterpret_cast<int64_t *>(T.result + T.nfeas_off)[m] = nf;
+    }
+    if ((int)threadIdx.x < k) {
+        reinterpret_cast<mpcd_best *>(T.result + T.elite_off)[m * k + threadIdx.x] = mpcd_best{mv, mi};
+        reinterpret_cast<double *>(T.result + T.eviol_off)[m * k + threadIdx.x] = mV;
+    }
+    const float *wr = T.u_norm + (size_t)i * row;
+    float *plan = reinterpret_cast<float *>(T.result + T.plan_off) + (size_t)m * row;
+    float *po = T.prior_out ? T.prior_out + (size_t)m * row : nullptr;
+    for (int q = threadIdx.x; q < row; q += RT_THREADS) {
+        const int h = q / nu, e = q - h * nu;
+        float mn = S.umin[0], mx = S.umax[0];
+#pragma unroll
+        for (int c = 1; c < nu; ++c)
+            if (e == c) { mn = S.umin[c]; mx = S.umax[c]; }
+        plan[q] = unnorm1(wr[q], clip, mn, mx);
+        if (po) po[q] = wr[min(h + 1, H - 1) * nu + e];
+    }
+}
+
 __global__ __launch_bounds__(256) void repeat_rows_kernel(const float *rows, int64_t total, int64_t n, int row_len, float *out)
 {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
@@ -1116,6 +1326,34 @@ hipError_t launch_batch_elite_tail(const mpcd_system_desc &d, const float *umin_
     return dispatch_system(d, [&](auto sys) {
         hipLaunchKernelGGL(batch_step_elite_tail_kernel<decltype(sys)::value>, dim3((unsigned)wgs), dim3(RT_THREADS), lds,
                            stream, S, t);
+    });
+}
+
+hipError_t launch_batch_box_tail(const mpcd_system_desc &d, const float *umin_host, const float *umax_host,
+                                 const mpcd_state_box &box, double tol, const BatchBoxTail &t, hipStream_t stream)
+{
+    const SysK S = make_sysk(d, umin_host, umax_host);
+    const int64_t wgs = t.n_states * ((t.group + RT_THREADS - 1) / RT_THREADS);
+    if (t.n_states < 1 || t.group < 1 || wgs > 0x7fffffff) return hipErrorInvalidValue;
+    if (t.rec_stride != batch_step_rec_stride(d.n_u) || t.plan_off < t.n_states * t.rec_stride) return hipErrorInvalidValue;
+    // the result block's parts in order, none overlapping the one before: plans, V, n_feasible, entries, their V
+    if (t.k < 1 || t.k > MPCD_MAX_ELITES || t.k > t.group || t.select_first || !t.part_elite || !t.part_viol ||
+        !t.part_nfeas || !(tol >= 0.0) ||
+        t.viol_off < t.plan_off + (int64_t)sizeof(float) * t.n_states * t.H * d.n_u || t.viol_off % alignof(double) ||
+        t.nfeas_off < t.viol_off + (int64_t)sizeof(double) * t.n_states || t.nfeas_off % alignof(int64_t) ||
+        t.elite_off < t.nfeas_off + (int64_t)sizeof(int64_t) * t.n_states || t.elite_off % alignof(mpcd_best) ||
+        t.eviol_off < t.elite_off + (int64_t)sizeof(mpcd_best) * t.n_states * t.k || t.eviol_off % alignof(double))
+        return hipErrorInvalidValue;
+    BoxTolK C;
+    for (int i = 0; i < 12; ++i) {  // entries >= n_x are ignored: the kernel never reads them
+        C.box.lo[i] = i < d.n_x ? box.lo[i] : -INFINITY;
+        C.box.hi[i] = i < d.n_x ? box.hi[i] : INFINITY;
+    }
+    C.tol = tol;
+    const size_t lds = sizeof(float) * RT_THREADS * (t.H * d.n_u + 1);
+    return dispatch_system(d, [&](auto sys) {
+        hipLaunchKernelGGL(batch_step_box_tail_kernel<decltype(sys)::value>, dim3((unsigned)wgs), dim3(RT_THREADS), lds,
+                           stream, S, C, t);
     });
 }
 

@@ -139,6 +139,10 @@ class BatchStepResult:
     u_norm: torch.Tensor = None  # [M * n, H, d] this step's normalised samples (return_samples=True)
     elite_index: np.ndarray = None  # [M, k] int64 global indices of each state's k best, best first (elites=k)
     elite_cost: np.ndarray = None   # [M, k] fp64 their costs, nondecreasing (a NaN cost is reported as +inf)
+    violation: np.ndarray = None    # [M] mpc_step_batch_box: the selected candidate's box violation V (0.0 = inside)
+    n_feasible: np.ndarray = None   # [M] int64 mpc_step_batch_box: the state's candidates with V <= viol_tol (0: the
+                                    # least violating one was selected; the state carries MPCD_STEP_INFEASIBLE)
+    elite_violation: np.ndarray = None  # [M, k] mpc_step_batch_box with elites: V of each ranked candidate
 
 
 _STATE_RESULT = np.dtype([("cost", "<f8"), ("index", "<i8"), ("flags", "<i4"), ("reserved", "<i4")])
@@ -985,12 +989,41 @@ class DiffusionMPC:
         n_samples changed, samples cold. A stored [M, H, d] set seeds every candidate of a state from its one prior; a
         call without elites after one with them starts from row 0 of each state, the winner's (as warm_prior() does).
         elites=1 computes what warm_start alone computes.
-        state_box: raises ValueError. The fused tail selects by cost alone; state constraints are available on the
-        composed paths (mpc_step and closed_loop with native=False)."""
+        state_box: raises ValueError. This method selects by cost alone; mpc_step_batch_box is the same step with a
+        state box."""
         if state_box is not None:
-            raise ValueError("mpc_step_batch takes no state_box: folding the constraint into the fused tail "
-                             "(mpcd_mpc_step_batch) is the follow-up; use closed_loop(native=False) or the composed calls "
-                             "rollout_cost_box / topk_feasible / control_step_picked")
+            raise ValueError("mpc_step_batch takes no state_box: the constrained one-call step that was the follow-up "
+                             "is mpc_step_batch_box(x_states, system, n_samples, state_box, viol_tol)")
+        return self._mpc_step_batch(x_states, system, n_samples, w, sample_fn, n_wo_noise, ddim_steps, clamp_x0, seed,
+                                    noise, select, decimals, clip_rule, grouped, warm_start, reset, return_samples,
+                                    allow_nonfinite, elites)
+
+    def mpc_step_batch_box(self, x_states, system: System, n_samples, state_box, viol_tol=0.0, **kw):
+        """mpc_step_batch with a state box: still ONE library call (mpcd_mpc_step_batch_box) - one upload, the sampler,
+        one fused launch (batch_step_box_tail_kernel), with elites the one mpcd_elite_priors launch, one download.
+        Inside the fused launch every candidate's rollout also reports its violation V of state_box = (lo, hi) (None
+        entries = unbounded; rollout_cost_box's definition), and the selection and the elite ranking follow
+        topk_feasible's feasibility-first order with tol = viol_tol: every candidate with V <= viol_tol before every
+        other one, those by (cost, index), the others by (V, cost, index). index, cost, violation, n_feasible and the
+        elite lists are bit for bit what rollout_cost_box + topk_feasible give on the step's samples, u and the plan
+        what control_step_picked applies for that pick, the kept priors shift_plans / elite_priors on that ranking.
+        **kw: mpc_step_batch's own keywords (w, sample_fn, n_wo_noise, ddim_steps, clamp_x0, seed, noise, decimals,
+        clip_rule, grouped, warm_start, elites, reset, return_samples, allow_nonfinite), with the same meaning and the
+        same kept prior set (batch_priors(), set_batch_priors(), reset_warm_start()): a fleet may switch between the
+        two methods. select="first" raises ValueError.
+        The result carries violation [M], n_feasible [M] and, with elites, elite_violation [M, k]. Where n_feasible is
+        0 no candidate stayed in the box: the least violating plan is returned and the state's flags carry
+        MPCD_STEP_INFEASIBLE - not an error; the caller decides whether to apply it. An all-infinite box with
+        viol_tol=0 returns mpc_step_batch's results bit for bit."""
+        if kw.get("select", "argmin") != "argmin":
+            raise ValueError("state_box ranks candidates feasibility-first: it needs select='argmin'")
+        box, tol = self._state_box(state_box, system.n_x), self._viol_tol(viol_tol)
+        return self._mpc_step_batch(x_states, system, n_samples, box=(box, tol), **kw)
+
+    def _mpc_step_batch(self, x_states, system, n_samples, w=0.01, sample_fn="ddpm_cfg", n_wo_noise=0, ddim_steps=None,
+                        clamp_x0=False, seed=0, noise=None, select="argmin", decimals=4, clip_rule="chain", grouped=False,
+                        warm_start=None, reset=None, return_samples=False, allow_nonfinite=False, elites=None, box=None):
+        """mpc_step_batch and mpc_step_batch_box (box = (mpcd_state_box, tol), checked): one body, one kept prior set"""
         K = None if warm_start is None else int(warm_start)
         if elites is not None:
             if K is None:
@@ -1031,7 +1064,7 @@ class DiffusionMPC:
         H, d = self.spec.horizon, self.spec.state_dim
         kw = dict(system=system, n=n, w=w, sample_fn=sample_fn, n_wo_noise=n_wo_noise, ddim_steps=ddim_steps,
                   clamp_x0=clamp_x0, seed=seed, select=select, decimals=decimals, clip_rule=clip_rule, grouped=grouped,
-                  return_samples=return_samples, elites=elites)
+                  return_samples=return_samples, elites=elites, box=box)
         priors = getattr(self, "_batch_priors", None) if K is not None else None
         if priors is not None and priors.shape[0] != M:
             priors = None  # the fleet changed size: a cold start
@@ -1069,12 +1102,20 @@ class DiffusionMPC:
             if elites is not None:
                 res.elite_index = np.empty((M, elites), dtype=np.int64)
                 res.elite_cost = np.empty((M, elites))
+            if box is not None:
+                res.violation, res.n_feasible = np.empty(M), np.empty(M, dtype=np.int64)
+                if elites is not None:
+                    res.elite_violation = np.empty((M, elites))
             for idx, tidx, sub in ((ic, tc, rc_), (iw, tw, rw_)):
                 res.u[idx], res.plan[idx], res.cost[idx], res.flags[idx] = sub.u, sub.plan, sub.cost, sub.flags
                 res.index[idx] = idx * n + (sub.index - np.arange(len(idx)) * n)
                 if elites is not None:
                     res.elite_cost[idx] = sub.elite_cost
                     res.elite_index[idx] = (idx * n)[:, None] + (sub.elite_index - (np.arange(len(idx)) * n)[:, None])
+                    if box is not None:
+                        res.elite_violation[idx] = sub.elite_violation
+                if box is not None:
+                    res.violation[idx], res.n_feasible[idx] = sub.violation, sub.n_feasible
                 if return_samples:
                     res.u_norm.view(M, n, H, d).index_copy_(0, tidx, sub.u_norm.view(len(idx), n, H, d))
         if K is not None:
@@ -1100,10 +1141,11 @@ class DiffusionMPC:
         self._batch_priors = priors
 
     def _batch_step_call(self, x, t_start, priors, noise, system, n, w, sample_fn, n_wo_noise, ddim_steps, clamp_x0,
-                         seed, select, decimals, clip_rule, grouped, return_samples, elites=None):
+                         seed, select, decimals, clip_rule, grouped, return_samples, elites=None, box=None):
         """One mpcd_mpc_step_batch call on the states x [M, n_x] (checked by mpc_step_batch): (BatchStepResult, whether
         the call returned MPCD_ENONFINITE). priors: device [M, H, d] read when t_start > 0 and refreshed, or None.
-        elites=k: mpcd_mpc_step_batch_elite, priors [M, n, H, d]."""
+        elites=k: mpcd_mpc_step_batch_elite, priors [M, n, H, d]. box = (mpcd_state_box, tol): mpcd_mpc_step_batch_box,
+        with or without elites."""
         x = np.ascontiguousarray(x)
         M = x.shape[0]
         H, d, B, dev = self.spec.horizon, self.spec.state_dim, M * n, self.device
@@ -1134,15 +1176,28 @@ class DiffusionMPC:
         a.x_host = x.ctypes.data
         a.result_host, a.u_host, a.plan_host = rec.ctypes.data, u.ctypes.data, plan.ctypes.data
         a.u_norm = u_norm.data_ptr() if u_norm is not None else None
+        e = None
         if elites is None:
             a.priors = priors.data_ptr() if priors is not None else None
-            rc = self._lib.mpcd_mpc_step_batch(self._ctx, ctypes.byref(a), self._stream())
         else:
             e = N.BatchEliteArgs()
             e.k = elites
             e.priors = priors.data_ptr() if priors is not None else None
             best = np.empty((M, elites), dtype=_BEST)
             e.elites_host = best.ctypes.data
+        if box is not None:
+            bx = N.BatchBoxArgs()
+            bx.box, bx.tol = ctypes.pointer(box[0]), box[1]
+            viol, nfeas = np.empty(M, dtype=np.float64), np.empty(M, dtype=np.int64)
+            bx.viol_host, bx.n_feasible_host = viol.ctypes.data, nfeas.ctypes.data
+            if elites is not None:
+                eviol = np.empty((M, elites), dtype=np.float64)
+                bx.elite_viol_host = eviol.ctypes.data
+            rc = self._lib.mpcd_mpc_step_batch_box(self._ctx, ctypes.byref(a), None if e is None else ctypes.byref(e),
+                                                   ctypes.byref(bx), self._stream())
+        elif e is None:
+            rc = self._lib.mpcd_mpc_step_batch(self._ctx, ctypes.byref(a), self._stream())
+        else:
             rc = self._lib.mpcd_mpc_step_batch_elite(self._ctx, ctypes.byref(a), ctypes.byref(e), self._stream())
         if rc != N.MPCD_ENONFINITE:
             N.check(rc, "mpcd_mpc_step_batch")
@@ -1150,6 +1205,10 @@ class DiffusionMPC:
                               flags=rec["flags"].copy(), u_norm=u_norm)
         if elites is not None:
             res.elite_index, res.elite_cost = best["index"].copy(), best["cost"].copy()
+        if box is not None:
+            res.violation, res.n_feasible = viol, nfeas
+            if elites is not None:
+                res.elite_violation = eviol
         return res, rc == N.MPCD_ENONFINITE
 
     def mpc_step(self, x0, system: System, n_samples, w=0.01, sample_fn="ddpm_cfg", n_wo_noise=0, ddim_steps=None,

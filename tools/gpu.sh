@@ -15,6 +15,9 @@
 #   sqpmc[:<B>]        SQ instruction / wait / MFMA-busy counters of the cfg2 bench at B candidates (two passes)
 #                                                                         -> gpurun_out/prof/sqpmc_<B>_*
 #   l2pmc[:<workload>]  L1->L2 read requests and L2 hit / miss counters of that bench -> gpurun_out/prof/l2pmc_*
+#   boxab               tools/batch_box_ab.py: the batched external step with and without a state box, against a
+#                       build of the parent commit ($PARENT_LIB, default libmpcd_parent.so beside the product library);
+#                       the table goes to standard output, extra arguments come from $AB_ARGS
 #
 # Extra bench.py arguments for bench / trace / pmc come from $BENCH_ARGS; extra pytest arguments from
 # $PYTEST_ARGS; extra unet_perf.py arguments from $UNET_ARGS.
@@ -85,6 +88,9 @@ run_job() {
           > "gpurun_out/prof/sqpmc_${b}_$i.log" 2>&1 || return $?
         i=$((i + 1))
       done ;;
+    boxab)
+      timeout -k 10 900 python -u tools/batch_box_ab.py \
+        --parent-lib "${PARENT_LIB:-mpc_via_diffusion_model_amd/libmpcd_parent.so}" $AB_ARGS ;;
     unet)
       local c=${arg:-cfg5}
       timeout -k 10 600 python -u tools/unet_perf.py ${UARGS[$c]} $UNET_ARGS > "gpurun_out/unet_$c.log" 2>&1 ;;
