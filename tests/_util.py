@@ -1,4 +1,5 @@
 """Shared helpers for the parity tests (oracle side + tolerance checks)."""
+import contextlib
 import os
 
 import numpy as np
@@ -69,6 +70,34 @@ class Spread(float):
     jitter = None
 
 
+def _layers_round_from_fp64():
+    """every Linear / Conv1d / ConvTranspose1d / GroupNorm computes in fp64 and rounds its output to fp32 once"""
+    import torch.nn as nn
+    import torch.nn.functional as F
+    nn.Linear.forward = lambda self, x: F.linear(x.double(), self.weight.double(), self.bias.double()).float()
+    nn.Conv1d.forward = lambda self, x: F.conv1d(x.double(), self.weight.double(), self.bias.double(),
+                                                 self.stride, self.padding).float()
+    nn.ConvTranspose1d.forward = lambda self, x: F.conv_transpose1d(x.double(), self.weight.double(),
+                                                                    self.bias.double(), self.stride,
+                                                                    self.padding).float()
+    nn.GroupNorm.forward = lambda self, x: F.group_norm(x.double(), self.num_groups, self.weight.double(),
+                                                        self.bias.double(), self.eps).float()
+
+
+@contextlib.contextmanager
+def oracle_fp64_layers():
+    """The oracle with the perturbation oracle_sensitivity applies, as a context: inside it every Linear / Conv /
+    ConvTranspose / GroupNorm of the oracle's nets computes in fp64, forward and (through autograd) backward. The
+    higher-precision reference of the training step's loss and gradients."""
+    import torch.nn as nn
+    saved = (nn.Linear.forward, nn.Conv1d.forward, nn.ConvTranspose1d.forward, nn.GroupNorm.forward)
+    _layers_round_from_fp64()
+    try:
+        yield
+    finally:
+        nn.Linear.forward, nn.Conv1d.forward, nn.ConvTranspose1d.forward, nn.GroupNorm.forward = saved
+
+
 def oracle_sensitivity(run, seeds=SENSITIVITY_SEEDS):
     """Elementwise spread of the oracle itself when every Linear / Conv / GroupNorm rounds from fp64 instead of fp32
     (a 1-ulp-level perturbation). Unclamped DDIM is ill-conditioned (x0 = a*x - b*eps with a, b up to 2.6e6 at N=100),
@@ -76,19 +105,9 @@ def oracle_sensitivity(run, seeds=SENSITIVITY_SEEDS):
     recorded GPU runs) the spread under each seeded random half-ulp rounding of every layer output (x (1 + 2^-24 u),
     u ~ U(-1, 1) per element) is measured too, and its maximum logged beside the bar's anchor."""
     import torch.nn as nn
-    import torch.nn.functional as F
     ref = run()
     saved = (nn.Linear.forward, nn.Conv1d.forward, nn.ConvTranspose1d.forward, nn.GroupNorm.forward)
-
-    def with_fp64():
-        nn.Linear.forward = lambda self, x: F.linear(x.double(), self.weight.double(), self.bias.double()).float()
-        nn.Conv1d.forward = lambda self, x: F.conv1d(x.double(), self.weight.double(), self.bias.double(),
-                                                     self.stride, self.padding).float()
-        nn.ConvTranspose1d.forward = lambda self, x: F.conv_transpose1d(x.double(), self.weight.double(),
-                                                                        self.bias.double(), self.stride,
-                                                                        self.padding).float()
-        nn.GroupNorm.forward = lambda self, x: F.group_norm(x.double(), self.num_groups, self.weight.double(),
-                                                            self.bias.double(), self.eps).float()
+    with_fp64 = _layers_round_from_fp64
 
     def with_jitter(seed):
         g = torch.Generator().manual_seed(seed)
@@ -129,4 +148,5 @@ def unnormalize_np(x, mn, mx):
     return h * (mx - mn) + mn
 
 
-__all__ = ["nets", "sampler", "schedule", "make_mlp", "make_unet", "assert_traj_close", "unnormalize_np", "oracle_sensitivity"]
+__all__ = ["nets", "sampler", "schedule", "make_mlp", "make_unet", "assert_traj_close", "unnormalize_np", "oracle_sensitivity",
+           "oracle_fp64_layers"]
