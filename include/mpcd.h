@@ -228,6 +228,11 @@ enum mpcd_cost_kind {
     MPCD_COST_CALMPC = 1,        /* calMPCCost quirks (Cart_Diffusion_inference.py:247-283) */
 };
 
+/* The system a rollout call computes with. No constant of a system is compiled in: the dynamics read params, the cost
+ * reads the weights and the set-point, as given on that call. Two rules say what is NOT read:
+ *  - entries of Q, P and x_ref at index >= n_x and entries of R at index >= n_u are ignored, whatever they hold;
+ *  - MPCD_COST_CALMPC ignores x_ref altogether (calMPCCost costs the state itself, x^T Q x), while MPCD_COST_CANONICAL
+ *    costs e = x - x_ref in every stage and in the terminal term. The dynamics never read x_ref. */
 typedef struct {
     int32_t system;      /* mpcd_system */
     int32_t cost_kind;   /* mpcd_cost_kind */

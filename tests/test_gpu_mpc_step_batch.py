@@ -17,6 +17,7 @@ from oracle import sampler as osam
 from oracle import schedule as osch
 from oracle import systems as osys
 
+from ._systems_ref import TAIL_DESCRIPTORS
 from ._util import assert_traj_close, make_mlp, make_unet
 
 pytestmark = pytest.mark.gpu
@@ -123,7 +124,10 @@ def test_equals_closed_loop_small_unet_layered():
 def test_every_system_and_cost_kind(name):
     """the tail's other five instantiations (cartpole_lin5 costs with calMPCCost): a net of the system's sizes, Philox
     noise, two waves with a tail per state, a warm sequence so that the priors are the tail's"""
-    sysm = systems.get(name)
+    _system_case(systems.get(name))
+
+
+def _system_case(sysm):
     d, Cx, Hs, M, n = sysm.n_u, sysm.n_x, 32 // min(sysm.n_u, 2), 3, 80
     net = make_mlp(d, Hs, Cx, seed=9)
     plan = DiffusionMPC(NetSpec("mlp", d, Hs, Cx), net.state_dict(), variance_schedule="exponential",
@@ -131,6 +135,14 @@ def test_every_system_and_cost_kind(name):
     x0 = np.random.default_rng(4).uniform(-0.3, 0.3, (M, Cx))
     ref, out = _steps_vs_loop(plan, M, n, None, sysm=sysm, x0=x0, seed=2, warm_start=5, check=_check_plan)
     assert np.isfinite(ref.cost).all()
+
+
+@pytest.mark.parametrize("which", sorted(TAIL_DESCRIPTORS))
+def test_non_default_descriptor(which):
+    """the same harness at a descriptor that is not the registry's (tests/_systems_ref.py: every constant distinct and
+    non-zero, a set-point that is non-zero everywhere; the nonlinear cart-pole under calMPCCost): the tail and the
+    composed calls take the descriptor through different arguments, and here a slip in either shows"""
+    _system_case(TAIL_DESCRIPTORS[which]())
 
 
 # ---- 2. warm start

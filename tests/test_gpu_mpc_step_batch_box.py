@@ -18,6 +18,7 @@ import torch
 from mpc_via_diffusion_model_amd import DiffusionMPC, NetSpec, systems
 from mpc_via_diffusion_model_amd import _native as N
 
+from ._systems_ref import TAIL_DESCRIPTORS
 from ._util import make_mlp
 from .test_gpu_mpc_step_batch_elites import (D, H, K, NSTEPS, T, _c_args, _cost_ref, _di, _e_args, _new_plan, _noises,
                                               _plan, _ptr, _x0)
@@ -349,7 +350,19 @@ def test_every_system_and_cost_kind(name):
     """the tail's six instantiations against the composed device path on the returned samples: rollout_cost_box +
     topk_feasible + control_step_picked, pinned to the host reference by their own tests (calMPCCost's visited-state set
     with them). The bounds are the medians of the excursions that path itself reports (V under a box of width 0)."""
-    sysm = systems.get(name)
+    _system_case(systems.get(name))
+
+
+@pytest.mark.parametrize("which", sorted(TAIL_DESCRIPTORS))
+def test_non_default_descriptor(which):
+    """the same harness at a descriptor that is not the registry's (tests/_systems_ref.py: every constant distinct and
+    non-zero, a set-point that is non-zero everywhere; the nonlinear cart-pole under calMPCCost, whose visited states
+    are x_1 .. x_{H-2})"""
+    _system_case(TAIL_DESCRIPTORS[which]())
+
+
+def _system_case(sysm):
+    name = sysm.name
     d, Cx, Hs, M, n, k = sysm.n_u, sysm.n_x, 32 // min(sysm.n_u, 2), 3, 35, 4
     net = make_mlp(d, Hs, Cx, seed=9)
     plan = DiffusionMPC(NetSpec("mlp", d, Hs, Cx), net.state_dict(), variance_schedule="exponential",

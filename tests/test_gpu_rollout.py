@@ -189,12 +189,25 @@ def test_native_step_equals_composed_step(B, sample_fn, dtype):
     (the last rollout workgroup is partial). DDIM leaves the clip flag live (no provable bound). f16x2 DDPM: the
     fp16 kernel computes the context row's projection inside its launch (no ctx prologue) and must match the
     composed step, which runs the prologue kernel."""
+    _native_vs_composed_step(B, sample_fn, dtype, systems.double_int2d())
+
+
+@pytest.mark.parametrize("sample_fn", ["ddpm_cfg", "ddim_cfg"])
+@pytest.mark.parametrize("dtype", ["f32x3", "f16x2"])
+def test_native_step_equals_composed_step_perturbed_descriptor(sample_fn, dtype):
+    """The same comparison at a double_int2d descriptor that is not the registry's (tests/_systems_ref.py: dt and
+    dt^2 / 2 scaled independently, every weight distinct, a non-zero set-point): the fused step takes the descriptor
+    through mpcd_step_args, the composed one through mpcd_rollout_cost. B = 100: a partial last workgroup."""
+    from ._systems_ref import perturbed
+    _native_vs_composed_step(100, sample_fn, dtype, perturbed("double_int2d", 1))
+
+
+def _native_vs_composed_step(B, sample_fn, dtype, sysm):
     d, H, C = 2, 32, 4
     net = make_mlp(d, H, C, seed=5)
     plan = DiffusionMPC(NetSpec("mlp", d, H, C, dtype=dtype), net.state_dict(), n_diffusion_steps=25,
                         action_limits=(np.array([-2.0, -0.5]), np.array([2.0, 0.5])))
     x0 = np.array([0.4, -0.3, 0.2, -0.1])
-    sysm = systems.double_int2d()
     a = plan.mpc_step(x0, sysm, B, sample_fn=sample_fn, seed=7, native=False)
     b = plan.mpc_step(x0, sysm, B, sample_fn=sample_fn, seed=7, native=True)
     assert torch.equal(a.u_norm, b.u_norm)
