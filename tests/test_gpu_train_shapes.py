@@ -19,14 +19,11 @@ from mpc_via_diffusion_model_amd.training import DiffusionTrainer
 from oracle import layers as olayers
 from oracle import nets
 from oracle import schedule as osch
-from oracle.train import OracleTrainer
 
-from ._util import ABS_ELEM, SPREAD_X, oracle_fp64_layers
+from ._train_util import REL_GRAD, REL_LOSS, _assert_grads, _errors, _inputs, _oracle_grads
+from ._util import ABS_ELEM, SPREAD_X
 
 pytestmark = pytest.mark.gpu
-
-REL_LOSS = 1e-5
-REL_GRAD = 1e-4
 
 
 def _net(kind, d, H, C, base, mults, seed=0):
@@ -34,57 +31,6 @@ def _net(kind, d, H, C, base, mults, seed=0):
     if kind == "mlp":
         return nets.ConditionedMLPNet(state_dim=d, horizon=H, context_dim=C, dim=base, dim_mults=mults).train()
     return nets.ConditionedTemporalUnet(state_dim=d, context_dim=C, unet_input_dim=base, dim_mults=mults).train()
-
-
-def _inputs(d, H, C, B, n_steps, seed, top_tenth=False):
-    g = torch.Generator().manual_seed(seed)
-    x0 = torch.rand(B, H, d, generator=g) * 2 - 1
-    ctx = torch.rand(B, C, generator=g) * 2 - 1
-    lo = n_steps - n_steps // 10 if top_tenth else 0
-    t = torch.randint(lo, n_steps, (B,), generator=g).long()
-    noise = torch.randn(B, H, d, generator=g)
-    mask = torch.bernoulli(torch.full((B, 1), 0.25), generator=g)
-    return x0, ctx, t, noise, mask
-
-
-def _oracle_grads(net, tables, batch, fp64=True):
-    """(loss, {name: gradient}) of the oracle on the CPU; fp64: with the layers computing in fp64"""
-    orc = OracleTrainer(net, tables)
-    net.zero_grad(set_to_none=True)
-    if fp64:
-        with oracle_fp64_layers():
-            loss = orc.loss(*batch)
-            loss.backward()
-    else:
-        loss = orc.loss(*batch)
-        loss.backward()
-    return float(loss.detach()), {n: p.grad.detach().clone() for n, p in net.named_parameters()}
-
-
-def _errors(grads, ref):
-    """per tensor (norm-relative, elementwise relative to max|ref|) errors; exact zeros checked here"""
-    out = {}
-    for n, r in ref.items():
-        got = grads[n]
-        assert torch.isfinite(got).all(), n
-        if float(r.abs().max()) == 0.0:
-            assert float(got.abs().max()) == 0.0, n
-            continue
-        dlt = (got.double() - r.double())
-        out[n] = (float(dlt.norm() / r.double().norm()), float(dlt.abs().max() / r.double().abs().max()))
-    return out
-
-
-def _assert_grads(grads, ref, what, bars=None):
-    errs = _errors(grads, ref)
-    wn = max((e[0], n) for n, e in errs.items())
-    we = max((e[1], n) for n, e in errs.items())
-    print(f"{what}: worst gradient tensor norm-rel {wn[0]:.3e} ({wn[1]}), elementwise {we[0]:.3e} ({we[1]})")
-    for n, (en, ee) in errs.items():
-        bn, be = (REL_GRAD, ABS_ELEM) if bars is None else bars[n]
-        assert en <= bn, (what, n, en, bn)
-        assert ee <= be, (what, n, ee, be)
-    return wn[0], we[0]
 
 
 CASES = [
