@@ -384,6 +384,47 @@ int mpcd_control_step_picked(mpcd_ctx *ctx, const mpcd_system_desc *sys, double 
                              const int32_t *flags_dev, int32_t decimals, double *u_applied, int64_t *best_index,
                              double *best_cost, void *hip_stream);
 
+/* ---- Constraint set: linear rows and input-rate bounds beside the state box. The violation V above is the box's; a
+ * constraint set generalises its producer and nothing else: the feasibility-first order, tol, n_feasible and every
+ * consumer of V (mpcd_topk_feasible, mpcd_control_step_picked, mpcd_shift_plans / mpcd_elite_priors on the ranked list,
+ * MPCD_STEP_INFEASIBLE) are unchanged.
+ *
+ * The tests run where the box is tested: each time the dynamics step produces a state inside the candidate's cost
+ * evaluation, on the pair (x_{k+1}, u_k) of the new state and the input that produced it: MPCD_COST_CANONICAL k = 0 ..
+ * H-1; MPCD_COST_CALMPC k = 0 .. H-3 (the quirk above). u is the unnormalised, clipped input in fp64 (exact from fp32).
+ * Excesses, all fp64, no contraction:
+ *   box       as above.
+ *   row r < n_rows   s = A[r][0]*x[0]; s = s + A[r][i]*x[i] for i = 1 .. n_x-1 in that order; s = s + C[r][j]*u[j] for
+ *             j = 0 .. n_u-1 in that order; the excess is s - b[r]. The order is part of the contract (it makes V
+ *             reproducible bit for bit). Entries at i >= n_x and j >= n_u are ignored. b[r] = +inf switches a row off.
+ *   rate, input j < n_u   fabs(u_k[j] - u_{k-1}[j]) - du_max[j] for every visited k that has a predecessor; +inf =
+ *             unbounded. For k = 0 the predecessor is the caller's previous applied action u_prev of that plant state, if
+ *             one is given; a u_prev row with a NaN in any entry means "no previous input" (a restarted episode in a
+ *             batch): that state's rate test starts at k = 1.
+ * V = max(0, every excess above); an excess that is NaN (a NaN state or input, inf - inf, 0 * inf) makes V = +inf. A
+ * maximum has no order, so for the systems without sin / cos V is exact. */
+#define MPCD_MAX_CON_ROWS 8
+typedef struct {
+    mpcd_state_box box;                 /* rules unchanged; all-infinite = no box */
+    int32_t n_rows;                     /* 0 .. MPCD_MAX_CON_ROWS */
+    int32_t reserved;                   /* 0 */
+    double A[MPCD_MAX_CON_ROWS][12];    /* row r: sum_i A[r][i] x[i] + sum_j C[r][j] u[j] <= b[r] */
+    double C[MPCD_MAX_CON_ROWS][4];
+    double b[MPCD_MAX_CON_ROWS];        /* +inf switches a row off */
+    double du_max[4];                   /* |u_k[j] - u_{k-1}[j]| <= du_max[j]; +inf = unbounded */
+} mpcd_constraints;
+
+/* mpcd_rollout_cost_box with the set (rollout_cost_constr_kernel, csrc/rollout.hip): cost_out [batch] stays bit for
+ * bit mpcd_rollout_cost_grouped's, viol_out [batch] is each candidate's V over the set. u_prev_dev: dev fp64
+ * [batch / group][n_u], each plant state's previous applied action, or NULL (no state has one). With n_rows = 0 and an
+ * infinite du_max the call writes mpcd_rollout_cost_box's bits. MPCD_EINVAL: mpcd_rollout_cost_box's cases (the box's
+ * included); con NULL; n_rows outside [0, MPCD_MAX_CON_ROWS]; reserved != 0; a NaN or infinite coefficient in a used
+ * row's A[r][i < n_x] / C[r][j < n_u]; a NaN or -inf in a used b[r]; a NaN or negative du_max[j < n_u]. */
+int mpcd_rollout_cost_constr(mpcd_ctx *ctx, const mpcd_system_desc *sys, const double *x0_dev, int64_t group,
+                             const float *u_norm, const float *umin_host, const float *umax_host, int64_t batch,
+                             int32_t horizon, const int32_t *flags_dev, const mpcd_constraints *con,
+                             const double *u_prev_dev, double *cost_out, double *viol_out, void *hip_stream);
+
 /* ---- The whole closed loop in one call. mpcd_closed_loop enqueues, on hip_stream and without a host synchronisation,
  * what DiffusionMPC.closed_loop composes from the entry points above: one mpcd_normalize_states launch for iteration
  * 0, then per iteration the sampler and ONE launch (closed_loop_tail_kernel, csrc/rollout.hip) for everything else:
@@ -554,6 +595,33 @@ typedef struct {
 int mpcd_mpc_step_batch_box(mpcd_ctx *ctx, const mpcd_batch_step_args *args,
                             const mpcd_batch_elite_args *elite /* NULL: winner only */, const mpcd_batch_box_args *box,
                             void *hip_stream);
+
+/* mpcd_mpc_step_batch_box with a constraint set ("Constraint set" above) in place of the box: the same shape of call -
+ * one state upload, the sampler, ONE tail launch (batch_step_box_tail_kernel<SYS, ConTolK>, csrc/rollout.hip), with elites the one
+ * mpcd_elite_priors launch, one download, one synchronisation. u_prev_host rides the pinned staging block and the single
+ * host-to-device copy of the states: [M][n_x], then [M][n_u].
+ * Everything mpcd_mpc_step_batch_box promises holds with mpcd_rollout_cost_constr in place of mpcd_rollout_cost_box:
+ * for the same samples, states, clip flags, set and u_prev, the index, cost, V and n_feasible of every state, the ranked
+ * lists and their V are bit for bit entries 0..k of mpcd_rollout_cost_constr followed by mpcd_topk_feasible(k, tol); u0
+ * and the plan are mpcd_control_step_picked's; the next priors mpcd_shift_plans' / mpcd_elite_priors(shift = 1)'s;
+ * MPCD_STEP_INFEASIBLE is set exactly when n_feasible_host[m] == 0. A set that is only a box gives
+ * mpcd_mpc_step_batch_box's results, an all-infinite set mpcd_mpc_step_batch's / _elite's, bit for bit.
+ * MPCD_EINVAL / MPCD_EUNSUP: mpcd_mpc_step_batch_box's cases (con and con->con for box and box->box), plus
+ * mpcd_rollout_cost_constr's for the set. */
+typedef struct {
+    const mpcd_constraints *con;  /* host */
+    double tol;                   /* mpcd_topk_feasible's tol */
+    const double *u_prev_host;    /* host [M][n_u] or NULL: each state's previous applied action (NaN row: none) */
+    double *viol_host;            /* host [M] */
+    int64_t *n_feasible_host;     /* host [M] */
+    double *elite_viol_host;      /* host [M][k] or NULL (with elite != NULL) */
+    int32_t reserved, reserved2;  /* 0 */
+} mpcd_batch_constr_args;
+/* The workspace is mpcd_mpc_step_batch's (which does not grow for this call either); the counters are the same
+ * self-resetting ones, so the four calls may alternate on one context. */
+int mpcd_mpc_step_batch_constr(mpcd_ctx *ctx, const mpcd_batch_step_args *args,
+                               const mpcd_batch_elite_args *elite /* NULL: winner only */,
+                               const mpcd_batch_constr_args *con, void *hip_stream);
 
 /* ---- Candidate-batch data parallelism over RCCL / xGMI. One process per GPU, one
  * communicator per context; rank r owns global candidates [r*B_local, (r+1)*B_local). The reference has

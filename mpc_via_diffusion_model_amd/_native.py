@@ -24,7 +24,8 @@ MPCD_CLIP_CHAIN, MPCD_CLIP_FINAL, MPCD_CLIP_NONE = 0, 1, 2
 _STATUS = {-1: "EINVAL", -2: "EHIP", -3: "ESTATE", -4: "ENOMEM", -5: "EUNSUP", -6: "ENONFINITE"}
 MPCD_ENONFINITE = -6
 MPCD_STEP_CLIPPED, MPCD_STEP_NAN_SAMPLES, MPCD_STEP_NONFINITE_WINNER, MPCD_STEP_F32X3_RERUN = 1, 2, 4, 8
-MPCD_STEP_INFEASIBLE = 16  # mpcd_mpc_step_batch_box: no candidate of the state has V <= tol
+MPCD_STEP_INFEASIBLE = 16  # mpcd_mpc_step_batch_box / _constr: no candidate of the state has V <= tol
+MPCD_MAX_CON_ROWS = 8
 
 
 class NetDesc(ctypes.Structure):
@@ -55,6 +56,12 @@ class Best(ctypes.Structure):
 
 class StateBox(ctypes.Structure):
     _fields_ = [("lo", ctypes.c_double * 12), ("hi", ctypes.c_double * 12)]
+
+
+class ConstraintSet(ctypes.Structure):  # mpcd_constraints
+    _fields_ = [("box", StateBox), ("n_rows", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("A", ctypes.c_double * 12 * MPCD_MAX_CON_ROWS), ("C", ctypes.c_double * 4 * MPCD_MAX_CON_ROWS),
+                ("b", ctypes.c_double * MPCD_MAX_CON_ROWS), ("du_max", ctypes.c_double * 4)]
 
 
 class StepArgs(ctypes.Structure):
@@ -103,6 +110,12 @@ class BatchBoxArgs(ctypes.Structure):
     _fields_ = [("box", ctypes.POINTER(StateBox)), ("tol", ctypes.c_double), ("viol_host", ctypes.c_void_p),
                 ("n_feasible_host", ctypes.c_void_p), ("elite_viol_host", ctypes.c_void_p), ("reserved", ctypes.c_int32),
                 ("reserved2", ctypes.c_int32)]
+
+
+class BatchConstrArgs(ctypes.Structure):
+    _fields_ = [("con", ctypes.POINTER(ConstraintSet)), ("tol", ctypes.c_double), ("u_prev_host", ctypes.c_void_p),
+                ("viol_host", ctypes.c_void_p), ("n_feasible_host", ctypes.c_void_p),
+                ("elite_viol_host", ctypes.c_void_p), ("reserved", ctypes.c_int32), ("reserved2", ctypes.c_int32)]
 
 
 class TrainCfg(ctypes.Structure):
@@ -167,6 +180,10 @@ EXPORTS = {
                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                ctypes.c_void_p, ctypes.POINTER(StateBox), ctypes.c_void_p, ctypes.c_void_p,
                                ctypes.c_void_p], ctypes.c_int),
+    "mpcd_rollout_cost_constr": ([ctypes.c_void_p, ctypes.POINTER(SystemDesc), ctypes.c_void_p, ctypes.c_int64,
+                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                  ctypes.c_void_p, ctypes.POINTER(ConstraintSet), ctypes.c_void_p, ctypes.c_void_p,
+                                  ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "mpcd_topk_feasible": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                             ctypes.c_int32, ctypes.c_double, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                             ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
@@ -180,6 +197,8 @@ EXPORTS = {
                                    ctypes.c_void_p], ctypes.c_int),
     "mpcd_mpc_step_batch_box": ([ctypes.c_void_p, ctypes.POINTER(BatchStepArgs), ctypes.POINTER(BatchEliteArgs),
                                  ctypes.POINTER(BatchBoxArgs), ctypes.c_void_p], ctypes.c_int),
+    "mpcd_mpc_step_batch_constr": ([ctypes.c_void_p, ctypes.POINTER(BatchStepArgs), ctypes.POINTER(BatchEliteArgs),
+                                    ctypes.POINTER(BatchConstrArgs), ctypes.c_void_p], ctypes.c_int),
     "mpcd_comm_unique_id": ([ctypes.c_void_p], ctypes.c_int),
     "mpcd_comm_init": ([ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p], ctypes.c_int),
     "mpcd_philox_noise": ([ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,

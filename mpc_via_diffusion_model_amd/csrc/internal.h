@@ -234,6 +234,16 @@ struct BatchBoxTail : BatchEliteTail {
 };
 hipError_t launch_batch_box_tail(const mpcd_system_desc &d, const float *umin_host, const float *umax_host,
                                  const mpcd_state_box &box, double tol, const BatchBoxTail &t, hipStream_t stream);
+// The same step with a constraint set (rollout.hip batch_step_box_tail_kernel<SYS, ConTolK>, mpcd_mpc_step_batch_constr): the box
+// tail's argument block and result block; u_prev_dev [n_states][n_u] fp64 (a NaN row: none) or null.
+hipError_t launch_batch_constr_tail(const mpcd_system_desc &d, const float *umin_host, const float *umax_host,
+                                    const mpcd_constraints &con, double tol, const double *u_prev_dev,
+                                    const BatchBoxTail &t, hipStream_t stream);
+// launch_rollout_cost_box with a constraint set (mpcd.h "Constraint set"); u_prev_dev [batch / group][n_u] or null
+hipError_t launch_rollout_cost_constr(const mpcd_system_desc &d, const double *x0_dev, int64_t group, const float *u_norm,
+                                      const float *umin_host, const float *umax_host, const int *flags_dev, int64_t batch,
+                                      int H, const mpcd_constraints &con, const double *u_prev_dev, double *cost,
+                                      double *viol, hipStream_t stream);
 // Elite sets (elite.hip). launch_topk: out[m][0..k) = the k best of cost[m * group, (m + 1) * group), best first, in
 // rollout.hip's better() order, index = offset + position in cost[]; 1 <= k <= min(group, MPCD_MAX_ELITES).
 // mirror (n_groups == 1 only): the entries also written to mapped host memory, then *host_flag = host_seq after a

@@ -1225,6 +1225,45 @@ int mpcd_rollout_cost_box(mpcd_ctx *c, const mpcd_system_desc *sys, const double
     return MPCD_OK;
 }
 
+// The set's rules (mpcd.h "Constraint set") of every call that takes one
+static int check_constraints(const char *fn, const mpcd_constraints *con, int n_x, int n_u)
+{
+    int rc = check_state_box(fn, &con->box, n_x);
+    if (rc) return rc;
+    if (con->n_rows < 0 || con->n_rows > MPCD_MAX_CON_ROWS)
+        return fail(MPCD_EINVAL, "%s: n_rows %d outside [0, %d]", fn, con->n_rows, MPCD_MAX_CON_ROWS);
+    if (con->reserved) return fail(MPCD_EINVAL, "%s: constraints reserved %d != 0", fn, con->reserved);
+    for (int r = 0; r < con->n_rows; ++r) {
+        for (int i = 0; i < n_x; ++i)
+            if (!std::isfinite(con->A[r][i])) return fail(MPCD_EINVAL, "%s: A[%d][%d] = %g is not finite", fn, r, i, con->A[r][i]);
+        for (int j = 0; j < n_u; ++j)
+            if (!std::isfinite(con->C[r][j])) return fail(MPCD_EINVAL, "%s: C[%d][%d] = %g is not finite", fn, r, j, con->C[r][j]);
+        if (con->b[r] != con->b[r] || con->b[r] == -INFINITY)
+            return fail(MPCD_EINVAL, "%s: b[%d] = %g (use +inf to switch a row off)", fn, r, con->b[r]);
+    }
+    for (int j = 0; j < n_u; ++j)
+        if (!(con->du_max[j] >= 0.0))
+            return fail(MPCD_EINVAL, "%s: du_max[%d] = %g is negative or NaN (use +inf for unbounded)", fn, j, con->du_max[j]);
+    return MPCD_OK;
+}
+int mpcd_rollout_cost_constr(mpcd_ctx *c, const mpcd_system_desc *sys, const double *x0_dev, int64_t group,
+                             const float *u_norm, const float *umin, const float *umax, int64_t batch, int32_t horizon,
+                             const int32_t *flags, const mpcd_constraints *con, const double *u_prev_dev, double *cost,
+                             double *viol, void *stream_ptr)
+{
+    if (!c || !sys || !x0_dev || !u_norm || !umin || !umax || !flags || !con || !cost || !viol)
+        return fail(MPCD_EINVAL, "mpcd_rollout_cost_constr: null argument");
+    if (batch < 1 || horizon < 2 || group < 1 || batch % group)
+        return fail(MPCD_EINVAL, "mpcd_rollout_cost_constr: batch/group/horizon");
+    int rc = check_system(sys, horizon);
+    if (rc) return rc;
+    if ((rc = check_constraints("mpcd_rollout_cost_constr", con, sys->n_x, sys->n_u))) return rc;
+    DEVICE_GUARD(c->device);
+    HIP_TRY(launch_rollout_cost_constr(*sys, x0_dev, group, u_norm, umin, umax, flags, batch, horizon, *con, u_prev_dev,
+                                       cost, viol, static_cast<hipStream_t>(stream_ptr)));
+    return MPCD_OK;
+}
+
 int mpcd_control_step_picked(mpcd_ctx *c, const mpcd_system_desc *sys, double *x, int64_t n_states, const float *u_norm,
                              int64_t batch, int32_t horizon, const mpcd_best *picks, int64_t pick_stride, int64_t offset,
                              const float *umin, const float *umax, const int32_t *flags, int32_t decimals,
@@ -1435,19 +1474,39 @@ int mpcd_closed_loop(mpcd_ctx *c, const mpcd_closed_loop_args *a, void *stream_p
 // mpcd_mpc_step_batch and, ELITE, mpcd_mpc_step_batch_elite (e: its own arguments, else null): one host body. The
 // elite parts are compiled out of the plain call, which runs the statements it always ran. BOX:
 // mpcd_mpc_step_batch_box (bx: its own arguments), with or without elites; its parts are compiled out of the other two.
+// CON: mpcd_mpc_step_batch_constr (cx: its own arguments): the box call's result block, partial lists and counters
+// (VIOL = BOX or CON), the set in place of the box, and the states' previous actions behind the states in the one upload.
 extern "C++" {
-template <bool ELITE, bool BOX = false>
+template <bool ELITE, bool BOX = false, bool CON = false>
 static int batch_step_impl(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpcd_batch_elite_args *e, void *stream_ptr,
-                           const mpcd_batch_box_args *bx = nullptr)
+                           const mpcd_batch_box_args *bx = nullptr, const mpcd_batch_constr_args *cx = nullptr)
 {
-    constexpr const char *fn = BOX ? "mpcd_mpc_step_batch_box" : ELITE ? "mpcd_mpc_step_batch_elite" : "mpcd_mpc_step_batch";
+    static_assert(!(BOX && CON), "one producer of V");
+    constexpr bool VIOL = BOX || CON;
+    constexpr const char *fn = CON     ? "mpcd_mpc_step_batch_constr"
+                               : BOX   ? "mpcd_mpc_step_batch_box"
+                               : ELITE ? "mpcd_mpc_step_batch_elite"
+                                       : "mpcd_mpc_step_batch";
     if (!c || !a) return fail(MPCD_EINVAL, "null argument");
+    // what the box call and the constraint call take beside their box / set
+    double tol = 0.0, *viol_host = nullptr, *elite_viol_host = nullptr;
+    int64_t *n_feasible_host = nullptr;
     if constexpr (BOX) {
         if (!bx || !bx->box || !bx->viol_host || !bx->n_feasible_host) return fail(MPCD_EINVAL, "%s: null argument (box)", fn);
         if (bx->reserved || bx->reserved2)
             return fail(MPCD_EINVAL, "%s: box reserved %d / %d != 0", fn, bx->reserved, bx->reserved2);
-        if (!(bx->tol >= 0.0)) return fail(MPCD_EINVAL, "%s: tol %g is negative or NaN", fn, bx->tol);
-        if (!ELITE && bx->elite_viol_host) return fail(MPCD_EINVAL, "%s: elite_viol_host without elite", fn);
+        tol = bx->tol, viol_host = bx->viol_host, n_feasible_host = bx->n_feasible_host, elite_viol_host = bx->elite_viol_host;
+    }
+    if constexpr (CON) {
+        if (!cx || !cx->con || !cx->viol_host || !cx->n_feasible_host)
+            return fail(MPCD_EINVAL, "%s: null argument (constraints)", fn);
+        if (cx->reserved || cx->reserved2)
+            return fail(MPCD_EINVAL, "%s: constraints reserved %d / %d != 0", fn, cx->reserved, cx->reserved2);
+        tol = cx->tol, viol_host = cx->viol_host, n_feasible_host = cx->n_feasible_host, elite_viol_host = cx->elite_viol_host;
+    }
+    if constexpr (VIOL) {
+        if (!(tol >= 0.0)) return fail(MPCD_EINVAL, "%s: tol %g is negative or NaN", fn, tol);
+        if (!ELITE && elite_viol_host) return fail(MPCD_EINVAL, "%s: elite_viol_host without elite", fn);
         if (a->select_first)
             return fail(MPCD_EINVAL, "%s: select_first != 0 (the feasibility-first ranking needs the costs)", fn);
     }
@@ -1476,6 +1535,9 @@ static int batch_step_impl(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpc
     if constexpr (BOX) {
         if ((rc = check_state_box(fn, bx->box, g.nx))) return rc;
     }
+    if constexpr (CON) {
+        if ((rc = check_constraints(fn, cx->con, g.nx, g.nu))) return rc;
+    }
     const int nu = g.nu, nx = g.nx, row = g.row;
     const int64_t M = g.M, n = g.n, B = g.B;
     hipStream_t st = static_cast<hipStream_t>(stream_ptr);
@@ -1487,25 +1549,29 @@ static int batch_step_impl(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpc
     const int64_t rec_stride = batch_step_rec_stride(nu);
     const size_t plan_off = ((size_t)(M * rec_stride) + 255) & ~(size_t)255;
     // ELITE: the elites mpcd_best [M][k] follow the plans
-    const int64_t k = ELITE ? e->k : BOX ? 1 : 0;  // BOX without elites: a ranked list of one
-    // BOX: the selected candidates' V [M] and n_feasible [M] follow the plans, then the entries and their V [M][k]
+    const int64_t k = ELITE ? e->k : VIOL ? 1 : 0;  // VIOL without elites: a ranked list of one
+    // VIOL: the selected candidates' V [M] and n_feasible [M] follow the plans, then the entries and their V [M][k]
     const size_t viol_off = (plan_off + sizeof(float) * M * row + 255) & ~(size_t)255;
     const size_t nfeas_off = (viol_off + sizeof(double) * M + 255) & ~(size_t)255;
-    const size_t elite_off = BOX ? (nfeas_off + sizeof(int64_t) * M + 255) & ~(size_t)255 : viol_off;
+    const size_t elite_off = VIOL ? (nfeas_off + sizeof(int64_t) * M + 255) & ~(size_t)255 : viol_off;
     const size_t eviol_off = (elite_off + sizeof(mpcd_best) * M * k + 255) & ~(size_t)255;
-    const size_t res_bytes = BOX     ? eviol_off + sizeof(double) * M * k
+    const size_t res_bytes = VIOL    ? eviol_off + sizeof(double) * M * k
                              : ELITE ? elite_off + sizeof(mpcd_best) * M * k
                                      : plan_off + sizeof(float) * M * row;
-    const size_t x_bytes = sizeof(double) * M * nx;
+    // CON with u_prev: [M][n_u] behind the states, in the same staging block and the same copy
+    const size_t xs_bytes = sizeof(double) * M * nx;
+    bool with_prev = false;
+    if constexpr (CON) with_prev = cx->u_prev_host != nullptr;
+    const size_t x_bytes = xs_bytes + (with_prev ? sizeof(double) * M * nu : 0);
     const bool repeat_priors = !ELITE && a->warm_t_start > 0 && !g.grouped;  // ELITE: one per candidate already
     const size_t o_x = carve(x_bytes), o_pc = carve(sizeof(double) * M * g.wps), o_pr = carve(sizeof(double) * M * g.wps),
                  o_pi = carve(sizeof(int64_t) * M * g.wps), o_res = carve(res_bytes), o_u = carve(sizeof(float) * B * row),
                  o_amax = carve(g.chain_rule ? sizeof(float) * B : 0), o_ctx = carve(sizeof(float) * g.rows * nx),
                  o_ctx0 = carve(g.grouped ? 0 : sizeof(float) * M * nx),
                  o_prior = carve(repeat_priors ? sizeof(float) * B * row : 0),
-                 o_pe = carve(sizeof(mpcd_best) * M * g.wps * k),  // ELITE / BOX: the workgroups' ranked lists
-                 o_pv = carve(BOX ? sizeof(double) * M * g.wps * k : 0),  // BOX: their violations and feasible counts
-                 o_pn = carve(BOX ? sizeof(int64_t) * M * g.wps : 0);
+                 o_pe = carve(sizeof(mpcd_best) * M * g.wps * k),  // ELITE / VIOL: the workgroups' ranked lists
+                 o_pv = carve(VIOL ? sizeof(double) * M * g.wps * k : 0),  // VIOL: their violations and feasible counts
+                 o_pn = carve(VIOL ? sizeof(int64_t) * M * g.wps : 0);
     if ((rc = c->batch_ws.ensure(carve.off))) return rc;
     if ((rc = grow_counters(c->batch_cnt, M, st))) return rc;
     const size_t h_res = (x_bytes + 255) & ~(size_t)255, host_bytes = h_res + res_bytes;
@@ -1522,7 +1588,10 @@ static int batch_step_impl(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpc
     float *amax = g.chain_rule ? reinterpret_cast<float *>(w + o_amax) : nullptr;
     float *ctx = reinterpret_cast<float *>(w + o_ctx);
 
-    memcpy(hs, a->x_host, x_bytes);
+    memcpy(hs, a->x_host, xs_bytes);
+    if constexpr (CON) {
+        if (with_prev) memcpy(hs + xs_bytes, cx->u_prev_host, x_bytes - xs_bytes);
+    }
     HIP_TRY(hipMemcpyAsync(x_dev, hs, x_bytes, hipMemcpyHostToDevice, st));
     if ((rc = tail_context_rows(g, x_dev, a->ctx_min, a->ctx_max, reinterpret_cast<float *>(w + o_ctx0), ctx, st))) return rc;
     s.context = ctx;
@@ -1542,13 +1611,13 @@ static int batch_step_impl(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpc
     rc = sample_impl(c, &s, stream_ptr, nullptr, g.grouped ? n : 0, a->warm_t_start ? &warm : nullptr);
     if (rc) return rc;
 
-    std::conditional_t<BOX, BatchBoxTail, std::conditional_t<ELITE, BatchEliteTail, BatchStepTail>> t{};
+    std::conditional_t<VIOL, BatchBoxTail, std::conditional_t<ELITE, BatchEliteTail, BatchStepTail>> t{};
     fill_tail_common(t, g, u_norm, amax, x_dev, a->select_first, a->decimals, reinterpret_cast<double *>(w + o_pc),
                      reinterpret_cast<double *>(w + o_pr), reinterpret_cast<int64_t *>(w + o_pi), c->batch_cnt.as<unsigned>());
     t.result = w + o_res;
     t.rec_stride = rec_stride;
     t.plan_off = (int64_t)plan_off;
-    if constexpr (BOX) {
+    if constexpr (VIOL) {
         t.part_elite = reinterpret_cast<mpcd_best *>(w + o_pe);
         t.part_viol = reinterpret_cast<double *>(w + o_pv);
         t.part_nfeas = reinterpret_cast<int64_t *>(w + o_pn);
@@ -1558,7 +1627,11 @@ static int batch_step_impl(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpc
         t.eviol_off = (int64_t)eviol_off;
         t.k = (int32_t)k;
         if constexpr (!ELITE) t.prior_out = a->priors;  // written by the tail, as in the plain call
-        HIP_TRY(launch_batch_box_tail(*a->sys, a->act_min, a->act_max, *bx->box, bx->tol, t, st));
+        if constexpr (CON)
+            HIP_TRY(launch_batch_constr_tail(*a->sys, a->act_min, a->act_max, *cx->con, tol,
+                                             with_prev ? reinterpret_cast<const double *>(w + o_x + xs_bytes) : nullptr, t, st));
+        else
+            HIP_TRY(launch_batch_box_tail(*a->sys, a->act_min, a->act_max, *bx->box, tol, t, st));
         if constexpr (ELITE) {
             if (e->priors)  // the next priors, from the ranked list where the tail left it
                 HIP_TRY(launch_elite_priors(u_norm, M, n, g.H, nu, reinterpret_cast<const mpcd_best *>(w + o_res + elite_off),
@@ -1593,10 +1666,10 @@ static int batch_step_impl(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpc
     if constexpr (ELITE) {
         if (e->elites_host) memcpy(e->elites_host, hs + h_res + elite_off, sizeof(mpcd_best) * M * e->k);
     }
-    if constexpr (BOX) {
-        memcpy(bx->viol_host, hs + h_res + viol_off, sizeof(double) * M);
-        memcpy(bx->n_feasible_host, hs + h_res + nfeas_off, sizeof(int64_t) * M);
-        if (bx->elite_viol_host) memcpy(bx->elite_viol_host, hs + h_res + eviol_off, sizeof(double) * M * k);
+    if constexpr (VIOL) {
+        memcpy(viol_host, hs + h_res + viol_off, sizeof(double) * M);
+        memcpy(n_feasible_host, hs + h_res + nfeas_off, sizeof(int64_t) * M);
+        if (elite_viol_host) memcpy(elite_viol_host, hs + h_res + eviol_off, sizeof(double) * M * k);
     }
     if (bad)
         return fail(MPCD_ENONFINITE, "%s: %lld of %lld states have no candidate with a finite cost "
@@ -1620,6 +1693,13 @@ int mpcd_mpc_step_batch_box(mpcd_ctx *c, const mpcd_batch_step_args *a, const mp
                             const mpcd_batch_box_args *bx, void *stream_ptr)
 {
     return e ? batch_step_impl<true, true>(c, a, e, stream_ptr, bx) : batch_step_impl<false, true>(c, a, nullptr, stream_ptr, bx);
+}
+
+int mpcd_mpc_step_batch_constr(mpcd_ctx *c, const mpcd_batch_step_args *a, const mpcd_batch_elite_args *e,
+                               const mpcd_batch_constr_args *cx, void *stream_ptr)
+{
+    return e ? batch_step_impl<true, false, true>(c, a, e, stream_ptr, nullptr, cx)
+             : batch_step_impl<false, false, true>(c, a, nullptr, stream_ptr, nullptr, cx);
 }
 
 int mpcd_unnormalize(mpcd_ctx *c, const float *x, int64_t n_rows, int32_t dim, const float *mn, const float *mx,

@@ -267,10 +267,11 @@ __device__ __forceinline__ void stage_rows(const float *src, int64_t nvalid, int
 
 // The MPC cost of the normalised plan ur[H][nu] from the state x (overwritten), both cost kinds. The fp64 operations
 // and their order are the contract with the C oracle (-ffp-contract=off: no contraction changes a rounding).
-// visit(xn) sees every state dyn_step produces, right after the step (canonical: x_1 .. x_H; calMPCCost: x_1 ..
-// x_{H-2}, its loop applies u_0 .. u_{H-3}); the default sees nothing and compiles to nothing.
+// visit(xn, u) sees every state dyn_step produces, right after the step, with the input that produced it (canonical:
+// (x_1, u_0) .. (x_H, u_{H-1}); calMPCCost: (x_1, u_0) .. (x_{H-2}, u_{H-3}), its loop applies u_0 .. u_{H-3}); the
+// default sees nothing and compiles to nothing.
 struct NoVisit {
-    __device__ __forceinline__ void operator()(const double *) const {}
+    __device__ __forceinline__ void operator()(const double *, const double *) const {}
 };
 template <int SYS, class Visit = NoVisit>
 __device__ __forceinline__ double candidate_cost(const SysK &S, const float *ur, bool clip, double *x, int H,
@@ -292,7 +293,7 @@ __device__ __forceinline__ double candidate_cost(const SysK &S, const float *ur,
         double ucur = u[0];
         for (int i = 1; i < H - 1; ++i) {
             dyn_step<SYS>(S, x, &ucur, xn);
-            visit(xn);
+            visit(xn, &ucur);
             const double un = (double)unnorm1(ur[i * nu], clip, mn[0], mx[0]);
             for (int j = 1; j < nx; ++j) J = J + S.Q[j] * (xn[j] * xn[j]);
             J = J + S.R[0] * (un * un);
@@ -306,7 +307,7 @@ __device__ __forceinline__ double candidate_cost(const SysK &S, const float *ur,
         for (int k = 0; k < H; ++k) {
             for (int i = 0; i < nu; ++i) u[i] = (double)unnorm1(ur[k * nu + i], clip, mn[i], mx[i]);
             dyn_step<SYS>(S, x, u, xn);
-            visit(xn);
+            visit(xn, u);
             const double sx = k < H - 1 ? quadform<nx>(S.Q, xn, S.xr) : quadform<nx>(S.P, xn, S.xr);
             const double sv = quadform<nu>(S.R, u, zero);
             J = J + (sx + sv);
@@ -622,7 +623,7 @@ struct BoxVisit {
     const BoxK &box;
     double &V;   // starts at 0.0
     bool &bad;   // an excess was NaN
-    __device__ __forceinline__ void operator()(const double *xn) const
+    __device__ __forceinline__ void operator()(const double *xn, const double *) const
     {
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
@@ -655,6 +656,88 @@ __global__ __launch_bounds__(RT_THREADS) void rollout_cost_box_kernel(const SysK
     double V = 0.0;
     bool bad = false;
     const double J = candidate_cost<SYS>(S, su + (b - c0) * stride, clip, x, H, BoxVisit<nx>{box, V, bad});
+    if (c0 + threadIdx.x < batch) {
+        cost[b] = J;
+        viol[b] = BoxVisit<nx>::finish(V, bad);
+    }
+}
+
+// ---- Constraint set (mpcd.h "Constraint set"): the box, n_rows linear rows over (x_{k+1}, u_k) and per-input rate
+// bounds. A kernel argument of its own, like BoxK (about 1.3 KiB; with SysK well under the 4 KiB limit). The row loop
+// runs to the run-time, wave-uniform n_rows and reads its coefficients with scalar loads; the component loops are over
+// the compile-time NX / NU, so nothing per-lane is indexed dynamically.
+struct ConK {
+    BoxK box;
+    double A[MPCD_MAX_CON_ROWS][12], C[MPCD_MAX_CON_ROWS][4], b[MPCD_MAX_CON_ROWS];
+    double du[4];
+    int32_t n_rows, pad;
+};
+// BoxVisit with the rows and the rate test. up holds the previous input once has is set: the caller's u_prev before
+// the first visit (has = it is a real one), then every visited u. A row's sum is taken in the contract's order, A's
+// terms then C's, each product rounded on its own. NaN excesses are collected as in BoxVisit.
+template <int NX, int NU>
+struct ConstrVisit {
+    const ConK &con;
+    double &V;          // starts at 0.0
+    bool &bad;          // an excess was NaN
+    double (&up)[NU];
+    bool &has;
+    __device__ __forceinline__ void operator()(const double *xn, const double *u) const
+    {
+        BoxVisit<NX>{con.box, V, bad}(xn, u);
+        for (int r = 0; r < con.n_rows; ++r) {
+            double s = con.A[r][0] * xn[0];
+#pragma unroll
+            for (int i = 1; i < NX; ++i) s = s + con.A[r][i] * xn[i];
+#pragma unroll
+            for (int j = 0; j < NU; ++j) s = s + con.C[r][j] * u[j];
+            const double e = s - con.b[r];
+            bad |= e != e;
+            V = fmax(V, e);
+        }
+#pragma unroll
+        for (int j = 0; j < NU; ++j) {
+            const double e = has ? fabs(u[j] - up[j]) - con.du[j] : 0.0;
+            bad |= e != e;
+            V = fmax(V, e);
+            up[j] = u[j];
+        }
+        has = true;
+    }
+    // the previous applied action of plant state m, or none: u_prev null, or a NaN in any entry of the row
+    __device__ __forceinline__ static bool load_prev(const double *u_prev, int64_t m, double (&up)[NU])
+    {
+        bool has = u_prev != nullptr;
+#pragma unroll
+        for (int j = 0; j < NU; ++j) {
+            up[j] = u_prev ? u_prev[m * NU + j] : 0.0;
+            has = has && up[j] == up[j];
+        }
+        return has;
+    }
+};
+// rollout_cost_box_kernel with the set (mpcd_rollout_cost_constr): the same cost, hence the same bits
+template <int SYS>
+__global__ __launch_bounds__(RT_THREADS) void rollout_cost_constr_kernel(const SysK S, const ConK con, const float *u_norm,
+                                                                         const int *flags, const double *x0_dev,
+                                                                         const double *u_prev, int64_t group,
+                                                                         int64_t batch, int H, double *cost, double *viol)
+{
+    constexpr int nx = SysDim<SYS>::NX, nu = SysDim<SYS>::NU;
+    extern __shared__ float su[];  // [RT_THREADS][H*nu + 1]
+    const int row = H * nu, stride = row + 1;
+    const int64_t c0 = (int64_t)blockIdx.x * RT_THREADS;
+    stage_rows(u_norm + (size_t)c0 * row, min((int64_t)RT_THREADS, batch - c0), row, su);
+    __syncthreads();
+    const int64_t b = min(c0 + threadIdx.x, batch - 1);  // lanes past the batch recompute the last one
+    const bool clip = flags[b / group] == 1;
+    double x[nx], up[nu];
+#pragma unroll
+    for (int i = 0; i < nx; ++i) x[i] = x0_dev[(b / group) * nx + i];
+    bool has = ConstrVisit<nx, nu>::load_prev(u_prev, b / group, up);
+    double V = 0.0;
+    bool bad = false;
+    const double J = candidate_cost<SYS>(S, su + (b - c0) * stride, clip, x, H, ConstrVisit<nx, nu>{con, V, bad, up, has});
     if (c0 + threadIdx.x < batch) {
         cost[b] = J;
         viol[b] = BoxVisit<nx>::finish(V, bad);
@@ -1116,8 +1199,20 @@ struct BoxTolK {
 // and writes: the record (MPCD_STEP_INFEASIBLE iff the sum is 0), u0, the selected candidate's V and n_feasible, the k
 // ranked entries with their V (bit for bit mpcd_topk_feasible over mpcd_rollout_cost_box), the plan and, with
 // prior_out (no elites), the next prior by shift_plan_kernel's rule. No cost or violation array goes through memory.
-template <int SYS>
-__global__ __launch_bounds__(RT_THREADS) void batch_step_box_tail_kernel(const SysK S, const BoxTolK C, const BatchBoxTail T)
+// The constraint-set tail (mpcd_mpc_step_batch_constr) is the instantiation <SYS, ConTolK> of this same kernel: C is
+// then the set, the tolerance and the states' previous applied actions (dev [n_states][n_u] or null), again a kernel
+// argument of their own, so the SysK and tail argument blocks stay as they are, and ConstrVisit rides candidate_cost
+// (the bits rollout_cost_constr_kernel writes). The lines that choose the visitor are all the two differ in. They are
+// one kernel template and not two kernels around a shared __device__ body: inlined from such a body the box
+// instantiations come out with another register allocation (3,905 against 3,869 lines for <3>, more SGPR spills to
+// lanes), as the control tails above did; this way <SYS, BoxTolK> is the former kernel instruction for instruction.
+struct ConTolK {
+    ConK con;
+    double tol;
+    const double *u_prev;
+};
+template <int SYS, class ConArg = BoxTolK>
+__global__ __launch_bounds__(RT_THREADS) void batch_step_box_tail_kernel(const SysK S, const ConArg C, const BatchBoxTail T)
 {
     constexpr int nx = SysDim<SYS>::NX, nu = SysDim<SYS>::NU;
     extern __shared__ float su[];  // [RT_THREADS][H*nu + 1]
@@ -1136,9 +1231,15 @@ __global__ __launch_bounds__(RT_THREADS) void batch_step_box_tail_kernel(const S
     double x[nx];
 #pragma unroll
     for (int i = 0; i < nx; ++i) x[i] = T.x_dev[m * nx + i];
-    double Vacc = 0.0;
+    double Vacc = 0.0, J;
     bool bad = false;
-    const double J = candidate_cost<SYS>(S, su + (b - c0) * stride, clip, x, H, BoxVisit<nx>{C.box, Vacc, bad});
+    if constexpr (std::is_same<ConArg, ConTolK>::value) {
+        double up[nu];
+        bool has = ConstrVisit<nx, nu>::load_prev(C.u_prev, m, up);
+        J = candidate_cost<SYS>(S, su + (b - c0) * stride, clip, x, H, ConstrVisit<nx, nu>{C.con, Vacc, bad, up, has});
+    } else {
+        J = candidate_cost<SYS>(S, su + (b - c0) * stride, clip, x, H, BoxVisit<nx>{C.box, Vacc, bad});
+    }
     const double tol = C.tol;
     const double V = BoxVisit<nx>::finish(Vacc, bad);  // never NaN: a NaN excess is +inf
     const double v = isnan(J) ? INFINITY : J;
@@ -1222,7 +1323,6 @@ __global__ __launch_bounds__(RT_THREADS) void batch_step_box_tail_kernel(const S
         if (po) po[q] = wr[min(h + 1, H - 1) * nu + e];
     }
 }
-
 __global__ __launch_bounds__(256) void repeat_rows_kernel(const float *rows, int64_t total, int64_t n, int row_len, float *out)
 {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
@@ -1329,21 +1429,78 @@ hipError_t launch_batch_elite_tail(const mpcd_system_desc &d, const float *umin_
     });
 }
 
+// The set as the kernels take it: entries the kernels never read (i >= n_x, j >= n_u, rows >= n_rows) are neutral
+static ConK make_conk(const mpcd_system_desc &d, const mpcd_constraints &con)
+{
+    ConK k = {};
+    for (int i = 0; i < 12; ++i) {
+        k.box.lo[i] = i < d.n_x ? con.box.lo[i] : -INFINITY;
+        k.box.hi[i] = i < d.n_x ? con.box.hi[i] : INFINITY;
+    }
+    k.n_rows = con.n_rows;
+    for (int r = 0; r < MPCD_MAX_CON_ROWS; ++r) {
+        const bool used = r < con.n_rows;
+        for (int i = 0; i < 12; ++i) k.A[r][i] = used && i < d.n_x ? con.A[r][i] : 0.0;
+        for (int j = 0; j < 4; ++j) k.C[r][j] = used && j < d.n_u ? con.C[r][j] : 0.0;
+        k.b[r] = used ? con.b[r] : INFINITY;
+    }
+    for (int j = 0; j < 4; ++j) k.du[j] = j < d.n_u ? con.du_max[j] : INFINITY;
+    return k;
+}
+
+// What the box tail and the constraint-set tail check of their common argument block
+static bool viol_tail_ok(const mpcd_system_desc &d, double tol, const BatchBoxTail &t)
+{
+    const int64_t wgs = t.n_states * ((t.group + RT_THREADS - 1) / RT_THREADS);
+    if (t.n_states < 1 || t.group < 1 || wgs > 0x7fffffff) return false;
+    if (t.rec_stride != batch_step_rec_stride(d.n_u) || t.plan_off < t.n_states * t.rec_stride) return false;
+    // the result block's parts in order, none overlapping the one before: plans, V, n_feasible, entries, their V
+    return !(t.k < 1 || t.k > MPCD_MAX_ELITES || t.k > t.group || t.select_first || !t.part_elite || !t.part_viol ||
+             !t.part_nfeas || !(tol >= 0.0) ||
+             t.viol_off < t.plan_off + (int64_t)sizeof(float) * t.n_states * t.H * d.n_u || t.viol_off % alignof(double) ||
+             t.nfeas_off < t.viol_off + (int64_t)sizeof(double) * t.n_states || t.nfeas_off % alignof(int64_t) ||
+             t.elite_off < t.nfeas_off + (int64_t)sizeof(int64_t) * t.n_states || t.elite_off % alignof(mpcd_best) ||
+             t.eviol_off < t.elite_off + (int64_t)sizeof(mpcd_best) * t.n_states * t.k || t.eviol_off % alignof(double));
+}
+
+hipError_t launch_batch_constr_tail(const mpcd_system_desc &d, const float *umin_host, const float *umax_host,
+                                    const mpcd_constraints &con, double tol, const double *u_prev_dev,
+                                    const BatchBoxTail &t, hipStream_t stream)
+{
+    if (!viol_tail_ok(d, tol, t) || con.n_rows < 0 || con.n_rows > MPCD_MAX_CON_ROWS) return hipErrorInvalidValue;
+    const SysK S = make_sysk(d, umin_host, umax_host);
+    const int64_t wgs = t.n_states * ((t.group + RT_THREADS - 1) / RT_THREADS);
+    const ConTolK C{make_conk(d, con), tol, u_prev_dev};
+    const size_t lds = sizeof(float) * RT_THREADS * (t.H * d.n_u + 1);
+    return dispatch_system(d, [&](auto sys) {
+        hipLaunchKernelGGL((batch_step_box_tail_kernel<decltype(sys)::value, ConTolK>), dim3((unsigned)wgs),
+                           dim3(RT_THREADS), lds, stream, S, C, t);
+    });
+}
+
+hipError_t launch_rollout_cost_constr(const mpcd_system_desc &d, const double *x0_dev, int64_t group, const float *u_norm,
+                                      const float *umin_host, const float *umax_host, const int *flags_dev, int64_t batch,
+                                      int H, const mpcd_constraints &con, const double *u_prev_dev, double *cost,
+                                      double *viol, hipStream_t stream)
+{
+    const int64_t wgs = (batch + RT_THREADS - 1) / RT_THREADS;
+    if (batch < 1 || group < 1 || wgs > 0x7fffffff || con.n_rows < 0 || con.n_rows > MPCD_MAX_CON_ROWS)
+        return hipErrorInvalidValue;
+    const SysK S = make_sysk(d, umin_host, umax_host);
+    const ConK ck = make_conk(d, con);
+    const size_t lds = sizeof(float) * RT_THREADS * (H * d.n_u + 1);
+    return dispatch_system(d, [&](auto sys) {
+        hipLaunchKernelGGL(rollout_cost_constr_kernel<decltype(sys)::value>, dim3((unsigned)wgs), dim3(RT_THREADS), lds,
+                           stream, S, ck, u_norm, flags_dev, x0_dev, u_prev_dev, group, batch, H, cost, viol);
+    });
+}
+
 hipError_t launch_batch_box_tail(const mpcd_system_desc &d, const float *umin_host, const float *umax_host,
                                  const mpcd_state_box &box, double tol, const BatchBoxTail &t, hipStream_t stream)
 {
+    if (!viol_tail_ok(d, tol, t)) return hipErrorInvalidValue;
     const SysK S = make_sysk(d, umin_host, umax_host);
     const int64_t wgs = t.n_states * ((t.group + RT_THREADS - 1) / RT_THREADS);
-    if (t.n_states < 1 || t.group < 1 || wgs > 0x7fffffff) return hipErrorInvalidValue;
-    if (t.rec_stride != batch_step_rec_stride(d.n_u) || t.plan_off < t.n_states * t.rec_stride) return hipErrorInvalidValue;
-    // the result block's parts in order, none overlapping the one before: plans, V, n_feasible, entries, their V
-    if (t.k < 1 || t.k > MPCD_MAX_ELITES || t.k > t.group || t.select_first || !t.part_elite || !t.part_viol ||
-        !t.part_nfeas || !(tol >= 0.0) ||
-        t.viol_off < t.plan_off + (int64_t)sizeof(float) * t.n_states * t.H * d.n_u || t.viol_off % alignof(double) ||
-        t.nfeas_off < t.viol_off + (int64_t)sizeof(double) * t.n_states || t.nfeas_off % alignof(int64_t) ||
-        t.elite_off < t.nfeas_off + (int64_t)sizeof(int64_t) * t.n_states || t.elite_off % alignof(mpcd_best) ||
-        t.eviol_off < t.elite_off + (int64_t)sizeof(mpcd_best) * t.n_states * t.k || t.eviol_off % alignof(double))
-        return hipErrorInvalidValue;
     BoxTolK C;
     for (int i = 0; i < 12; ++i) {  // entries >= n_x are ignored: the kernel never reads them
         C.box.lo[i] = i < d.n_x ? box.lo[i] : -INFINITY;

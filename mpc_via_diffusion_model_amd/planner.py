@@ -114,7 +114,7 @@ class MPCResult:
     flags: int = 0          # mpcd_last_step_flags bits (native step): 1 clipped, 2 NaN in the samples
     elite_index: np.ndarray = None  # [k] int64 global indices of the k best candidates, best first (elites=k)
     elite_cost: np.ndarray = None   # [k] fp64 their costs, nondecreasing (a NaN cost is reported as +inf)
-    violation: float = None  # state_box=: the selected candidate's box violation V (0.0 = inside the box)
+    violation: float = None  # state_box= / constraints=: the selected candidate's violation V (0.0 = admissible)
     n_feasible: int = None   # state_box=: how many candidates have V <= viol_tol (0: the least violating was selected)
 
 
@@ -139,10 +139,60 @@ class BatchStepResult:
     u_norm: torch.Tensor = None  # [M * n, H, d] this step's normalised samples (return_samples=True)
     elite_index: np.ndarray = None  # [M, k] int64 global indices of each state's k best, best first (elites=k)
     elite_cost: np.ndarray = None   # [M, k] fp64 their costs, nondecreasing (a NaN cost is reported as +inf)
-    violation: np.ndarray = None    # [M] mpc_step_batch_box: the selected candidate's box violation V (0.0 = inside)
-    n_feasible: np.ndarray = None   # [M] int64 mpc_step_batch_box: the state's candidates with V <= viol_tol (0: the
+    violation: np.ndarray = None    # [M] mpc_step_batch_box / _constr: the selected candidate's violation V (0.0 = admissible)
+    n_feasible: np.ndarray = None   # [M] int64 mpc_step_batch_box / _constr: the state's candidates with V <= viol_tol (0: the
                                     # least violating one was selected; the state carries MPCD_STEP_INFEASIBLE)
-    elite_violation: np.ndarray = None  # [M, k] mpc_step_batch_box with elites: V of each ranked candidate
+    elite_violation: np.ndarray = None  # [M, k] mpc_step_batch_box / _constr with elites: V of each ranked candidate
+
+
+class Constraints:
+    """A constraint set (mpcd.h "Constraint set"): a state box, up to 8 linear rows and per-input rate bounds.
+
+    state_box: (lo, hi) as everywhere (None = unbounded: the whole box, a side, or single entries).
+    rows: a sequence of (a, c, b) meaning sum_i a[i] x[i] + sum_j c[j] u[j] <= b on every visited pair (x_{k+1}, u_k):
+    a has n_x entries, c has n_u entries or is None (zeros), b is a float (+inf switches the row off).
+    du_max: n_u entries bounding |u_k[j] - u_{k-1}[j]| (None, or None entries = unbounded).
+    The set is checked against a system when a call takes it; a ValueError names the entry."""
+
+    def __init__(self, state_box=None, rows=(), du_max=None):
+        self.state_box, self.rows, self.du_max = state_box, tuple(rows), du_max
+
+    def native(self, n_x, n_u):
+        """the mpcd_constraints of a system with n_x states and n_u inputs (checked)"""
+        con = N.ConstraintSet()
+        con.box = DiffusionMPC._state_box((None, None) if self.state_box is None else self.state_box, n_x)
+        if len(self.rows) > N.MPCD_MAX_CON_ROWS:
+            raise ValueError(f"constraints: {len(self.rows)} rows, at most {N.MPCD_MAX_CON_ROWS}")
+        con.n_rows = len(self.rows)
+        for r in range(N.MPCD_MAX_CON_ROWS):
+            con.b[r] = np.inf
+        for r, row in enumerate(self.rows):
+            try:
+                a, c, b = row
+                a = [float(v) for v in a]
+                c = [0.0] * n_u if c is None else [float(v) for v in c]
+                b = float(b)
+            except (TypeError, ValueError):
+                raise ValueError(f"constraints row {r}: must be (a [n_x], c [n_u] or None, b)") from None
+            if len(a) != n_x or len(c) != n_u:
+                raise ValueError(f"constraints row {r}: a has {len(a)} entries (n_x = {n_x}), c has {len(c)} (n_u = {n_u})")
+            for what, vals, dst in (("a", a, con.A[r]), ("c", c, con.C[r])):
+                for i, v in enumerate(vals):
+                    if not np.isfinite(v):
+                        raise ValueError(f"constraints row {r}: {what}[{i}] = {v} is not finite")
+                    dst[i] = v
+            if np.isnan(b) or b == -np.inf:
+                raise ValueError(f"constraints row {r}: b = {b} (use +inf to switch a row off)")
+            con.b[r] = b
+        du = [None] * n_u if self.du_max is None else list(self.du_max)
+        if len(du) != n_u:
+            raise ValueError(f"constraints du_max must have n_u = {n_u} entries, got {len(du)}")
+        for j in range(4):
+            v = np.inf if j >= n_u or du[j] is None else float(du[j])
+            if not v >= 0.0:
+                raise ValueError(f"constraints du_max[{j}] = {v} must be >= 0 (None = unbounded)")
+            con.du_max[j] = v
+        return con
 
 
 _STATE_RESULT = np.dtype([("cost", "<f8"), ("index", "<i8"), ("flags", "<i4"), ("reserved", "<i4")])
@@ -686,6 +736,68 @@ class DiffusionMPC:
         self._rollout_cost_box_raw(system.desc(), x, group, u_norm, clip_flags, box, cost, viol)
         return cost, viol
 
+    @staticmethod
+    def _constraints(constraints, system):
+        if not isinstance(constraints, Constraints):
+            raise ValueError("constraints must be a Constraints(state_box=, rows=, du_max=)")
+        return constraints.native(system.n_x, system.n_u)
+
+    def _u_prev(self, u_prev, M, n_u):
+        """u_prev [M, n_u] (or [n_u] for one state; a NaN row: none) as a device float64 tensor, or None"""
+        if u_prev is None:
+            return None
+        if torch.is_tensor(u_prev):
+            up = u_prev.to(self.device, torch.float64)
+        else:
+            up = torch.from_numpy(np.ascontiguousarray(u_prev, dtype=np.float64)).to(self.device)
+        up = (up[None] if up.dim() == 1 else up).contiguous()
+        if tuple(up.shape) != (M, n_u):
+            raise ValueError(f"u_prev must be [{M}, {n_u}], got {tuple(up.shape)}")
+        return up
+
+    def _rollout_cost_constr_raw(self, desc, x_dev, group, u_norm, flags, con, u_prev, cost, viol):
+        B, H, _ = u_norm.shape
+        N.check(self._lib.mpcd_rollout_cost_constr(
+            self._ctx, ctypes.byref(desc), ctypes.c_void_p(x_dev.data_ptr()), group, ctypes.c_void_p(u_norm.data_ptr()),
+            self.act_min.ctypes.data, self.act_max.ctypes.data, B, H, ctypes.c_void_p(flags.data_ptr()), ctypes.byref(con),
+            None if u_prev is None else ctypes.c_void_p(u_prev.data_ptr()), ctypes.c_void_p(cost.data_ptr()),
+            ctypes.c_void_p(viol.data_ptr()), self._stream()), "mpcd_rollout_cost_constr")
+
+    def rollout_cost_constr(self, system: System, x0_states, u_norm, constraints, group=None, clip_flags=None, u_prev=None):
+        """rollout_cost_box with a constraint set (mpcd_rollout_cost_constr): (cost [B], violation [B]) device float64
+        tensors. constraints: a Constraints; violation[b] = max(0, every excess of the box, the rows and the rate bounds
+        over the pairs (x_{k+1}, u_k) the candidate's cost evaluation visits), +inf where an excess is NaN. u_prev
+        [M, n_u] (host values or a device float64 tensor; [n_u] for one state): each state's previous applied action,
+        the predecessor of u_0 in the rate test; None, or a row with a NaN: that state's rate test starts at u_1.
+        x0_states, group, clip_flags: rollout_cost_box's. cost is bit for bit the unconstrained rollout's."""
+        B, H, d = u_norm.shape
+        if d != system.n_u:
+            raise ValueError(f"system {system.name} has {system.n_u} inputs, samples have {d}")
+        if torch.is_tensor(x0_states):
+            x = x0_states.to(self.device, torch.float64)
+        else:
+            x = torch.from_numpy(np.ascontiguousarray(x0_states, dtype=np.float64)).to(self.device)
+        x = (x[None] if x.dim() == 1 else x).contiguous()
+        M = x.shape[0]
+        if x.dim() != 2 or x.shape[1] != system.n_x:
+            raise ValueError(f"x0_states must be [M, {system.n_x}], got {tuple(x.shape)}")
+        group = B // M if group is None else int(group)
+        if group < 1 or M * group != B:
+            raise ValueError(f"u_norm has {B} candidates: not {M} states x group={group}")
+        con = self._constraints(constraints, system)
+        up = self._u_prev(u_prev, M, d)
+        u_norm = u_norm.contiguous()
+        if clip_flags is None:
+            clip_flags = torch.empty(M, dtype=torch.int32, device=self.device)
+            N.check(self._lib.mpcd_clip_flags(self._ctx, ctypes.c_void_p(u_norm.data_ptr()), M, group * H * d,
+                                              ctypes.c_void_p(clip_flags.data_ptr()), self._stream()), "mpcd_clip_flags")
+        elif clip_flags.dtype != torch.int32 or clip_flags.device != self.device or clip_flags.numel() != M:
+            raise ValueError(f"clip_flags must be {M} int32 codes on {self.device}")
+        cost = torch.empty(B, dtype=torch.float64, device=self.device)
+        viol = torch.empty(B, dtype=torch.float64, device=self.device)
+        self._rollout_cost_constr_raw(system.desc(), x, group, u_norm, clip_flags, con, up, cost, viol)
+        return cost, viol
+
     def _topk_feasible_raw(self, cost, viol, k, n_groups, tol, index_offset=0):
         """mpcd_topk_feasible: (mpcd_best records as int64 [M, k, 2] (cost bits, index), violation [M, k], n_feasible [M])"""
         for name, t in (("cost", cost), ("violation", viol)):
@@ -757,7 +869,7 @@ class DiffusionMPC:
     def closed_loop(self, x0_states, system: System, iterations, n_samples=1, w=0.01, sample_fn="ddpm_cfg",
                     n_wo_noise=0, ddim_steps=None, clamp_x0=False, select="argmin", decimals=4, seed=0, noise=None,
                     clip_rule="chain", grouped=False, warm_start=None, native=False, elites=None, state_box=None,
-                    viol_tol=0.0):
+                    viol_tol=0.0, constraints=None, u_prev=None):
         """Closed-loop diffusion MPC for M plant states at once, resident on the device.
         The reference runs one initial state at a time on the host (Cart_Diffusion_inference.py:405-512:
         normalize_condition -> run_CFG -> unnormalize -> u0 = round(u[0], 4) -> x = f(x, u0), repeated
@@ -800,9 +912,25 @@ class DiffusionMPC:
         the next priors from the same ranked list (shift_plans on entry 0's index, or elite_priors: the elites are
         feasibility-first too). The result carries violation / n_feasible [M, T]: where n_feasible is 0 no candidate
         stayed in the box and the least violating one was applied. The fused tail of native=True takes no box: it
-        raises ValueError, as does select="first"."""
+        raises ValueError, as does select="first".
+        constraints=Constraints(...) (instead of state_box, which goes into the set): the same loop with
+        mpcd_rollout_cost_constr as the producer of V - the box, linear rows over (x_{k+1}, u_k) and input-rate bounds.
+        u_prev [M, n_u] or None is each state's previous applied action for iteration 0 (a NaN row: none); every later
+        iteration's is the previous iteration's applied (rounded) action, read on the device. Same refusals."""
         K = None if warm_start is None else int(warm_start)
-        box = None
+        box = con = None
+        if constraints is not None:
+            if state_box is not None:
+                raise ValueError("state_box together with constraints: put the box into the set, "
+                                 "Constraints(state_box=...)")
+            if native:
+                raise ValueError("constraints are not available with native=True: mpcd_closed_loop's fused tail takes no "
+                                 "constraint set; use native=False")
+            if select != "argmin":
+                raise ValueError("constraints rank candidates feasibility-first: they need select='argmin'")
+            con, tol = self._constraints(constraints, system), self._viol_tol(viol_tol)
+        elif u_prev is not None:
+            raise ValueError("u_prev serves the rate bounds of constraints=")
         if state_box is not None:
             if native:
                 raise ValueError("state_box is not available with native=True: folding the constraint into "
@@ -853,10 +981,12 @@ class DiffusionMPC:
         priors = None
         if K is not None:  # one prior per state, or (elites) one per candidate
             priors = torch.empty((M if elites is None else B, H, d), dtype=torch.float32, device=dev)
-        if box is not None:
+        if box is not None or con is not None:
             viol = torch.empty(B, dtype=torch.float64, device=dev)
             vs = torch.empty((T, M), dtype=torch.float64, device=dev)
             nfs = torch.empty((T, M), dtype=torch.int64, device=dev)
+        if con is not None:
+            up = self._u_prev(u_prev, M, d)
         xs[0] = x
         for it in range(T):
             warm = {}
@@ -874,8 +1004,11 @@ class DiffusionMPC:
                 N.check(self._lib.mpcd_clip_flags(self._ctx, ptr(absmax), M, n, ptr(flags), st), "mpcd_clip_flags")
             else:
                 N.check(self._lib.mpcd_clip_flags(self._ctx, ptr(u_norm), M, n * H * d, ptr(flags), st), "mpcd_clip_flags")
-            if box is not None:  # feasibility-first: one ranked list serves the selection and the next priors
-                self._rollout_cost_box_raw(desc, x, n, u_norm, flags, box, cost, viol)
+            if box is not None or con is not None:  # feasibility-first: one ranked list serves the selection and the next priors
+                if con is not None:  # the predecessor of u_0: the action the plant received last
+                    self._rollout_cost_constr_raw(desc, x, n, u_norm, flags, con, up if it == 0 else us[it - 1], cost, viol)
+                else:
+                    self._rollout_cost_box_raw(desc, x, n, u_norm, flags, box, cost, viol)
                 raw, vk, nf = self._topk_feasible_raw(cost, viol, elites or 1, M, tol)
                 self._control_step_picked_raw(desc, x, u_norm, raw, 0, flags, decimals, us[it], ix[it], cs[it])
                 if elites is not None:
@@ -899,7 +1032,7 @@ class DiffusionMPC:
             xs[it + 1] = x
         res = ClosedLoopResult(x=xs.transpose(0, 1).cpu().numpy(), u=us.transpose(0, 1).cpu().numpy(),
                                cost=cs.t().cpu().numpy(), index=ix.t().cpu().numpy())
-        if box is not None:
+        if box is not None or con is not None:
             res.violation, res.n_feasible = vs.t().cpu().numpy(), nfs.t().cpu().numpy()
         return res
 
@@ -1020,10 +1153,31 @@ class DiffusionMPC:
         box, tol = self._state_box(state_box, system.n_x), self._viol_tol(viol_tol)
         return self._mpc_step_batch(x_states, system, n_samples, box=(box, tol), **kw)
 
+    def mpc_step_batch_constr(self, x_states, system: System, n_samples, constraints, viol_tol=0.0, u_prev=None, **kw):
+        """mpc_step_batch_box with a constraint set in place of the box: still ONE library call
+        (mpcd_mpc_step_batch_constr; the fused launch is batch_step_box_tail_kernel<SYS, ConTolK>). constraints: a Constraints (box,
+        linear rows over (x_{k+1}, u_k), input-rate bounds); V and everything ranked by it are bit for bit
+        rollout_cost_constr + topk_feasible on the step's samples. u_prev [M, n_u] or None: each state's previous
+        applied action (the predecessor of u_0 in the rate test; a NaN row: none), uploaded with the states in the one
+        copy. A state named by `reset` whose row the caller left out (u_prev=None) has none. **kw, the kept prior set,
+        the `reset` split and the result fields: mpc_step_batch_box's."""
+        if kw.get("select", "argmin") != "argmin":
+            raise ValueError("constraints rank candidates feasibility-first: they need select='argmin'")
+        con, tol = self._constraints(constraints, system), self._viol_tol(viol_tol)
+        x = np.asarray(x_states, dtype=np.float64)
+        M = 1 if x.ndim == 1 else x.shape[0]
+        up = None
+        if u_prev is not None:
+            up = np.ascontiguousarray(np.atleast_2d(np.asarray(u_prev, dtype=np.float64)))
+            if up.shape != (M, system.n_u):
+                raise ValueError(f"u_prev must be [{M}, {system.n_u}], got {up.shape}")
+        return self._mpc_step_batch(x_states, system, n_samples, box=(con, tol, up), **kw)
+
     def _mpc_step_batch(self, x_states, system, n_samples, w=0.01, sample_fn="ddpm_cfg", n_wo_noise=0, ddim_steps=None,
                         clamp_x0=False, seed=0, noise=None, select="argmin", decimals=4, clip_rule="chain", grouped=False,
                         warm_start=None, reset=None, return_samples=False, allow_nonfinite=False, elites=None, box=None):
-        """mpc_step_batch and mpc_step_batch_box (box = (mpcd_state_box, tol), checked): one body, one kept prior set"""
+        """mpc_step_batch, mpc_step_batch_box (box = (mpcd_state_box, tol), checked) and mpc_step_batch_constr (box =
+        (mpcd_constraints, tol, u_prev [M, n_u] or None), checked): one body, one kept prior set"""
         K = None if warm_start is None else int(warm_start)
         if elites is not None:
             if K is None:
@@ -1090,8 +1244,11 @@ class DiffusionMPC:
             tc, tw = torch.from_numpy(ic).to(self.device), torch.from_numpy(iw).to(self.device)
             pc = torch.empty((len(ic),) + pshape, dtype=torch.float32, device=self.device)
             pw = priors.index_select(0, tw)
-            rc_, bad_c = self._batch_step_call(x[ic], 0, pc, noise[0], **kw)
-            rw_, bad_w = self._batch_step_call(x[iw], K, pw, noise[1], **kw)
+            kc = kwm = kw
+            if box is not None and len(box) == 3 and box[2] is not None:  # each sub-call takes its states' u_prev rows
+                kc, kwm = dict(kw, box=(box[0], box[1], box[2][ic])), dict(kw, box=(box[0], box[1], box[2][iw]))
+            rc_, bad_c = self._batch_step_call(x[ic], 0, pc, noise[0], **kc)
+            rw_, bad_w = self._batch_step_call(x[iw], K, pw, noise[1], **kwm)
             priors.index_copy_(0, tc, pc)
             priors.index_copy_(0, tw, pw)
             bad = bad_c or bad_w
@@ -1145,7 +1302,7 @@ class DiffusionMPC:
         """One mpcd_mpc_step_batch call on the states x [M, n_x] (checked by mpc_step_batch): (BatchStepResult, whether
         the call returned MPCD_ENONFINITE). priors: device [M, H, d] read when t_start > 0 and refreshed, or None.
         elites=k: mpcd_mpc_step_batch_elite, priors [M, n, H, d]. box = (mpcd_state_box, tol): mpcd_mpc_step_batch_box,
-        with or without elites."""
+        with or without elites; box = (mpcd_constraints, tol, u_prev [M, n_u] or None): mpcd_mpc_step_batch_constr."""
         x = np.ascontiguousarray(x)
         M = x.shape[0]
         H, d, B, dev = self.spec.horizon, self.spec.state_dim, M * n, self.device
@@ -1186,15 +1343,22 @@ class DiffusionMPC:
             best = np.empty((M, elites), dtype=_BEST)
             e.elites_host = best.ctypes.data
         if box is not None:
-            bx = N.BatchBoxArgs()
-            bx.box, bx.tol = ctypes.pointer(box[0]), box[1]
+            if len(box) == 3:
+                bx = N.BatchConstrArgs()
+                bx.con, bx.tol = ctypes.pointer(box[0]), box[1]
+                up = None if box[2] is None else np.ascontiguousarray(box[2], dtype=np.float64)
+                bx.u_prev_host = None if up is None else up.ctypes.data
+                call = self._lib.mpcd_mpc_step_batch_constr
+            else:
+                bx = N.BatchBoxArgs()
+                bx.box, bx.tol = ctypes.pointer(box[0]), box[1]
+                call = self._lib.mpcd_mpc_step_batch_box
             viol, nfeas = np.empty(M, dtype=np.float64), np.empty(M, dtype=np.int64)
             bx.viol_host, bx.n_feasible_host = viol.ctypes.data, nfeas.ctypes.data
             if elites is not None:
                 eviol = np.empty((M, elites), dtype=np.float64)
                 bx.elite_viol_host = eviol.ctypes.data
-            rc = self._lib.mpcd_mpc_step_batch_box(self._ctx, ctypes.byref(a), None if e is None else ctypes.byref(e),
-                                                   ctypes.byref(bx), self._stream())
+            rc = call(self._ctx, ctypes.byref(a), None if e is None else ctypes.byref(e), ctypes.byref(bx), self._stream())
         elif e is None:
             rc = self._lib.mpcd_mpc_step_batch(self._ctx, ctypes.byref(a), self._stream())
         else:
@@ -1213,7 +1377,7 @@ class DiffusionMPC:
 
     def mpc_step(self, x0, system: System, n_samples, w=0.01, sample_fn="ddpm_cfg", n_wo_noise=0, ddim_steps=None,
                  clamp_x0=False, seed=0, noise=None, group=None, comm=None, native=None, clip_rule="chain",
-                 warm_start=None, prior=None, elites=None, state_box=None, viol_tol=0.0):
+                 warm_start=None, prior=None, elites=None, state_box=None, viol_tol=0.0, constraints=None, u_prev=None):
         """One control step: sample n_samples candidates on this rank (weak scaling: every rank adds
         n_samples), roll out + cost them, all-gather costs, pick the global argmin, broadcast it.
         comm: a distributed.NativeComm (the exchange inside libmpcd.so over RCCL) or None
@@ -1246,14 +1410,32 @@ class DiffusionMPC:
         and box violation, and the winner is entry 0 of mpcd_topk_feasible - the cheapest candidate whose predicted
         states stay in the box, or, when none does, the least violating one. The result carries violation and
         n_feasible. ValueError with native=True, warm_start / prior / elites, a comm or several ranks: the fused step
-        and the multi-rank selection with a box are the follow-up."""
+        and the multi-rank selection with a box are the follow-up.
+        constraints=Constraints(...), u_prev [n_u] or None: the same composed step with mpcd_rollout_cost_constr as the
+        producer of V (the box goes into the set: state_box= together with constraints= raises ValueError); u_prev is the
+        previous applied action, the predecessor of u_0 in the rate test. Same result fields, same refusals."""
         if clip_rule not in _CLIP_RULES:
             raise ValueError(f"clip_rule must be one of {sorted(_CLIP_RULES)}")
         if comm is not None:
             rank, size = comm.rank, comm.size
         else:
             rank, size = D.world(group)
-        box = None
+        box = con = None
+        if constraints is not None:
+            if state_box is not None:
+                raise ValueError("state_box together with constraints: put the box into the set, "
+                                 "Constraints(state_box=...)")
+            if native:
+                raise ValueError("constraints are not available with native=True: the fused step (mpcd_mpc_step) takes "
+                                 "no constraint set; leave native unset or False")
+            if warm_start is not None or prior is not None or elites is not None:
+                raise ValueError("constraints with warm_start / prior / elites need the native step, which takes no "
+                                 "constraint set; closed_loop(native=False) combines them")
+            if comm is not None or size > 1:
+                raise ValueError("constraints are single-rank: there is no multi-rank feasibility-first selection")
+            con, tol, native = self._constraints(constraints, system), self._viol_tol(viol_tol), False
+        elif u_prev is not None:
+            raise ValueError("u_prev serves the rate bounds of constraints=")
         if state_box is not None:
             if native:
                 raise ValueError("state_box is not available with native=True: folding the constraint into the fused step "
@@ -1295,8 +1477,11 @@ class DiffusionMPC:
             flag = self.clip_flag(absmax if absmax is not None else u_norm)
             if size > 1:
                 flag = comm.any_flag(flag) if comm else D.any_flag(flag, group)
-        if box is not None:
-            cost_local, viol = self.rollout_cost_box(system, x0, u_norm, state_box, clip_flags=flag)
+        if box is not None or con is not None:
+            if con is not None:
+                cost_local, viol = self.rollout_cost_constr(system, x0, u_norm, constraints, clip_flags=flag, u_prev=u_prev)
+            else:
+                cost_local, viol = self.rollout_cost_box(system, x0, u_norm, state_box, clip_flags=flag)
             raw, vk, nf = self._topk_feasible_raw(cost_local, viol, 1, 1, tol)
             idx, best = int(raw[0, 0, 1]), float(raw[0, 0, 0:1].view(torch.float64))
             u_host = self.unnormalize_states(u_norm[idx][None], flag)[0].cpu().numpy()

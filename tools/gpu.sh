@@ -18,6 +18,8 @@
 #   boxab               tools/batch_box_ab.py: the batched external step with and without a state box, against a
 #                       build of the parent commit ($PARENT_LIB, default libmpcd_parent.so beside the product library);
 #                       the table goes to standard output, extra arguments come from $AB_ARGS
+#   constrab            tools/constraints_ab.py: the constraint set beside the box (rollout and batched step) and the
+#                       unchanged paths against the same parent build; table to standard output, $AB_ARGS as above
 #
 # Extra bench.py arguments for bench / trace / pmc come from $BENCH_ARGS; extra pytest arguments from
 # $PYTEST_ARGS; extra unet_perf.py arguments from $UNET_ARGS.
@@ -90,6 +92,9 @@ run_job() {
       done ;;
     boxab)
       timeout -k 10 900 python -u tools/batch_box_ab.py \
+        --parent-lib "${PARENT_LIB:-mpc_via_diffusion_model_amd/libmpcd_parent.so}" $AB_ARGS ;;
+    constrab)
+      timeout -k 10 900 python -u tools/constraints_ab.py \
         --parent-lib "${PARENT_LIB:-mpc_via_diffusion_model_amd/libmpcd_parent.so}" $AB_ARGS ;;
     unet)
       local c=${arg:-cfg5}
