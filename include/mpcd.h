@@ -333,7 +333,9 @@ int mpcd_control_step(mpcd_ctx *ctx, const mpcd_system_desc *sys, double *x_dev,
  * by cost alone; these three entry points let a caller keep the plant inside a box of admissible states. They compose
  * with the calls above (mpcd_elite_priors and mpcd_shift_plans consume the ranked list unchanged). Of the one-call
  * tails the batched external step takes a box (mpcd_mpc_step_batch_box below: the same violation and the same order,
- * computed inside its one tail launch); mpcd_mpc_step* and mpcd_closed_loop do not.
+ * computed inside its one tail launch) and the single-state step takes one as a constraint set that is only a box
+ * (mpcd_mpc_step_constr below, on one rank or many); mpcd_mpc_step / _warm / _elite themselves and mpcd_closed_loop do
+ * not.
  *
  * State box: component i < n_x of a state is admissible in [lo[i], hi[i]]; -inf / +inf mean unbounded; entries >= n_x
  * are ignored.
@@ -387,7 +389,9 @@ int mpcd_control_step_picked(mpcd_ctx *ctx, const mpcd_system_desc *sys, double 
 /* ---- Constraint set: linear rows and input-rate bounds beside the state box. The violation V above is the box's; a
  * constraint set generalises its producer and nothing else: the feasibility-first order, tol, n_feasible and every
  * consumer of V (mpcd_topk_feasible, mpcd_control_step_picked, mpcd_shift_plans / mpcd_elite_priors on the ranked list,
- * MPCD_STEP_INFEASIBLE) are unchanged.
+ * MPCD_STEP_INFEASIBLE) are unchanged. Of the one-call steps mpcd_mpc_step_batch_constr (many external states) and
+ * mpcd_mpc_step_constr (one state: cold, warm-started, with elites, or over a communicator's ranks) take a set;
+ * mpcd_closed_loop does not.
  *
  * The tests run where the box is tested: each time the dynamics step produces a state inside the candidate's cost
  * evaluation, on the pair (x_{k+1}, u_k) of the new state and the input that produced it: MPCD_COST_CANONICAL k = 0 ..
@@ -765,6 +769,56 @@ int mpcd_mpc_step_elite(mpcd_ctx *ctx, const mpcd_step_args *args, const mpcd_wa
  * split-bf16 programs - the other bits and the outputs are the re-run's. */
 enum { MPCD_STEP_CLIPPED = 1, MPCD_STEP_NAN_SAMPLES = 2, MPCD_STEP_NONFINITE_WINNER = 4, MPCD_STEP_F32X3_RERUN = 8 };
 int mpcd_last_step_flags(mpcd_ctx *ctx, int32_t *flags);
+
+/* mpcd_mpc_step / _warm / _elite with a constraint set ("Constraint set" above) and the feasibility-first order, on
+ * one rank or over a communicator. warm NULL: a cold step; else mpcd_mpc_step_warm's (k == 0) or mpcd_mpc_step_elite's
+ * (k >= 1) warm start. All results below are for the same samples, x0, global clip flag, set and u_prev:
+ *  - cost_local / viol_local are bit for bit what mpcd_rollout_cost_constr writes with group = batch, the one start
+ *    state x0 and the step's global clip flag.
+ *  - *best_host, *viol_host and *n_feasible_host are bit for bit entry 0, its V and the count of
+ *    mpcd_topk_feasible(k = 1, tol, index_offset = 0) over the gathered arrays of all ranks, in rank order: indices are
+ *    global, a NaN cost is reported as +inf. (One rank: index_offset = sample.global_offset, as in mpcd_mpc_step.)
+ *  - u_best_host is the winner's row unnormalised with the global clip flag, as mpcd_mpc_step does.
+ *  - k == 0: next_priors_out (dev [H][d] or NULL) is mpcd_shift_plans on the winner; with a communicator it is taken
+ *    from the all-reduced winner row, identical on every rank, as in mpcd_mpc_step_warm.
+ *  - k >= 1 (single rank): elites_host / elite_viol_host are entries 0..k of mpcd_topk_feasible(k, tol) over
+ *    cost_local / viol_local, elites_host[0] equals *best_host, and next_priors_out (dev [batch][H][d] or NULL) is
+ *    mpcd_elite_priors(shift = 1) on that list.
+ *  - A set that is only a box gives the box's V. An all-infinite set with tol = 0 and no u_prev gives bit for bit the
+ *    results of mpcd_mpc_step / _warm / _elite (V = 0 then, except that a candidate with a NaN state has V = +inf and
+ *    ranks after every candidate without one: mpcd_mpc_step_batch_box's caveat).
+ * Flags (mpcd_last_step_flags): the bits above keep their meaning; MPCD_STEP_INFEASIBLE (16) is set exactly when
+ * *n_feasible_host == 0 - a flag, not an error: the return code stays MPCD_OK. MPCD_ENONFINITE is returned, with all
+ * outputs written, when the selected cost is not finite. The MPCD_F16X2 re-run rule is mpcd_mpc_step's (single rank);
+ * next_priors_out may not alias warm->x_init or sample.x_out. A refused call leaves the flags as they were.
+ * One rank: the sampler, then ONE launch (rollout_constr_select_kernel, csrc/rollout.hip: rollout, cost, V, the
+ * selection, the winner's row); with elites the mpcd_topk_feasible and mpcd_elite_priors launches follow. The result
+ * returns through mapped host memory and a completion word, V and n_feasible included. With a communicator: the
+ * clip-flag launch and its max-reduce, the producer launch, all-gathers of the costs and of the violations,
+ * mpcd_topk_feasible over the gathered arrays (one group, k = 1), the owner-row sum all-reduce, one device-to-host copy
+ * and one stream synchronisation.
+ * MPCD_EINVAL: mpcd_mpc_step_warm's / _elite's cases; con or con->con NULL; mpcd_rollout_cost_constr's cases for the
+ * set; tol negative or NaN; viol_local, viol_host or n_feasible_host NULL; viols_all NULL with a communicator;
+ * reserved != 0; k < 0, k > sample.batch or k > MPCD_MAX_ELITES; warm->t_start > 0 with warm->rows not 1 (k == 0), or
+ * neither 1 nor batch (k >= 1); elites_host or elite_viol_host given with k == 0. MPCD_EUNSUP: k >= 1 with a
+ * communicator (multi-rank elites stay out); t_start > 0 with a DDIM sampler. */
+typedef struct {
+    const mpcd_constraints *con;  /* host; mpcd_rollout_cost_constr's rules and refusals */
+    double tol;                   /* mpcd_topk_feasible's tol */
+    const double *u_prev_host;    /* host [n_u] or NULL: the action applied last; a NaN entry: none */
+    double *viol_local;           /* dev [batch] out: V of this rank's candidates (required) */
+    double *viols_all;            /* dev [nranks * batch] out; required with a communicator, else unused */
+    int32_t k;                    /* 0: winner only; 1 .. min(batch, MPCD_MAX_ELITES): elites (single rank) */
+    int32_t reserved;             /* 0 */
+    float *next_priors_out;       /* dev or NULL. k == 0: [H][d], mpcd_mpc_step_warm's next_init_out;
+                                     k >= 1: [batch][H][d], mpcd_mpc_step_elite's next_priors_out */
+    mpcd_best *elites_host;       /* host [k] or NULL */
+    double *elite_viol_host;      /* host [k] or NULL (k >= 1) */
+    double *viol_host;            /* host [1]: the selected candidate's V (required) */
+    int64_t *n_feasible_host;     /* host [1]: candidates of ALL ranks with V <= tol (required) */
+} mpcd_step_constr_args;
+int mpcd_mpc_step_constr(mpcd_ctx *ctx, const mpcd_step_args *args, const mpcd_warm_start *warm /* NULL: cold */,
+                         const mpcd_step_constr_args *con, mpcd_best *best_host, float *u_best_host, void *hip_stream);
 
 /* U-Net conv tilings (MPCD_F32X3 / MPCD_F16). Each conv launch picks rows-per-workgroup x register tile
  * x persistent-or-not among candidates by timing them once per layer shape and batch, and each

@@ -118,6 +118,14 @@ class BatchConstrArgs(ctypes.Structure):
                 ("elite_viol_host", ctypes.c_void_p), ("reserved", ctypes.c_int32), ("reserved2", ctypes.c_int32)]
 
 
+class StepConstrArgs(ctypes.Structure):  # mpcd_step_constr_args
+    _fields_ = [("con", ctypes.POINTER(ConstraintSet)), ("tol", ctypes.c_double), ("u_prev_host", ctypes.c_void_p),
+                ("viol_local", ctypes.c_void_p), ("viols_all", ctypes.c_void_p), ("k", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("next_priors_out", ctypes.c_void_p), ("elites_host", ctypes.c_void_p),
+                ("elite_viol_host", ctypes.c_void_p), ("viol_host", ctypes.POINTER(ctypes.c_double)),
+                ("n_feasible_host", ctypes.POINTER(ctypes.c_int64))]
+
+
 class TrainCfg(ctypes.Structure):
     _fields_ = [("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
                 ("ema_decay", ctypes.c_float), ("step_start_ema", ctypes.c_int32), ("update_ema_every", ctypes.c_int32)]
@@ -152,6 +160,9 @@ EXPORTS = {
     "mpcd_mpc_step_elite": ([ctypes.c_void_p, ctypes.POINTER(StepArgs), ctypes.POINTER(WarmStart), ctypes.c_int32,
                              ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Best), ctypes.c_void_p, ctypes.c_void_p],
                             ctypes.c_int),
+    "mpcd_mpc_step_constr": ([ctypes.c_void_p, ctypes.POINTER(StepArgs), ctypes.POINTER(WarmStart),
+                              ctypes.POINTER(StepConstrArgs), ctypes.POINTER(Best), ctypes.c_void_p, ctypes.c_void_p],
+                             ctypes.c_int),
     "mpcd_eps": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "mpcd_clip_flag": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p],

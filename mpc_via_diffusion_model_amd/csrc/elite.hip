@@ -147,9 +147,15 @@ __device__ __forceinline__ void tf_wave_argmin(double &V, double &v, int64_t &i,
 // (each cost and each violation is read from memory once), the k best so far riding along as one more item of threads
 // 0..k-1. out[m][r] = {cost, offset + position}, viol_out[m][r] = that entry's V (NaN reported as +inf; not g), and
 // n_feasible[m] = how many items of the whole group have V <= tol (0: entry 0 is the least violating one).
+// MIRROR (mpcd_mpc_step_constr with elites, one group): the k entries and their V also go to mapped host memory, then
+// *host_flag = host_seq after a system-scope fence (topk_kernel's protocol). A compile-time parameter: <false> is the
+// kernel as it was, its trailing arguments never read.
+template <bool MIRROR>
 __global__ __launch_bounds__(TK_THREADS) void topk_feasible_kernel(const double *cost, const double *viol, int64_t group,
                                                                    int k, double tol, int64_t offset, mpcd_best *out,
-                                                                   double *viol_out, int64_t *n_feasible)
+                                                                   double *viol_out, int64_t *n_feasible,
+                                                                   mpcd_best *mirror, double *mirror_viol,
+                                                                   uint32_t *host_flag, uint32_t host_seq)
 {
     __shared__ double pV_s[2][TK_WAVES], pv_s[2][TK_WAVES];
     __shared__ int64_t pi_s[2][TK_WAVES];
@@ -233,6 +239,12 @@ __global__ __launch_bounds__(TK_THREADS) void topk_feasible_kernel(const double 
         out[m * k + t] = mpcd_best{carry_v, carry_i < 0 ? -1 : offset + carry_i};
         if (viol_out) viol_out[m * k + t] = carry_V;
     }
+    if constexpr (MIRROR) {
+        if (t < k) {
+            mirror[t] = mpcd_best{carry_v, carry_i < 0 ? -1 : offset + carry_i};
+            mirror_viol[t] = carry_V;
+        }
+    }
     if (n_feasible) {  // uniform: a kernel argument
 #pragma unroll
         for (int s = 32; s >= 1; s >>= 1) feasible += __shfl_xor(feasible, s);
@@ -244,6 +256,11 @@ __global__ __launch_bounds__(TK_THREADS) void topk_feasible_kernel(const double 
             for (int w = 0; w < TK_WAVES; ++w) n += cnt_s[w];
             n_feasible[m] = n;
         }
+    }
+    if constexpr (MIRROR) {  // every lane's host stores ordered before the completion word
+        __threadfence_system();
+        __syncthreads();
+        if (t == 0) __hip_atomic_store(host_flag, host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
@@ -286,12 +303,20 @@ hipError_t launch_topk(const double *cost, int64_t n_groups, int64_t group, int 
 }
 
 hipError_t launch_topk_feasible(const double *cost, const double *viol, int64_t n_groups, int64_t group, int k, double tol,
-                                int64_t offset, mpcd_best *out, double *viol_out, int64_t *n_feasible, hipStream_t stream)
+                                int64_t offset, mpcd_best *out, double *viol_out, int64_t *n_feasible, hipStream_t stream,
+                                const TopkFeasMirror *mirror)
 {
-    if (n_groups < 1 || n_groups > 0x7fffffff || group < 1 || k < 1 || k > MPCD_MAX_ELITES || k > group || !(tol >= 0.0))
+    if (n_groups < 1 || n_groups > 0x7fffffff || group < 1 || k < 1 || k > MPCD_MAX_ELITES || k > group || !(tol >= 0.0) ||
+        (mirror && (n_groups != 1 || !mirror->host_out || !mirror->host_viol || !mirror->host_flag)))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(topk_feasible_kernel, dim3((unsigned)n_groups), dim3(TK_THREADS), 0, stream, cost, viol, group, k,
-                       tol, offset, out, viol_out, n_feasible);
+    if (mirror)
+        hipLaunchKernelGGL(topk_feasible_kernel<true>, dim3(1), dim3(TK_THREADS), 0, stream, cost, viol, group, k, tol,
+                           offset, out, viol_out, n_feasible, mirror->host_out, mirror->host_viol, mirror->host_flag,
+                           mirror->host_seq);
+    else
+        hipLaunchKernelGGL(topk_feasible_kernel<false>, dim3((unsigned)n_groups), dim3(TK_THREADS), 0, stream, cost, viol,
+                           group, k, tol, offset, out, viol_out, n_feasible, (mpcd_best *)nullptr, (double *)nullptr,
+                           (uint32_t *)nullptr, 0u);
     return hipGetLastError();
 }
 

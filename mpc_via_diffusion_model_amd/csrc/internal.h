@@ -244,6 +244,34 @@ hipError_t launch_rollout_cost_constr(const mpcd_system_desc &d, const double *x
                                       const float *umin_host, const float *umax_host, const int *flags_dev, int64_t batch,
                                       int H, const mpcd_constraints &con, const double *u_prev_dev, double *cost,
                                       double *viol, hipStream_t stream);
+// The constraint set in the one-call control step (rollout.hip rollout_constr_select_kernel, mpcd_mpc_step_constr):
+// launch_rollout_cost of the single-state step with the set, the one start state and the previous applied action
+// (u_prev_host [n_u] or null; a NaN entry: none) by value; cost / viol [batch] are launch_rollout_cost_constr's bits.
+// sel null: that is all (the multi-rank producer; flag_dev[0] is the clip code). sel: the selection in the
+// feasibility-first order in the same launch, RolloutSelect's protocol; the result block, on the device (block) and in
+// mapped host memory (host_out), is {mpcd_best, winner row [row] fp32, clip code int32, padding to 8 bytes, V double,
+// n_feasible int64}.
+constexpr size_t step_constr_viol_off(int row)
+{
+    return (sizeof(mpcd_best) + sizeof(float) * (size_t)row + sizeof(int32_t) + 7) & ~(size_t)7;
+}
+constexpr size_t step_constr_out_bytes(int row) { return step_constr_viol_off(row) + sizeof(double) + sizeof(int64_t); }
+struct RolloutConstrSelect {
+    char *block;          // the device result block, step_constr_out_bytes(row)
+    double *part;         // 4 * n_part 8-byte entries: the workgroups' partials (V, cost, index, feasible count)
+    int64_t n_part;       // >= ceil(batch / kRolloutBlock)
+    unsigned *counter;    // zero-initialised, reset by the kernel
+    int64_t offset;
+    const float *clip_src;  // optional, as in RolloutSelect
+    int64_t clip_n;
+    char *host_out;         // optional mapped mirror of the block, the same layout
+    uint32_t *host_flag;
+    uint32_t host_seq;
+};
+hipError_t launch_rollout_constr_select(const mpcd_system_desc &d, const double *x0_host, const float *u_norm,
+                                        const float *umin_host, const float *umax_host, const int *flag_dev, int64_t batch,
+                                        int H, const mpcd_constraints &con, double tol, const double *u_prev_host,
+                                        double *cost, double *viol, hipStream_t stream, const RolloutConstrSelect *sel);
 // Elite sets (elite.hip). launch_topk: out[m][0..k) = the k best of cost[m * group, (m + 1) * group), best first, in
 // rollout.hip's better() order, index = offset + position in cost[]; 1 <= k <= min(group, MPCD_MAX_ELITES).
 // mirror (n_groups == 1 only): the entries also written to mapped host memory, then *host_flag = host_seq after a
@@ -266,8 +294,17 @@ hipError_t launch_elite_priors(const float *rows, int64_t n_groups, int64_t grou
 hipError_t launch_rollout_cost_box(const mpcd_system_desc &d, const double *x0_dev, int64_t group, const float *u_norm,
                                    const float *umin_host, const float *umax_host, const int *flags_dev, int64_t batch,
                                    int H, const mpcd_state_box &box, double *cost, double *viol, hipStream_t stream);
+// mirror (n_groups == 1 only; mpcd_mpc_step_constr with elites): the k entries and their V also written to mapped host
+// memory, then *host_flag = host_seq after a system-scope fence, as TopkMirror does for launch_topk
+struct TopkFeasMirror {
+    mpcd_best *host_out;
+    double *host_viol;
+    uint32_t *host_flag;
+    uint32_t host_seq;
+};
 hipError_t launch_topk_feasible(const double *cost, const double *viol, int64_t n_groups, int64_t group, int k, double tol,
-                                int64_t offset, mpcd_best *out, double *viol_out, int64_t *n_feasible, hipStream_t stream);
+                                int64_t offset, mpcd_best *out, double *viol_out, int64_t *n_feasible, hipStream_t stream,
+                                const TopkFeasMirror *mirror = nullptr);
 hipError_t launch_control_step_picked(const mpcd_system_desc &d, double *x_dev, int64_t M, const float *u_norm,
                                       int64_t batch, int H, const mpcd_best *picks, int64_t pick_stride, int64_t offset,
                                       const float *umin_host, const float *umax_host, const int *flags_dev, int decimals,

@@ -1902,21 +1902,29 @@ static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_h
 // activation beyond 65504 turns into one: hi = inf, lo = inf - inf) or with no finite cost is re-run with the net's
 // split-bf16 (MPCD_F32X3) programs and flagged MPCD_STEP_F32X3_RERUN. Single rank only: with a communicator every
 // rank would have to agree to re-run (the flag and the ENONFINITE return report it there).
-template <int MODE>
-static int mpc_step_rerun(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream,
-                          const WarmArgs *warm = nullptr, float *next_init_out = nullptr,
-                          const EliteArgs *elite = nullptr)
+// step(): one attempt of the control step, whichever entry point it belongs to
+template <class Step>
+static int mpc_step_rerun(mpcd_ctx *c, Step step)
 {
-    int rc = mpc_step_impl<MODE>(c, a, best_host, u_best_host, stream, warm, next_init_out, elite);
+    int rc = step();
     const bool f16x2 = c && c->net_loaded && c->desc.dtype == MPCD_F16X2 && !c->force_x3;
     if (f16x2 && !c->comm && (rc == MPCD_ENONFINITE || (rc == MPCD_OK && (c->step_flags & MPCD_STEP_NAN_SAMPLES)))) {
         c->force_x3 = c->unet.force3 = true;
-        rc = mpc_step_impl<MODE>(c, a, best_host, u_best_host, stream, warm, next_init_out, elite);
+        rc = step();
         c->force_x3 = c->unet.force3 = false;
         c->step_flags |= MPCD_STEP_F32X3_RERUN;
     }
     return rc;
 }
+template <int MODE>
+static int mpc_step_rerun(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream,
+                          const WarmArgs *warm = nullptr, float *next_init_out = nullptr,
+                          const EliteArgs *elite = nullptr)
+{
+    return mpc_step_rerun(c, [&] { return mpc_step_impl<MODE>(c, a, best_host, u_best_host, stream, warm, next_init_out, elite); });
+}
+static int mpc_step_constr_impl(mpcd_ctx *c, const mpcd_step_args *a, const WarmArgs *warm, const mpcd_step_constr_args *e,
+                                mpcd_best *best_host, float *u_best_host, void *stream);
 }  // extern "C++"
 
 int mpcd_mpc_step(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream)
@@ -1964,6 +1972,41 @@ int mpcd_mpc_step_elite(mpcd_ctx *c, const mpcd_step_args *a, const mpcd_warm_st
     if (int rc = resolve_warm(c, &a->sample, 0, warm, w)) return rc;
     const EliteArgs e{k, elites_host};
     return mpc_step_rerun<STEP_ELITE>(c, a, best_host, u_best_host, stream, &w, next_priors_out, &e);
+}
+
+int mpcd_mpc_step_constr(mpcd_ctx *c, const mpcd_step_args *a, const mpcd_warm_start *warm,
+                         const mpcd_step_constr_args *e, mpcd_best *best_host, float *u_best_host, void *stream)
+{
+    const char *fn = "mpcd_mpc_step_constr";
+    if (!c || !a || !e || !e->con) return fail(MPCD_EINVAL, "%s: null argument", fn);
+    if (!e->viol_local || !e->viol_host || !e->n_feasible_host)
+        return fail(MPCD_EINVAL, "%s: viol_local / viol_host / n_feasible_host", fn);
+    if (e->reserved) return fail(MPCD_EINVAL, "%s: reserved %d != 0", fn, e->reserved);
+    if (!(e->tol >= 0.0)) return fail(MPCD_EINVAL, "%s: tol %g is negative or NaN", fn, e->tol);
+    const int64_t B = a->sample.batch;
+    const int32_t k = e->k;
+    if (k < 0 || k > B || k > MPCD_MAX_ELITES)
+        return fail(MPCD_EINVAL, "%s: k %d outside [0, min(batch %lld, %d)]", fn, k, (long long)B, MPCD_MAX_ELITES);
+    if (k == 0 && (e->elites_host || e->elite_viol_host))
+        return fail(MPCD_EINVAL, "%s: elites_host / elite_viol_host without elites (k == 0)", fn);
+    if (k >= 1 && c->comm) return fail(MPCD_EUNSUP, "%s: elites are single-rank only (the elite rows live on other ranks)", fn);
+    if (c->comm && !e->viols_all) return fail(MPCD_EINVAL, "%s: viols_all is required with a communicator", fn);
+    WarmArgs w;
+    if (warm) {
+        if (warm->t_start > 0 && warm->rows != 1 && (k == 0 || warm->rows != B))
+            return fail(MPCD_EINVAL, "%s: %lld prior rows: one prior (rows == 1)%s", fn, (long long)warm->rows,
+                        k ? " or one per candidate (rows == batch)" : " for every candidate");
+        // the re-run of an MPCD_F16X2 step reads the priors again: the next priors must not have replaced them
+        if (e->next_priors_out && warm->t_start > 0 && warm->x_init && c->net_loaded) {
+            const size_t row = (size_t)c->desc.horizon * c->desc.state_dim;
+            const float *in_end = warm->x_init + (size_t)warm->rows * row;
+            const float *out_end = e->next_priors_out + (size_t)(k ? B : 1) * row;
+            if (e->next_priors_out < in_end && warm->x_init < out_end)
+                return fail(MPCD_EINVAL, "%s: next_priors_out aliases warm->x_init", fn);
+        }
+        if (int rc = resolve_warm(c, &a->sample, 0, warm, w)) return rc;
+    }
+    return mpc_step_rerun(c, [&] { return mpc_step_constr_impl(c, a, warm ? &w : nullptr, e, best_host, u_best_host, stream); });
 }
 
 extern "C++" {
@@ -2156,6 +2199,190 @@ static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_h
         return fail(MPCD_ENONFINITE, "mpcd_mpc_step: no candidate has a finite cost (best %g, index %lld)%s",
                     best_host->cost, (long long)best_host->index,
                     code == 2 ? "; NaN in the sampled trajectories" : "");
+    }
+    return MPCD_OK;
+}
+
+// mpcd_mpc_step_constr's one attempt: mpc_step_impl's sequence with the constraint set. A function of its own, so the
+// three instantiations above compile the code they had. The mapped host block is the one mpc_step_impl allocates; this
+// call's parts lie behind everything that function uses (its result block, the elites and both completion words), so
+// neither call ever finds the other's data where it waits for a completion word: [.. mpc_step_impl's parts | result
+// block {best, row, code, V, n_feasible} | completion word | k elites | their V | the ranking launch's completion word].
+static int mpc_step_constr_impl(mpcd_ctx *c, const mpcd_step_args *a, const WarmArgs *warm, const mpcd_step_constr_args *e,
+                                mpcd_best *best_host, float *u_best_host, void *stream)
+{
+    const char *fn = "mpcd_mpc_step_constr";
+    if (!c || !a || !a->sys || !a->x0 || !a->act_min || !a->act_max || !a->cost_local || !best_host || !u_best_host)
+        return fail(MPCD_EINVAL, "null argument");
+    if (!c->net_loaded) return fail(MPCD_ESTATE, "no net loaded");
+    const mpcd_net_desc &d = c->desc;
+    const mpcd_system_desc &sys = *a->sys;
+    const int64_t B = a->sample.batch;
+    const int H = d.horizon, row = H * d.state_dim, k = e->k;
+    if (B < 1 || !a->sample.x_out) return fail(MPCD_EINVAL, "sample.batch / sample.x_out");
+    if (sys.n_u != d.state_dim) return fail(MPCD_EINVAL, "system n_u %d != net state_dim %d", sys.n_u, d.state_dim);
+    int rc = check_system(&sys, H);
+    if (rc) return rc;
+    if ((rc = check_constraints(fn, e->con, sys.n_x, sys.n_u))) return rc;
+    if (d.context_dim > 0 && (!a->ctx_min || !a->ctx_max)) return fail(MPCD_EINVAL, "ctx_min / ctx_max");
+    if (d.context_dim > 0 && d.context_dim != sys.n_x) return fail(MPCD_EINVAL, "context_dim %d != n_x %d", d.context_dim, sys.n_x);
+    if (c->comm && !a->costs_all) return fail(MPCD_EINVAL, "costs_all is required with a communicator");
+    if (a->clip_rule < MPCD_CLIP_CHAIN || a->clip_rule > MPCD_CLIP_NONE) return fail(MPCD_EINVAL, "clip_rule %d", a->clip_rule);
+    float *next_out = e->next_priors_out;
+    if (next_out) {  // the prior launches read x_out and write next_priors_out
+        const float *x_end = a->sample.x_out + (size_t)B * row, *o_end = next_out + (size_t)(k ? B : 1) * row;
+        if (next_out < x_end && a->sample.x_out < o_end) return fail(MPCD_EINVAL, "%s: next_priors_out overlaps sample.x_out", fn);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    DEVICE_GUARD(c->device);
+
+    const size_t base_out = sizeof(mpcd_best) + sizeof(float) * (size_t)row + sizeof(int32_t);  // mpc_step_impl's layout
+    const size_t base_end = 64 + ((base_out + 63) & ~(size_t)63) + 64 + sizeof(mpcd_best) * MPCD_MAX_ELITES + 64;
+    const size_t out_bytes = step_constr_out_bytes(row), viol_off = step_constr_viol_off(row);
+    const size_t blk_off = base_end, flag_off = blk_off + ((out_bytes + 63) & ~(size_t)63);
+    const size_t elite_off = flag_off + 64, eviol_off = elite_off + sizeof(mpcd_best) * MPCD_MAX_ELITES;
+    const size_t elite_flag_off = eviol_off + sizeof(double) * MPCD_MAX_ELITES, host_bytes = elite_flag_off + 64;
+    if (c->step_host_bytes < host_bytes) {
+        if (c->step_host) (void)hipHostFree(c->step_host);
+        c->step_host = nullptr;
+        c->step_host_dev = nullptr;
+        c->step_host_bytes = 0;
+        HIP_TRY(hipHostMalloc(&c->step_host, host_bytes, hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(hipHostGetDevicePointer(&c->step_host_dev, c->step_host, 0));
+        memset(c->step_host, 0, host_bytes);
+        c->step_seq = 0;
+        c->step_host_bytes = host_bytes;
+    }
+    if ((rc = c->step_ctx.ensure(64)) || (rc = c->step_out.ensure(out_bytes))) return rc;
+    const int64_t n_part = (B + kRolloutBlock - 1) / kRolloutBlock;
+    if ((rc = c->step_part.ensure(32 * (size_t)n_part + sizeof(float) * (size_t)row))) return rc;
+    if (k && (rc = c->step_elite.ensure((sizeof(mpcd_best) + sizeof(double)) * MPCD_MAX_ELITES))) return rc;
+
+    // normalize_condition (A12), fp64 then the net's .float()
+    mpcd_sample_args sa = a->sample;
+    CtxRowArg ctx_row{};
+    const bool by_value = d.context_dim > 0 && d.context_dim <= kCtxRowMax;
+    if (d.context_dim > 0) {
+        float *ch = by_value ? ctx_row.v : static_cast<float *>(c->step_host);
+        for (int i = 0; i < d.context_dim; ++i) {
+            const double den = (double)(a->ctx_max[i] - a->ctx_min[i]);
+            ch[i] = (float)(2.0 * ((a->x0[i] - (double)a->ctx_min[i]) / den) - 1.0);
+        }
+        if (!by_value)
+            HIP_TRY(hipMemcpyAsync(c->step_ctx.p, ch, sizeof(float) * d.context_dim, hipMemcpyHostToDevice, st));
+        sa.context = by_value ? nullptr : c->step_ctx.as<float>();
+        sa.context_shared = 1;
+    } else {
+        sa.context = nullptr;
+    }
+    sa.chain_absmax = nullptr;
+    if (a->clip_rule == MPCD_CLIP_CHAIN) {
+        if ((rc = c->step_amax.ensure(sizeof(float) * (size_t)B))) return rc;
+        sa.chain_absmax = c->step_amax.as<float>();
+    }
+    if (warm) {
+        if ((rc = sample_impl(c, &sa, stream, by_value ? &ctx_row : nullptr, 0, warm))) return rc;
+    } else {
+        if ((rc = sample_impl(c, &sa, stream, by_value ? &ctx_row : nullptr))) return rc;
+    }
+
+    // the global clip flag, as in mpc_step_impl
+    int *flags = c->flag.as<int>();
+    const int *flag = flags + 1;  // flag[1] is never written: a constant 0
+    const float *clip_src = a->clip_rule == MPCD_CLIP_CHAIN ? sa.chain_absmax : sa.x_out;
+    const int64_t clip_n = a->clip_rule == MPCD_CLIP_CHAIN ? B : B * row;
+    const bool fuse_clip = !c->comm && a->clip_rule != MPCD_CLIP_NONE && clip_n <= kFuseClipMax;
+    if (a->clip_rule != MPCD_CLIP_NONE && !fuse_clip) {
+        HIP_TRY(launch_clip_flag(clip_src, clip_n, flags, c->sync_ws(), st));
+        if ((rc = comm_reduce(c, flags, 1, COMM_MAX_I32, st))) return rc;
+        flag = flags;
+    }
+    char *blk_dev = c->step_out.as<char>();
+    mpcd_best *best_dev = reinterpret_cast<mpcd_best *>(blk_dev);
+    float *u_dev = reinterpret_cast<float *>(best_dev + 1);
+    int32_t *code_dev = reinterpret_cast<int32_t *>(u_dev + row);
+    double *viol_dev = reinterpret_cast<double *>(blk_dev + viol_off);
+    int64_t *nfeas_dev = reinterpret_cast<int64_t *>(viol_dev + 1);
+    double *part = c->step_part.as<double>();
+    float *row_norm = reinterpret_cast<float *>(part + 4 * n_part);
+    char *hblk = static_cast<char *>(c->step_host) + blk_off;
+    volatile uint32_t *host_flag =
+        reinterpret_cast<volatile uint32_t *>(static_cast<char *>(c->step_host) + (k ? elite_flag_off : flag_off));
+    uint32_t seq = 0;
+    if (!c->comm) {  // rollout + cost + V + the feasibility-first selection + the winner's row in one launch
+        seq = ++c->step_seq;
+        if (seq == 0) seq = ++c->step_seq;
+        char *hdev = static_cast<char *>(c->step_host_dev);
+        const RolloutConstrSelect sel{blk_dev, part, n_part, c->sync_ws() + 8, sa.global_offset,
+                                      fuse_clip ? clip_src : nullptr, fuse_clip ? clip_n : 0, hdev + blk_off,
+                                      reinterpret_cast<uint32_t *>(hdev + flag_off), seq};
+        HIP_TRY(launch_rollout_constr_select(sys, a->x0, sa.x_out, a->act_min, a->act_max, flag, B, H, *e->con, e->tol,
+                                             e->u_prev_host, a->cost_local, e->viol_local, st, &sel));
+    } else {
+        HIP_TRY(launch_rollout_constr_select(sys, a->x0, sa.x_out, a->act_min, a->act_max, flag, B, H, *e->con, e->tol,
+                                             e->u_prev_host, a->cost_local, e->viol_local, st, nullptr));
+        if ((rc = comm_gather(c, a->cost_local, a->costs_all, (size_t)B, 8, st))) return rc;
+        if ((rc = comm_gather(c, e->viol_local, e->viols_all, (size_t)B, 8, st))) return rc;
+        HIP_TRY(launch_topk_feasible(a->costs_all, e->viols_all, 1, B * c->nranks, 1, e->tol, 0, best_dev, viol_dev,
+                                     nfeas_dev, st));
+        HIP_TRY(launch_winner_row(best_dev, (int64_t)c->rank * B, B, sa.x_out, row, row_norm, st));
+        if ((rc = comm_reduce(c, row_norm, (size_t)row, COMM_SUM_F32, st))) return rc;
+        HIP_TRY(launch_unnormalize(row_norm, row, d.state_dim, flag, a->act_min, a->act_max, u_dev, st));
+        HIP_TRY(hipMemcpyAsync(code_dev, flag, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    }
+    if (k == 0 && next_out) {  // mpc_step_impl's STEP_WARM: the winner's normalised plan moved one horizon point ahead
+        if (!c->comm)
+            HIP_TRY(launch_shift_plans(sa.x_out, B, H, d.state_dim, &best_dev->index, sa.global_offset, 1, next_out, st));
+        else
+            HIP_TRY(launch_shift_plans(row_norm, 1, H, d.state_dim, nullptr, 0, 1, next_out, st));
+    }
+    if (k) {
+        // the k first of (cost_local, viol_local) in the feasibility-first order (entry 0 = the selection above), mirrored
+        // to mapped host memory with a completion word of their own, which the wait below takes: it follows the
+        // selecting launch on the stream, so the result block is complete too. Then every candidate's next prior.
+        char *hdev = static_cast<char *>(c->step_host_dev);
+        mpcd_best *el_dev = c->step_elite.as<mpcd_best>();
+        const TopkFeasMirror mir{reinterpret_cast<mpcd_best *>(hdev + elite_off), reinterpret_cast<double *>(hdev + eviol_off),
+                                 reinterpret_cast<uint32_t *>(hdev + elite_flag_off), seq};
+        HIP_TRY(launch_topk_feasible(a->cost_local, e->viol_local, 1, B, k, e->tol, sa.global_offset, el_dev,
+                                     reinterpret_cast<double *>(el_dev + MPCD_MAX_ELITES), nullptr, st, &mir));
+        if (next_out)
+            HIP_TRY(launch_elite_priors(sa.x_out, 1, B, H, d.state_dim, el_dev, k, sa.global_offset, 1, next_out, st));
+    }
+    if (c->comm) {
+        HIP_TRY(hipMemcpyAsync(hblk, c->step_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    } else {
+        // spin on the completion word, as mpc_step_impl does
+        for (uint32_t n = 1; *host_flag != seq; ++n) {
+            if ((n & 4095) == 0) {
+                const hipError_t q = hipStreamQuery(st);
+                if (q == hipSuccess && *host_flag != seq)
+                    return fail(MPCD_EHIP, "%s: the stream finished without the result block", fn);
+                if (q != hipSuccess && q != hipErrorNotReady) HIP_TRY(q);
+            }
+#if defined(__x86_64__) || defined(__i386__)
+            __builtin_ia32_pause();  // spin-wait hint (host CPU)
+#else
+            std::this_thread::yield();
+#endif
+        }
+        std::atomic_thread_fence(std::memory_order_acquire);
+    }
+    memcpy(best_host, hblk, sizeof(mpcd_best));
+    memcpy(u_best_host, hblk + sizeof(mpcd_best), sizeof(float) * (size_t)row);
+    int32_t code = 0;
+    memcpy(&code, hblk + sizeof(mpcd_best) + sizeof(float) * (size_t)row, sizeof code);
+    memcpy(e->viol_host, hblk + viol_off, sizeof(double));
+    memcpy(e->n_feasible_host, hblk + viol_off + sizeof(double), sizeof(int64_t));
+    if (k && e->elites_host) memcpy(e->elites_host, static_cast<char *>(c->step_host) + elite_off, sizeof(mpcd_best) * k);
+    if (k && e->elite_viol_host) memcpy(e->elite_viol_host, static_cast<char *>(c->step_host) + eviol_off, sizeof(double) * k);
+    c->step_flags = (code == 1 ? MPCD_STEP_CLIPPED : 0) | (code == 2 ? MPCD_STEP_NAN_SAMPLES : 0) |
+                    (*e->n_feasible_host == 0 ? MPCD_STEP_INFEASIBLE : 0);
+    if (!std::isfinite(best_host->cost)) {
+        c->step_flags |= MPCD_STEP_NONFINITE_WINNER;
+        return fail(MPCD_ENONFINITE, "%s: the selected candidate's cost is not finite (best %g, index %lld)%s", fn,
+                    best_host->cost, (long long)best_host->index, code == 2 ? "; NaN in the sampled trajectories" : "");
     }
     return MPCD_OK;
 }

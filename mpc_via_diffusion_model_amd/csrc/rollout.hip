@@ -744,6 +744,142 @@ __global__ __launch_bounds__(RT_THREADS) void rollout_cost_constr_kernel(const S
     }
 }
 
+// ---- The constraint set in the one-call control step (mpcd_mpc_step_constr): rollout_cost_kernel<SYS, SEL> with
+// ConstrVisit riding candidate_cost and the selection in the feasibility-first order. The one start state stays in
+// SysK; the set, the tolerance and the previous applied action (with its "has a predecessor" bit, decided on the host
+// by load_prev's rule) are a kernel argument of their own, so the step uploads nothing. cost[b] and viol[b] are the
+// bits rollout_cost_constr_kernel writes for group = batch: the same candidate_cost, the same visitor, the same finish.
+// SEL = false ends there (the multi-rank producer). SEL = true: wave_argmin3 over the workgroup's real lanes, its
+// feasible count by ballot and popcount, the hand-off through last_arriver with partials (V, cost, index, count); the
+// last workgroup reduces them in a strided loop (there may be more partials than lanes), sums the counts and writes
+// {best, winner row unnormalised, clip code, V, n_feasible} to the device block and to mapped host memory, then the
+// completion word (rollout_cost_kernel's system-scope fence protocol): entry 0, its V and the count of
+// topk_feasible_kernel(k = 1) over the two arrays. A kernel of its own and not a shared __device__ body with
+// rollout_cost_kernel, for the reason given at batch_step_box_tail_kernel.
+struct ConStepK {
+    ConK con;
+    double tol;
+    double u_prev[4];
+    int32_t has_prev, pad;
+};
+// The selection's addresses, few on purpose (scalar registers are what this kernel runs out of): the device result block
+// and its mapped host mirror share one layout, {mpcd_best, winner row [H * n_u] fp32, clip code int32, padding to 8
+// bytes, V double, n_feasible int64} (step_constr_viol_off), and the four partial arrays are one block of 4 * gridDim.x
+// 8-byte entries: V, cost, index, count.
+struct ConSelectK {
+    char *block;          // the device result block
+    double *part;         // [4][gridDim.x]
+    unsigned *counter;
+    int64_t offset;       // global index of candidate 0
+    const float *clip_src;  // optional: the clip code computed here over clip_src[0, clip_n)
+    int64_t clip_n;
+    char *host_out;       // optional: the block mirrored to mapped host memory + a completion word
+    uint32_t *host_flag;
+    uint32_t host_seq;
+};
+template <int SYS, bool SEL>
+__global__ __launch_bounds__(RT_THREADS) void rollout_constr_select_kernel(const SysK S, const ConStepK C,
+                                                                           const float *u_norm, const int *flags,
+                                                                           int64_t batch, int H, double *cost,
+                                                                           double *viol, const ConSelectK K)
+{
+    constexpr int nx = SysDim<SYS>::NX, nu = SysDim<SYS>::NU;
+    extern __shared__ float su[];  // [RT_THREADS][H*nu + 1]
+    const int row = H * nu, stride = row + 1;
+    const int64_t c0 = (int64_t)blockIdx.x * RT_THREADS;
+    stage_rows(u_norm + (size_t)c0 * row, min((int64_t)RT_THREADS, batch - c0), row, su);
+    int code = 0;  // SEL with clip_src: the clip code, recomputed by every workgroup
+    if constexpr (SEL) {
+        if (K.clip_src) code = state_clip_code(K.clip_src, K.clip_n);
+    }
+    __syncthreads();
+    const int64_t b = min(c0 + threadIdx.x, batch - 1);  // lanes past the batch recompute the last one
+    const bool clip = (SEL && K.clip_src) ? code == 1 : flags[0] == 1;
+    double x[nx], up[nu];
+#pragma unroll
+    for (int i = 0; i < nx; ++i) x[i] = S.x0[i];
+#pragma unroll
+    for (int j = 0; j < nu; ++j) up[j] = C.u_prev[j];
+    bool has = C.has_prev != 0;
+    double Vacc = 0.0;
+    bool bad = false;
+    const double J = candidate_cost<SYS>(S, su + (b - c0) * stride, clip, x, H, ConstrVisit<nx, nu>{C.con, Vacc, bad, up, has});
+    const double V = BoxVisit<nx>::finish(Vacc, bad);  // never NaN: a NaN excess is +inf
+    const bool real = c0 + threadIdx.x < batch;
+    if (real) {
+        cost[b] = J;
+        viol[b] = V;
+    }
+    if constexpr (SEL) {
+        const double tol = C.tol;
+        double wV = V, wv = isnan(J) ? INFINITY : J;
+        int64_t wi = real ? b : -1;  // lanes past the batch are never entrants
+        int64_t nf = __popcll(__ballot(real && V <= tol));
+        wave_argmin3(wV, wv, wi, tol);  // RT_THREADS == one wave; every lane holds the result
+        const int slot = (int)blockIdx.x, nslots = (int)gridDim.x;
+        double *part_viol = K.part, *part_cost = part_viol + nslots;
+        int64_t *part_idx = reinterpret_cast<int64_t *>(part_cost + nslots), *part_nfeas = part_idx + nslots;
+        if (!last_arriver(
+                K.counter, nslots,
+                [&] {
+                    part_viol[slot] = wV;
+                    part_cost[slot] = wv;
+                    part_idx[slot] = wi;
+                    part_nfeas[slot] = nf;
+                },
+                [&] {
+                    double lV = INFINITY, lg = INFINITY, lv = INFINITY;
+                    int64_t li = -1, s = 0;
+                    for (int k = threadIdx.x; k < nslots; k += RT_THREADS) {
+                        const double pV = __builtin_nontemporal_load(part_viol + k);
+                        const double pv = __builtin_nontemporal_load(part_cost + k);
+                        const int64_t pi = __builtin_nontemporal_load(part_idx + k);
+                        const double pg = box_key(pV, tol);
+                        if (better3(pg, pv, pi, lg, lv, li)) { lV = pV; lg = pg; lv = pv; li = pi; }
+                        s += __builtin_nontemporal_load(part_nfeas + k);
+                    }
+                    wV = lV;
+                    wv = lv;
+                    wi = li;
+                    wave_argmin3(wV, wv, wi, tol);
+#pragma unroll
+                    for (int q = 32; q >= 1; q >>= 1) s += __shfl_xor(s, q);
+                    nf = s;
+                }))
+            return;
+        const int32_t ccode = K.clip_src ? code : flags[0];
+        const size_t viol_off = step_constr_viol_off(row);
+        float *drow = reinterpret_cast<float *>(K.block + sizeof(mpcd_best));
+        float *hrow = K.host_out ? reinterpret_cast<float *>(K.host_out + sizeof(mpcd_best)) : nullptr;
+        if (threadIdx.x == 0) {
+            const mpcd_best bst{wv, wi < 0 ? -1 : K.offset + wi};
+            *reinterpret_cast<mpcd_best *>(K.block) = bst;
+            *reinterpret_cast<int32_t *>(drow + row) = ccode;
+            *reinterpret_cast<double *>(K.block + viol_off) = wV;
+            *reinterpret_cast<int64_t *>(K.block + viol_off + sizeof(double)) = nf;
+            if (hrow) {
+                *reinterpret_cast<mpcd_best *>(K.host_out) = bst;
+                *reinterpret_cast<int32_t *>(hrow + row) = ccode;
+                *reinterpret_cast<double *>(K.host_out + viol_off) = wV;
+                *reinterpret_cast<int64_t *>(K.host_out + viol_off + sizeof(double)) = nf;
+            }
+        }
+        if (wi >= 0) {
+            const bool clip0 = ccode == 1;
+            for (int k = threadIdx.x; k < row; k += RT_THREADS) {
+                const float o = unnorm1(u_norm[(size_t)wi * row + k], clip0, S.umin[k % nu], S.umax[k % nu]);
+                drow[k] = o;
+                if (hrow) hrow[k] = o;
+            }
+        }
+        if (hrow) {  // every lane's host stores ordered before the completion word
+            __threadfence_system();
+            __syncthreads();
+            if (threadIdx.x == 0) __hip_atomic_store(K.host_flag, K.host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
 // Per-group clip flags: flags[g] = the clip code above over x[g*group_elems, (g+1)*group_elems)
 // (LimitsNormalizer's rule applied to each plant state's own candidate batch). One workgroup per group:
 // every flag is written, so no memset is needed.
@@ -1492,6 +1628,43 @@ hipError_t launch_rollout_cost_constr(const mpcd_system_desc &d, const double *x
     return dispatch_system(d, [&](auto sys) {
         hipLaunchKernelGGL(rollout_cost_constr_kernel<decltype(sys)::value>, dim3((unsigned)wgs), dim3(RT_THREADS), lds,
                            stream, S, ck, u_norm, flags_dev, x0_dev, u_prev_dev, group, batch, H, cost, viol);
+    });
+}
+
+hipError_t launch_rollout_constr_select(const mpcd_system_desc &d, const double *x0_host, const float *u_norm,
+                                        const float *umin_host, const float *umax_host, const int *flag_dev, int64_t batch,
+                                        int H, const mpcd_constraints &con, double tol, const double *u_prev_host,
+                                        double *cost, double *viol, hipStream_t stream, const RolloutConstrSelect *sel)
+{
+    const int64_t wgs = (batch + RT_THREADS - 1) / RT_THREADS;
+    if (batch < 1 || wgs > 0x7fffffff || con.n_rows < 0 || con.n_rows > MPCD_MAX_CON_ROWS || !(tol >= 0.0) || !x0_host)
+        return hipErrorInvalidValue;
+    SysK S = make_sysk(d, umin_host, umax_host);
+    for (int i = 0; i < d.n_x; ++i) S.x0[i] = x0_host[i];
+    ConStepK C = {};
+    C.con = make_conk(d, con);
+    C.tol = tol;
+    C.has_prev = u_prev_host != nullptr;  // ConstrVisit::load_prev's rule: a NaN in any entry means "none"
+    for (int j = 0; j < d.n_u && j < 4; ++j) {
+        C.u_prev[j] = u_prev_host ? u_prev_host[j] : 0.0;
+        if (C.u_prev[j] != C.u_prev[j]) C.has_prev = 0;
+    }
+    ConSelectK K = {};
+    if (sel) {
+        if (!sel->block || !sel->part || sel->n_part < wgs || !sel->counter || (sel->host_out && !sel->host_flag))
+            return hipErrorInvalidValue;
+        K = ConSelectK{sel->block,  sel->part,     sel->counter,   sel->offset,  sel->clip_src,
+                       sel->clip_n, sel->host_out, sel->host_flag, sel->host_seq};
+    }
+    const size_t lds = sizeof(float) * RT_THREADS * (H * d.n_u + 1);
+    return dispatch_system(d, [&](auto sys) {
+        constexpr int SYS = decltype(sys)::value;
+        if (sel)
+            hipLaunchKernelGGL((rollout_constr_select_kernel<SYS, true>), dim3((unsigned)wgs), dim3(RT_THREADS), lds, stream,
+                               S, C, u_norm, flag_dev, batch, H, cost, viol, K);
+        else
+            hipLaunchKernelGGL((rollout_constr_select_kernel<SYS, false>), dim3((unsigned)wgs), dim3(RT_THREADS), lds, stream,
+                               S, C, u_norm, flag_dev, batch, H, cost, viol, K);
     });
 }
 

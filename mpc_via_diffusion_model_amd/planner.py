@@ -116,6 +116,7 @@ class MPCResult:
     elite_cost: np.ndarray = None   # [k] fp64 their costs, nondecreasing (a NaN cost is reported as +inf)
     violation: float = None  # state_box= / constraints=: the selected candidate's violation V (0.0 = admissible)
     n_feasible: int = None   # state_box=: how many candidates have V <= viol_tol (0: the least violating was selected)
+    elite_violation: np.ndarray = None  # [k] fp64 mpc_step_constr(elites=k): V of each ranked candidate
 
 
 @dataclass
@@ -1409,8 +1410,8 @@ class DiffusionMPC:
         composed step, single rank (native then defaults to False): mpcd_rollout_cost_box gives every candidate's cost
         and box violation, and the winner is entry 0 of mpcd_topk_feasible - the cheapest candidate whose predicted
         states stay in the box, or, when none does, the least violating one. The result carries violation and
-        n_feasible. ValueError with native=True, warm_start / prior / elites, a comm or several ranks: the fused step
-        and the multi-rank selection with a box are the follow-up.
+        n_feasible. ValueError with native=True, warm_start / prior / elites, a comm or several ranks: those are
+        mpc_step_constr's, the one-call step with a set (a plain box is Constraints(state_box=...)).
         constraints=Constraints(...), u_prev [n_u] or None: the same composed step with mpcd_rollout_cost_constr as the
         producer of V (the box goes into the set: state_box= together with constraints= raises ValueError); u_prev is the
         previous applied action, the predecessor of u_0 in the rate test. Same result fields, same refusals."""
@@ -1496,6 +1497,112 @@ class DiffusionMPC:
         u_host = u_best.cpu().numpy()
         return MPCResult(u0=u_host[0].copy(), u_best=u_host, best_cost=best, best_index=idx, costs=costs,
                          u_norm=u_norm)
+
+    def mpc_step_constr(self, x0, system: System, n_samples, constraints, viol_tol=0.0, u_prev=None, w=0.01,
+                        sample_fn="ddpm_cfg", n_wo_noise=0, ddim_steps=None, clamp_x0=False, seed=0, noise=None, comm=None,
+                        clip_rule="chain", warm_start=None, prior=None, elites=None):
+        """mpc_step's native step with a constraint set and the feasibility-first selection (mpcd_mpc_step_constr;
+        DESIGN §4 "Constraint set in the one-call step"): one library call, on one rank or over a NativeComm's ranks,
+        cold, warm-started (warm_start=K, prior=) or with an elite set (elites=k, single rank), exactly as in mpc_step.
+        constraints: a Constraints (a plain box is Constraints(state_box=...)); viol_tol >= 0; u_prev [n_u] or None: the
+        action applied last, the predecessor of u_0 in the rate test (a NaN entry: none). The winner is the cheapest
+        candidate of all ranks whose violation V is <= viol_tol or, when there is none, the least violating one (flags
+        then carries MPCD_STEP_INFEASIBLE). The kept prior (reset_warm_start(), warm_prior()) is mpc_step's: a loop may
+        alternate the two methods. Returns an MPCResult with violation, n_feasible (over all ranks), flags and costs
+        (all ranks' gathered costs); with elites also elite_index, elite_cost and elite_violation.
+        ValueError: constraints that is no Constraints, a bad viol_tol, a u_prev that is not [n_u], elites without
+        warm_start or with a comm, several torch.distributed ranks without a NativeComm."""
+        if clip_rule not in _CLIP_RULES:
+            raise ValueError(f"clip_rule must be one of {sorted(_CLIP_RULES)}")
+        con = self._constraints(constraints, system)
+        tol = self._viol_tol(viol_tol)
+        up = None
+        if u_prev is not None:
+            up = np.ascontiguousarray(u_prev.detach().cpu().numpy() if torch.is_tensor(u_prev) else u_prev, dtype=np.float64)
+            if up.shape != (system.n_u,):
+                raise ValueError(f"u_prev must be [{system.n_u}], got {tuple(up.shape)}")
+        if elites is not None:
+            if warm_start is None:
+                raise ValueError("elites needs warm_start=K: the elite set seeds the warm-start priors")
+            if comm is not None:
+                raise ValueError("elites is single-rank: the elite rows live on other ranks (no comm)")
+        if comm is not None:
+            rank, size = comm.rank, comm.size
+        else:
+            rank, size = D.world(None)
+            if size > 1:
+                raise ValueError("mpc_step_constr on several ranks needs a NativeComm")
+        B, H, d = int(n_samples), self.spec.horizon, self.spec.state_dim
+        if d != system.n_u:
+            raise ValueError(f"system {system.name} has {system.n_u} inputs, samples have {d}")
+        sampler = self._sampler_id(sample_fn)
+        warm = nxt = None
+        if warm_start is not None or prior is not None:
+            K = int(warm_start) if warm_start is not None else 0
+            if K < 1 or K > self.n_steps or sampler != N.MPCD_DDPM_CFG:
+                raise ValueError(f"warm_start={warm_start} needs 1 <= K <= {self.n_steps} and the CFG-DDPM sampler")
+            if elites is not None:
+                elites = self._check_elites(elites, B)
+            if prior is None:
+                prior = getattr(self, "_prior", None)
+                if elites is not None and prior is not None and prior.shape[0] not in (1, B):
+                    raise ValueError(f"the stored priors have {prior.shape[0]} rows, neither 1 nor n_samples={B}: call "
+                                     "reset_warm_start() after changing n_samples")
+            warm, prior = self._warm(prior, K if prior is not None else 0, B)  # no prior yet: a cold step that fills it
+            if elites is None and prior is not None and prior.shape[0] != 1:
+                raise ValueError(f"prior must be one plan [{H}, {d}], got {tuple(prior.shape)}")
+            rows = 1 if elites is None else B  # the next priors: the winner's plan, or one per candidate
+            nxt = getattr(self, "_prior_spare", None)
+            if nxt is None or nxt.shape[0] != rows or (prior is not None and nxt.data_ptr() == prior.data_ptr()):
+                nxt = torch.empty((rows, H, d), dtype=torch.float32, device=self.device)
+        if noise is not None:
+            steps = self.n_denoise_steps(sample_fn, n_wo_noise, ddim_steps, warm.t_start or None if warm else None)
+            noise = noise.to(self.device, torch.float32).contiguous()
+            if tuple(noise.shape) != (steps + 1, B, H, d):
+                raise ValueError(f"noise must be [{steps + 1}, {B}, {H}, {d}], got {tuple(noise.shape)}")
+        u_norm = torch.empty((B, H, d), dtype=torch.float32, device=self.device)
+        cost = torch.empty(B, dtype=torch.float64, device=self.device)
+        viol = torch.empty(B, dtype=torch.float64, device=self.device)
+        costs = torch.empty(size * B, dtype=torch.float64, device=self.device) if size > 1 else cost
+        viols = torch.empty(size * B, dtype=torch.float64, device=self.device) if size > 1 else viol
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        desc = self._system_desc(system)
+        a = N.StepArgs()
+        a.sys = ctypes.pointer(desc)
+        a.ctx_min, a.ctx_max = self.ctx_min.ctypes.data, self.ctx_max.ctypes.data
+        a.act_min, a.act_max = self.act_min.ctypes.data, self.act_max.ctypes.data
+        a.sample = self._args(sampler, B, _STEP_CONTEXT, w, n_wo_noise, ddim_steps, clamp_x0, seed, rank * B, noise, u_norm,
+                              None)
+        a.clip_rule = _CLIP_RULES[clip_rule]
+        if clip_rule == "final" and sampler == N.MPCD_DDPM_CFG and self.ddpm_final_in_range:
+            a.clip_rule = N.MPCD_CLIP_NONE
+        a.x0 = x0.__array_interface__["data"][0]
+        a.cost_local, a.costs_all = cost.data_ptr(), costs.data_ptr()
+        e = N.StepConstrArgs()
+        e.con, e.tol = ctypes.pointer(con), tol
+        e.u_prev_host = up.ctypes.data if up is not None else None
+        e.viol_local, e.viols_all = viol.data_ptr(), viols.data_ptr()
+        e.k = elites or 0
+        e.next_priors_out = nxt.data_ptr() if nxt is not None else None
+        el = ev = None
+        if elites is not None:
+            el, ev = np.empty(elites, dtype=_BEST), np.empty(elites, dtype=np.float64)
+            e.elites_host, e.elite_viol_host = el.ctypes.data, ev.ctypes.data
+        v_host, nf_host = ctypes.c_double(), ctypes.c_int64()
+        e.viol_host, e.n_feasible_host = ctypes.pointer(v_host), ctypes.pointer(nf_host)
+        best, fl = N.Best(), ctypes.c_int32()
+        u_best = np.empty((H, d), dtype=np.float32)
+        # MPCD_ENONFINITE (the selected cost is not finite: NaN / Inf samples) raises MpcdError here
+        N.check(self._lib.mpcd_mpc_step_constr(self._ctx, ctypes.byref(a), ctypes.byref(warm) if warm is not None else None,
+                                               ctypes.byref(e), ctypes.byref(best), u_best.__array_interface__["data"][0],
+                                               self._stream()), "mpcd_mpc_step_constr")
+        if nxt is not None:  # the refreshed prior becomes the next call's; this call's buffer is the next one's output
+            self._prior, self._prior_spare = nxt, getattr(self, "_prior", None)
+        N.check(self._lib.mpcd_last_step_flags(self._ctx, ctypes.byref(fl)), "mpcd_last_step_flags")
+        return MPCResult(u0=u_best[0].copy(), u_best=u_best, best_cost=best.cost, best_index=best.index, costs=costs,
+                         u_norm=u_norm, flags=fl.value, elite_index=None if el is None else el["index"].copy(),
+                         elite_cost=None if el is None else el["cost"].copy(), violation=v_host.value,
+                         n_feasible=nf_host.value, elite_violation=ev)
 
     def reset_warm_start(self):
         """Drop the prior plan mpc_step(warm_start=K) keeps and the prior set mpc_step_batch(warm_start=K) keeps: the

@@ -20,6 +20,8 @@
 #                       the table goes to standard output, extra arguments come from $AB_ARGS
 #   constrab            tools/constraints_ab.py: the constraint set beside the box (rollout and batched step) and the
 #                       unchanged paths against the same parent build; table to standard output, $AB_ARGS as above
+#   stepconstrab        tools/step_constr_ab.py: the constraint set in the one-call control step (mpc_step_constr) beside
+#                       mpc_step and the composed constrained step, against the same parent build; as above
 #
 # Extra bench.py arguments for bench / trace / pmc come from $BENCH_ARGS; extra pytest arguments from
 # $PYTEST_ARGS; extra unet_perf.py arguments from $UNET_ARGS.
@@ -95,6 +97,9 @@ run_job() {
         --parent-lib "${PARENT_LIB:-mpc_via_diffusion_model_amd/libmpcd_parent.so}" $AB_ARGS ;;
     constrab)
       timeout -k 10 900 python -u tools/constraints_ab.py \
+        --parent-lib "${PARENT_LIB:-mpc_via_diffusion_model_amd/libmpcd_parent.so}" $AB_ARGS ;;
+    stepconstrab)
+      timeout -k 10 900 python -u tools/step_constr_ab.py \
         --parent-lib "${PARENT_LIB:-mpc_via_diffusion_model_amd/libmpcd_parent.so}" $AB_ARGS ;;
     unet)
       local c=${arg:-cfg5}
