@@ -296,10 +296,10 @@ struct mpcd_ctx {
     int nranks = 1, rank = 0;
     // flag: [0] internal clip flag, [16..] zero-initialised counters of the self-resetting reductions
     unsigned *sync_ws() const { return flag.as<unsigned>() + 16; }
-    // mpcd_mpc_step: device context row, per-block argmin partials, {best, winner row} result block
-    // and its pinned host mirror (one D2H copy per control step)
-    DevBuf step_ctx, step_part, step_out, step_amax;
-    DevBuf step_elite;  // mpcd_mpc_step_elite: the k elites on the device, mpcd_best [MPCD_MAX_ELITES]
+    // mpcd_mpc_step and its siblings: per-workgroup selection partials, the device result block, the chain maxima;
+    // the block's mapped host mirror is step_host (StepHostPart)
+    DevBuf step_part, step_out, step_amax;
+    DevBuf step_elite;  // the k elites on the device, mpcd_best [MPCD_MAX_ELITES], with a set their V double [..] behind
     // mpcd_closed_loop: partials, samples, chain maxima, context rows and priors; one self-resetting counter per state
     DevBuf loop_ws, loop_cnt;
     // mpcd_mpc_step_batch: the same kinds of parts plus the states and the packed result block; its own self-resetting
@@ -632,7 +632,7 @@ void mpcd_destroy(mpcd_ctx *c)
     if (!c) return;
     DeviceGuard device_guard_(c->device);
     for (DevBuf *b : {&c->params, &c->wpack, &c->wpack3, &c->wpackh, &c->cond_layers, &c->unet_pack, &c->plan, &c->tproj, &c->cproj, &c->flag,
-                      &c->unet_ws, &c->step_ctx, &c->step_part, &c->step_out, &c->step_amax, &c->step_elite, &c->loop_ws, &c->loop_cnt,
+                      &c->unet_ws, &c->step_part, &c->step_out, &c->step_amax, &c->step_elite, &c->loop_ws, &c->loop_cnt,
                       &c->batch_ws, &c->batch_cnt})
         b->release();
     for (int i = 0; i < mpcd_ctx::kEvRing; ++i)
@@ -1882,22 +1882,256 @@ int mpcd_select(mpcd_ctx *c, const double *cost_local, int64_t n_local, const fl
     return comm_reduce(c, row_out, (size_t)row_len, COMM_SUM_F32, st);
 }
 
-// STEP_WARM (mpcd_mpc_step_warm): the sampler call takes the resolved warm start and, next_init_out non-null, one
-// shift_plan launch on the winner follows the selection. STEP_ELITE (mpcd_mpc_step_elite): the warm sampler call, then
-// the top-k launch over cost_local and the elite-prior launch into next_init_out ([batch][H][d] here); the call waits
-// for the top-k launch's completion word. A template value: mpcd_mpc_step's and mpcd_mpc_step_warm's instantiations
-// compile the code they had, with no branch on any of it.
-enum { STEP_COLD = 0, STEP_WARM = 1, STEP_ELITE = 2 };
-struct EliteArgs {
-    int32_t k;
-    mpcd_best *elites_host;  // [k] or null
-};
-extern "C++" {  // templates cannot have C linkage
-template <int MODE>
-static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream,
-                         const WarmArgs *warm = nullptr, float *next_init_out = nullptr,
-                         const EliteArgs *elite = nullptr);
+// ---- the single-state control step: mpcd_mpc_step, _warm, _elite and _constr are one host body (mpc_step_impl)
 
+// The step's mapped host block, a function of row = H * n_u alone and sized once for all four entry points. It has two
+// parts of one shape, the plain calls' first and mpcd_mpc_step_constr's behind it: [result block | completion word |
+// the k elites, MPCD_MAX_ELITES entries | their V (constrained part only) | the ranking launch's completion word], each
+// completion word on a 64-byte line of its own. The plain result block is {best, winner row [row] fp32, clip code
+// int32}, the constrained one adds {V, n_feasible} (step_constr_out_bytes). The parts are disjoint, so neither kind of
+// call ever finds the other's data where it waits for a completion word.
+struct StepHostPart {
+    size_t out_bytes, out, flag, elites, eviol, elite_flag, end;
+};
+static StepHostPart step_host_part(int row, bool constr)
+{
+    StepHostPart p;
+    p.out_bytes = constr ? step_constr_out_bytes(row) : sizeof(mpcd_best) + sizeof(float) * (size_t)row + sizeof(int32_t);
+    p.out = constr ? step_host_part(row, false).end : 0;
+    p.flag = p.out + ((p.out_bytes + 63) & ~(size_t)63);
+    p.elites = p.flag + 64;
+    p.eviol = p.elites + sizeof(mpcd_best) * MPCD_MAX_ELITES;
+    p.elite_flag = p.eviol + (constr ? sizeof(double) * MPCD_MAX_ELITES : 0);
+    p.end = p.elite_flag + 64;
+    return p;
+}
+
+// The block for this row (a net loaded later may need a larger one); a new block is zeroed and step_seq starts again
+static int step_host_ensure(mpcd_ctx *c, int row)
+{
+    const size_t bytes = step_host_part(row, true).end;
+    if (c->step_host_bytes >= bytes) return MPCD_OK;
+    if (c->step_host) (void)hipHostFree(c->step_host);
+    c->step_host = nullptr;
+    c->step_host_dev = nullptr;
+    c->step_host_bytes = 0;
+    // coherent (fine-grained) mapped memory: the selecting workgroup's system-scope stores of the result block
+    // and the completion word reach the host without depending on HIP_HOST_COHERENT's default
+    HIP_TRY(hipHostMalloc(&c->step_host, bytes, hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(hipHostGetDevicePointer(&c->step_host_dev, c->step_host, 0));
+    memset(c->step_host, 0, bytes);
+    c->step_seq = 0;
+    c->step_host_bytes = bytes;
+    return MPCD_OK;
+}
+
+// The launch that wrote a result to mapped host memory stores seq into its completion word last: spin on that word
+// (no copy launch, no stream synchronisation wake-up); the stream is queried now and then so that a failed launch
+// cannot leave this loop waiting
+static int wait_result(hipStream_t st, const volatile uint32_t *host_flag, uint32_t seq, const char *fn)
+{
+    for (uint32_t n = 1; *host_flag != seq; ++n) {
+        if ((n & 4095) == 0) {
+            const hipError_t q = hipStreamQuery(st);
+            if (q == hipSuccess && *host_flag != seq)
+                return fail(MPCD_EHIP, "%s: the stream finished without the result block", fn);
+            if (q != hipSuccess && q != hipErrorNotReady) HIP_TRY(q);
+        }
+#if defined(__x86_64__) || defined(__i386__)
+        __builtin_ia32_pause();  // spin-wait hint (host CPU)
+#else
+        std::this_thread::yield();
+#endif
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return MPCD_OK;
+}
+
+// Do the float ranges [a, a + n_a) and [b, b + n_b) share an element?
+static bool overlaps(const float *a, size_t n_a, const float *b, size_t n_b) { return a < b + n_b && b < a + n_a; }
+
+// What the four entry points ask of the one body
+struct StepCall {
+    const char *fn;                             // the name in the shared messages
+    const WarmArgs *warm = nullptr;             // null: the cold sampler call
+    int32_t k = 0;                              // elites to rank (single rank), 0: none
+    // null, or the next priors: k == 0 the winner's plan [H][d] moved one horizon point ahead, else every
+    // candidate's, [batch][H][d]
+    float *next_out = nullptr;
+    mpcd_best *elites_host = nullptr;           // [k] or null
+    const mpcd_step_constr_args *e = nullptr;   // mpcd_mpc_step_constr: the set, the extra outputs; null: a plain step
+};
+
+// One attempt of the control step. The sampler call (warm or cold), the clip flag, the selecting launch, the next
+// priors, the wait and the decoding are the same for every entry point; with e the selecting launch is
+// rollout_constr_select_kernel's, selection and ranking follow the feasibility-first order, and the result block
+// carries V and n_feasible.
+static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, const StepCall &s, mpcd_best *best_host, float *u_best_host,
+                         void *stream)
+{
+    const mpcd_step_constr_args *e = s.e;
+    if (!c || !a || !a->sys || !a->x0 || !a->act_min || !a->act_max || !a->cost_local || !best_host || !u_best_host)
+        return fail(MPCD_EINVAL, "null argument");
+    if (!c->net_loaded) return fail(MPCD_ESTATE, "no net loaded");
+    const mpcd_net_desc &d = c->desc;
+    const mpcd_system_desc &sys = *a->sys;
+    const int64_t B = a->sample.batch;
+    const int H = d.horizon, row = H * d.state_dim, k = s.k;
+    if (B < 1 || !a->sample.x_out) return fail(MPCD_EINVAL, "sample.batch / sample.x_out");
+    if (sys.n_u != d.state_dim) return fail(MPCD_EINVAL, "system n_u %d != net state_dim %d", sys.n_u, d.state_dim);
+    int rc = check_system(&sys, H);
+    if (rc) return rc;
+    if (e && (rc = check_constraints(s.fn, e->con, sys.n_x, sys.n_u))) return rc;
+    if (d.context_dim > 0 && (!a->ctx_min || !a->ctx_max)) return fail(MPCD_EINVAL, "ctx_min / ctx_max");
+    if (d.context_dim > 0 && d.context_dim != sys.n_x) return fail(MPCD_EINVAL, "context_dim %d != n_x %d", d.context_dim, sys.n_x);
+    if (c->comm && !a->costs_all) return fail(MPCD_EINVAL, "costs_all is required with a communicator");
+    if (a->clip_rule < MPCD_CLIP_CHAIN || a->clip_rule > MPCD_CLIP_NONE) return fail(MPCD_EINVAL, "clip_rule %d", a->clip_rule);
+    // the prior launches read x_out and write next_out (mpcd_mpc_step_warm's one row is not held to this)
+    if (s.next_out && (e || k) && overlaps(s.next_out, (size_t)(k ? B : 1) * row, a->sample.x_out, (size_t)B * row))
+        return fail(MPCD_EINVAL, "%s: next_priors_out overlaps sample.x_out", e ? s.fn : "mpcd_mpc_step_elite");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    DEVICE_GUARD(c->device);
+
+    const StepHostPart hp = step_host_part(row, e != nullptr);
+    if ((rc = step_host_ensure(c, row)) || (rc = c->step_out.ensure(hp.out_bytes))) return rc;
+    // per rollout workgroup the partials {cost, index} or, with a set, {V, cost, index, feasible count}; then the
+    // all-reduced winner row of the multi-rank step
+    const int64_t n_part = (B + kRolloutBlock - 1) / kRolloutBlock;
+    const size_t part_bytes = (e ? 32 : 16) * (size_t)n_part;
+    if ((rc = c->step_part.ensure(part_bytes + sizeof(float) * (size_t)row))) return rc;
+    if (k && (rc = c->step_elite.ensure((sizeof(mpcd_best) + (e ? sizeof(double) : 0)) * MPCD_MAX_ELITES))) return rc;
+
+    // normalize_condition (A12), fp64 then the net's .float(); the row travels by value (context_dim == n_x <= 12)
+    mpcd_sample_args sa = a->sample;
+    CtxRowArg ctx_row{};
+    sa.context = nullptr;
+    if (d.context_dim > 0) {
+        for (int i = 0; i < d.context_dim; ++i) {
+            const double den = (double)(a->ctx_max[i] - a->ctx_min[i]);
+            ctx_row.v[i] = (float)(2.0 * ((a->x0[i] - (double)a->ctx_min[i]) / den) - 1.0);
+        }
+        sa.context_shared = 1;
+    }
+    sa.chain_absmax = nullptr;
+    if (a->clip_rule == MPCD_CLIP_CHAIN) {
+        if ((rc = c->step_amax.ensure(sizeof(float) * (size_t)B))) return rc;
+        sa.chain_absmax = c->step_amax.as<float>();
+    }
+    if ((rc = sample_impl(c, &sa, stream, d.context_dim > 0 ? &ctx_row : nullptr, 0, s.warm))) return rc;
+
+    // LimitsNormalizer's global clip flag over the chain (the reference's unnormalize_states of run_CFG's
+    // whole chain), over the final samples, or proven 0; max-reduced over ranks (see mpcd_clip_flag)
+    int *flags = c->flag.as<int>();
+    const int *flag = flags + 1;  // flag[1] is never written: a constant 0
+    // single rank, a small clip input: the selecting rollout launch computes the clip code itself (each
+    // workgroup over the whole input, <= kFuseClipMax floats) - one launch fewer per control step
+    const float *clip_src = a->clip_rule == MPCD_CLIP_CHAIN ? sa.chain_absmax : sa.x_out;
+    const int64_t clip_n = a->clip_rule == MPCD_CLIP_CHAIN ? B : B * row;
+    const bool fuse_clip = !c->comm && a->clip_rule != MPCD_CLIP_NONE && clip_n <= kFuseClipMax;
+    if (a->clip_rule != MPCD_CLIP_NONE && !fuse_clip) {
+        HIP_TRY(launch_clip_flag(clip_src, clip_n, flags, c->sync_ws(), st));
+        if ((rc = comm_reduce(c, flags, 1, COMM_MAX_I32, st))) return rc;
+        flag = flags;
+    }
+    char *blk_dev = c->step_out.as<char>();
+    mpcd_best *best_dev = reinterpret_cast<mpcd_best *>(blk_dev);
+    float *u_dev = reinterpret_cast<float *>(best_dev + 1);
+    int32_t *code_dev = reinterpret_cast<int32_t *>(u_dev + row);
+    double *part = c->step_part.as<double>();
+    float *row_norm = reinterpret_cast<float *>(c->step_part.as<char>() + part_bytes);
+    char *host = static_cast<char *>(c->step_host), *hdev = static_cast<char *>(c->step_host_dev);
+    // one rank: rollout + cost (+ V) + the selection + the winner's unnormalised row + the clip code in one launch,
+    // which also writes the result block and then seq to mapped host memory
+    const bool one = !c->comm;
+    uint32_t seq = 0;
+    if (one) {
+        seq = ++c->step_seq;
+        if (seq == 0) seq = ++c->step_seq;
+    }
+    uint32_t *flag_hdev = reinterpret_cast<uint32_t *>(hdev + hp.flag);
+    if (e) {
+        const RolloutConstrSelect sel{blk_dev, part, n_part, c->sync_ws() + 8, sa.global_offset,
+                                      fuse_clip ? clip_src : nullptr, fuse_clip ? clip_n : 0, hdev + hp.out, flag_hdev, seq};
+        HIP_TRY(launch_rollout_constr_select(sys, a->x0, sa.x_out, a->act_min, a->act_max, flag, B, H, *e->con, e->tol,
+                                             e->u_prev_host, a->cost_local, e->viol_local, st, one ? &sel : nullptr));
+    } else {
+        const RolloutSelect sel{best_dev, u_dev, part, reinterpret_cast<int64_t *>(part + n_part), c->sync_ws() + 8, n_part,
+                                sa.global_offset, code_dev, fuse_clip ? clip_src : nullptr, fuse_clip ? clip_n : 0,
+                                hdev + hp.out, flag_hdev, seq};
+        HIP_TRY(launch_rollout_cost(sys, a->x0, nullptr, B, sa.x_out, a->act_min, a->act_max, flag, B, H, a->cost_local, st,
+                                    one ? &sel : nullptr));
+    }
+    if (!one) {  // the selection over every rank's candidates, the winner's row all-reduced from the rank that has it
+        if ((rc = comm_gather(c, a->cost_local, a->costs_all, (size_t)B, 8, st))) return rc;
+        if (e) {
+            double *viol_dev = reinterpret_cast<double *>(blk_dev + step_constr_viol_off(row));
+            if ((rc = comm_gather(c, e->viol_local, e->viols_all, (size_t)B, 8, st))) return rc;
+            HIP_TRY(launch_topk_feasible(a->costs_all, e->viols_all, 1, B * c->nranks, 1, e->tol, 0, best_dev, viol_dev,
+                                         reinterpret_cast<int64_t *>(viol_dev + 1), st));
+        } else {
+            HIP_TRY(launch_argmin(a->costs_all, B * c->nranks, 0, best_dev, st));
+        }
+        HIP_TRY(launch_winner_row(best_dev, (int64_t)c->rank * B, B, sa.x_out, row, row_norm, st));
+        if ((rc = comm_reduce(c, row_norm, (size_t)row, COMM_SUM_F32, st))) return rc;
+        HIP_TRY(launch_unnormalize(row_norm, row, d.state_dim, flag, a->act_min, a->act_max, u_dev, st));
+        HIP_TRY(hipMemcpyAsync(code_dev, flag, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    }
+    if (k == 0 && s.next_out) {
+        // the next step's prior: the winner's normalised plan moved one horizon point ahead. One rank: the row of
+        // x_out that the device-resident best.index names; ranks: the all-reduced winner row (the same on each)
+        if (one)
+            HIP_TRY(launch_shift_plans(sa.x_out, B, H, d.state_dim, &best_dev->index, sa.global_offset, 1, s.next_out, st));
+        else
+            HIP_TRY(launch_shift_plans(row_norm, 1, H, d.state_dim, nullptr, 0, 1, s.next_out, st));
+    }
+    if (k) {
+        // the k best of cost_local (with a set: of (cost_local, viol_local) in the feasibility-first order), ranked
+        // (entry 0 = the selection above), mirrored to mapped host memory with a completion word of their own, which
+        // the wait below takes instead of the selecting launch's: it follows that launch on the stream, so the result
+        // block is complete too. Then every candidate's next prior.
+        mpcd_best *el_dev = c->step_elite.as<mpcd_best>(), *el_hdev = reinterpret_cast<mpcd_best *>(hdev + hp.elites);
+        uint32_t *el_flag = reinterpret_cast<uint32_t *>(hdev + hp.elite_flag);
+        if (e) {
+            const TopkFeasMirror mir{el_hdev, reinterpret_cast<double *>(hdev + hp.eviol), el_flag, seq};
+            HIP_TRY(launch_topk_feasible(a->cost_local, e->viol_local, 1, B, k, e->tol, sa.global_offset, el_dev,
+                                         reinterpret_cast<double *>(el_dev + MPCD_MAX_ELITES), nullptr, st, &mir));
+        } else {
+            const TopkMirror mir{el_hdev, el_flag, seq};
+            HIP_TRY(launch_topk(a->cost_local, 1, B, k, sa.global_offset, el_dev, st, &mir));
+        }
+        if (s.next_out)
+            HIP_TRY(launch_elite_priors(sa.x_out, 1, B, H, d.state_dim, el_dev, k, sa.global_offset, 1, s.next_out, st));
+    }
+    const char *hblk = host + hp.out;
+    if (!one) {
+        HIP_TRY(hipMemcpyAsync(host + hp.out, c->step_out.p, hp.out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    } else if ((rc = wait_result(st, reinterpret_cast<volatile uint32_t *>(host + (k ? hp.elite_flag : hp.flag)), seq, s.fn))) {
+        return rc;
+    }
+    memcpy(best_host, hblk, sizeof(mpcd_best));
+    memcpy(u_best_host, hblk + sizeof(mpcd_best), sizeof(float) * (size_t)row);
+    int32_t code = 0;
+    memcpy(&code, hblk + sizeof(mpcd_best) + sizeof(float) * (size_t)row, sizeof code);
+    if (k && s.elites_host) memcpy(s.elites_host, host + hp.elites, sizeof(mpcd_best) * k);
+    c->step_flags = (code == 1 ? MPCD_STEP_CLIPPED : 0) | (code == 2 ? MPCD_STEP_NAN_SAMPLES : 0);
+    if (e) {
+        memcpy(e->viol_host, hblk + step_constr_viol_off(row), sizeof(double));
+        memcpy(e->n_feasible_host, hblk + step_constr_viol_off(row) + sizeof(double), sizeof(int64_t));
+        if (k && e->elite_viol_host) memcpy(e->elite_viol_host, host + hp.eviol, sizeof(double) * k);
+        if (*e->n_feasible_host == 0) c->step_flags |= MPCD_STEP_INFEASIBLE;
+    }
+    if (!std::isfinite(best_host->cost)) {
+        c->step_flags |= MPCD_STEP_NONFINITE_WINNER;
+        return fail(MPCD_ENONFINITE,
+                    e ? "%s: the selected candidate's cost is not finite (best %g, index %lld)%s"
+                      : "%s: no candidate has a finite cost (best %g, index %lld)%s",
+                    s.fn, best_host->cost, (long long)best_host->index, code == 2 ? "; NaN in the sampled trajectories" : "");
+    }
+    return MPCD_OK;
+}
+
+extern "C++" {  // templates cannot have C linkage
 // An MPCD_F16X2 net computes in the fp16 range: a step whose sampled trajectories came back with a NaN (an
 // activation beyond 65504 turns into one: hi = inf, lo = inf - inf) or with no finite cost is re-run with the net's
 // split-bf16 (MPCD_F32X3) programs and flagged MPCD_STEP_F32X3_RERUN. Single rank only: with a communicator every
@@ -1916,20 +2150,24 @@ static int mpc_step_rerun(mpcd_ctx *c, Step step)
     }
     return rc;
 }
-template <int MODE>
-static int mpc_step_rerun(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream,
-                          const WarmArgs *warm = nullptr, float *next_init_out = nullptr,
-                          const EliteArgs *elite = nullptr)
-{
-    return mpc_step_rerun(c, [&] { return mpc_step_impl<MODE>(c, a, best_host, u_best_host, stream, warm, next_init_out, elite); });
-}
-static int mpc_step_constr_impl(mpcd_ctx *c, const mpcd_step_args *a, const WarmArgs *warm, const mpcd_step_constr_args *e,
-                                mpcd_best *best_host, float *u_best_host, void *stream);
 }  // extern "C++"
+static int mpc_step_run(mpcd_ctx *c, const mpcd_step_args *a, const StepCall &s, mpcd_best *best_host, float *u_best_host,
+                        void *stream)
+{
+    return mpc_step_rerun(c, [&] { return mpc_step_impl(c, a, s, best_host, u_best_host, stream); });
+}
+
+// The re-run of an MPCD_F16X2 step reads the priors again: the next priors [out_rows][H][d] must not have replaced them
+static bool next_priors_alias(const mpcd_ctx *c, const mpcd_warm_start *warm, const float *next_out, int64_t out_rows)
+{
+    if (!next_out || warm->t_start <= 0 || !warm->x_init || !c->net_loaded) return false;
+    const size_t row = (size_t)c->desc.horizon * c->desc.state_dim;
+    return overlaps(next_out, (size_t)out_rows * row, warm->x_init, (size_t)warm->rows * row);
+}
 
 int mpcd_mpc_step(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream)
 {
-    return mpc_step_rerun<STEP_COLD>(c, a, best_host, u_best_host, stream);
+    return mpc_step_run(c, a, StepCall{"mpcd_mpc_step"}, best_host, u_best_host, stream);
 }
 
 int mpcd_mpc_step_warm(mpcd_ctx *c, const mpcd_step_args *a, const mpcd_warm_start *warm, float *next_init_out,
@@ -1944,7 +2182,7 @@ int mpcd_mpc_step_warm(mpcd_ctx *c, const mpcd_step_args *a, const mpcd_warm_sta
         return fail(MPCD_EINVAL, "mpcd_mpc_step_warm: next_init_out aliases warm->x_init");
     WarmArgs w;
     if (int rc = resolve_warm(c, &a->sample, 0, warm, w)) return rc;
-    return mpc_step_rerun<STEP_WARM>(c, a, best_host, u_best_host, stream, &w, next_init_out);
+    return mpc_step_run(c, a, StepCall{"mpcd_mpc_step", &w, 0, next_init_out}, best_host, u_best_host, stream);
 }
 
 int mpcd_mpc_step_elite(mpcd_ctx *c, const mpcd_step_args *a, const mpcd_warm_start *warm, int32_t k,
@@ -1961,17 +2199,11 @@ int mpcd_mpc_step_elite(mpcd_ctx *c, const mpcd_step_args *a, const mpcd_warm_st
     if (warm->t_start > 0 && warm->rows != 1 && warm->rows != B)
         return fail(MPCD_EINVAL, "mpcd_mpc_step_elite: one prior (rows == 1) or one per candidate (rows == batch %lld), not "
                                  "%lld rows", (long long)B, (long long)warm->rows);
-    // the re-run of an MPCD_F16X2 step reads the priors again: the next priors must not have replaced them
-    if (next_priors_out && warm->t_start > 0 && warm->x_init && c->net_loaded) {
-        const size_t row = (size_t)c->desc.horizon * c->desc.state_dim;
-        const float *in_end = warm->x_init + (size_t)warm->rows * row, *out_end = next_priors_out + (size_t)B * row;
-        if (next_priors_out < in_end && warm->x_init < out_end)
-            return fail(MPCD_EINVAL, "mpcd_mpc_step_elite: next_priors_out aliases warm->x_init");
-    }
+    if (next_priors_alias(c, warm, next_priors_out, B))
+        return fail(MPCD_EINVAL, "mpcd_mpc_step_elite: next_priors_out aliases warm->x_init");
     WarmArgs w;
     if (int rc = resolve_warm(c, &a->sample, 0, warm, w)) return rc;
-    const EliteArgs e{k, elites_host};
-    return mpc_step_rerun<STEP_ELITE>(c, a, best_host, u_best_host, stream, &w, next_priors_out, &e);
+    return mpc_step_run(c, a, StepCall{"mpcd_mpc_step", &w, k, next_priors_out, elites_host}, best_host, u_best_host, stream);
 }
 
 int mpcd_mpc_step_constr(mpcd_ctx *c, const mpcd_step_args *a, const mpcd_warm_start *warm,
@@ -1996,397 +2228,13 @@ int mpcd_mpc_step_constr(mpcd_ctx *c, const mpcd_step_args *a, const mpcd_warm_s
         if (warm->t_start > 0 && warm->rows != 1 && (k == 0 || warm->rows != B))
             return fail(MPCD_EINVAL, "%s: %lld prior rows: one prior (rows == 1)%s", fn, (long long)warm->rows,
                         k ? " or one per candidate (rows == batch)" : " for every candidate");
-        // the re-run of an MPCD_F16X2 step reads the priors again: the next priors must not have replaced them
-        if (e->next_priors_out && warm->t_start > 0 && warm->x_init && c->net_loaded) {
-            const size_t row = (size_t)c->desc.horizon * c->desc.state_dim;
-            const float *in_end = warm->x_init + (size_t)warm->rows * row;
-            const float *out_end = e->next_priors_out + (size_t)(k ? B : 1) * row;
-            if (e->next_priors_out < in_end && warm->x_init < out_end)
-                return fail(MPCD_EINVAL, "%s: next_priors_out aliases warm->x_init", fn);
-        }
+        if (next_priors_alias(c, warm, e->next_priors_out, k ? B : 1))
+            return fail(MPCD_EINVAL, "%s: next_priors_out aliases warm->x_init", fn);
         if (int rc = resolve_warm(c, &a->sample, 0, warm, w)) return rc;
     }
-    return mpc_step_rerun(c, [&] { return mpc_step_constr_impl(c, a, warm ? &w : nullptr, e, best_host, u_best_host, stream); });
+    return mpc_step_run(c, a, StepCall{fn, warm ? &w : nullptr, k, e->next_priors_out, e->elites_host, e}, best_host,
+                        u_best_host, stream);
 }
-
-extern "C++" {
-template <int MODE>
-static int mpc_step_impl(mpcd_ctx *c, const mpcd_step_args *a, mpcd_best *best_host, float *u_best_host, void *stream,
-                         const WarmArgs *warm, float *next_init_out, const EliteArgs *elite)
-{
-    constexpr bool WARM = MODE == STEP_WARM, ELITE = MODE == STEP_ELITE;
-    if (!c || !a || !a->sys || !a->x0 || !a->act_min || !a->act_max || !a->cost_local || !best_host || !u_best_host)
-        return fail(MPCD_EINVAL, "null argument");
-    if (!c->net_loaded) return fail(MPCD_ESTATE, "no net loaded");
-    const mpcd_net_desc &d = c->desc;
-    const mpcd_system_desc &sys = *a->sys;
-    const int64_t B = a->sample.batch;
-    const int H = d.horizon, row = H * d.state_dim;
-    if (B < 1 || !a->sample.x_out) return fail(MPCD_EINVAL, "sample.batch / sample.x_out");
-    if (sys.n_u != d.state_dim) return fail(MPCD_EINVAL, "system n_u %d != net state_dim %d", sys.n_u, d.state_dim);
-    int rc = check_system(&sys, H);
-    if (rc) return rc;
-    if (d.context_dim > 0 && (!a->ctx_min || !a->ctx_max)) return fail(MPCD_EINVAL, "ctx_min / ctx_max");
-    if (d.context_dim > 0 && d.context_dim != sys.n_x) return fail(MPCD_EINVAL, "context_dim %d != n_x %d", d.context_dim, sys.n_x);
-    if (c->comm && !a->costs_all) return fail(MPCD_EINVAL, "costs_all is required with a communicator");
-    if (a->clip_rule < MPCD_CLIP_CHAIN || a->clip_rule > MPCD_CLIP_NONE) return fail(MPCD_EINVAL, "clip_rule %d", a->clip_rule);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    DEVICE_GUARD(c->device);
-
-    // host staging (pinned): [context row | result block]
-    // result block: {best, winner row [row] fp32, clip code int32} - one D2H copy
-    const size_t out_bytes = sizeof(mpcd_best) + sizeof(float) * (size_t)row + sizeof(int32_t);
-    const size_t flag_off = 64 + ((out_bytes + 63) & ~(size_t)63);  // the completion word, own 64-byte line
-    // STEP_ELITE: [the k elites, MPCD_MAX_ELITES entries | the top-k launch's completion word] follow
-    const size_t elite_off = flag_off + 64, elite_flag_off = elite_off + sizeof(mpcd_best) * MPCD_MAX_ELITES;
-    const size_t host_bytes = ELITE ? elite_flag_off + 64 : flag_off + 64;
-    if (c->step_host_bytes < host_bytes) {
-        if (c->step_host) (void)hipHostFree(c->step_host);
-        c->step_host = nullptr;
-        c->step_host_dev = nullptr;
-        c->step_host_bytes = 0;
-        // coherent (fine-grained) mapped memory: the selecting workgroup's system-scope stores of the result block
-        // and the completion word reach the host without depending on HIP_HOST_COHERENT's default
-        HIP_TRY(hipHostMalloc(&c->step_host, host_bytes, hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_TRY(hipHostGetDevicePointer(&c->step_host_dev, c->step_host, 0));
-        memset(c->step_host, 0, host_bytes);
-        c->step_seq = 0;
-        c->step_host_bytes = host_bytes;
-    }
-    if ((rc = c->step_ctx.ensure(64)) || (rc = c->step_out.ensure(out_bytes))) return rc;
-    const int64_t n_part = (B + kRolloutBlock - 1) / kRolloutBlock;
-    if ((rc = c->step_part.ensure(16 * (size_t)n_part + sizeof(float) * (size_t)row))) return rc;
-
-    // normalize_condition (A12), fp64 then the net's .float()
-    mpcd_sample_args sa = a->sample;
-    CtxRowArg ctx_row{};
-    const bool by_value = d.context_dim > 0 && d.context_dim <= kCtxRowMax;
-    if (d.context_dim > 0) {
-        float *ch = by_value ? ctx_row.v : static_cast<float *>(c->step_host);
-        for (int i = 0; i < d.context_dim; ++i) {
-            const double den = (double)(a->ctx_max[i] - a->ctx_min[i]);
-            ch[i] = (float)(2.0 * ((a->x0[i] - (double)a->ctx_min[i]) / den) - 1.0);
-        }
-        if (!by_value)
-            HIP_TRY(hipMemcpyAsync(c->step_ctx.p, ch, sizeof(float) * d.context_dim, hipMemcpyHostToDevice, st));
-        sa.context = by_value ? nullptr : c->step_ctx.as<float>();
-        sa.context_shared = 1;
-    } else {
-        sa.context = nullptr;
-    }
-    sa.chain_absmax = nullptr;
-    if (a->clip_rule == MPCD_CLIP_CHAIN) {
-        if ((rc = c->step_amax.ensure(sizeof(float) * (size_t)B))) return rc;
-        sa.chain_absmax = c->step_amax.as<float>();
-    }
-    if constexpr (ELITE) {
-        if (next_init_out) {  // the elite-prior launch reads x_out and writes next_init_out
-            const float *x_end = sa.x_out + (size_t)B * row, *o_end = next_init_out + (size_t)B * row;
-            if (next_init_out < x_end && sa.x_out < o_end)
-                return fail(MPCD_EINVAL, "mpcd_mpc_step_elite: next_priors_out overlaps sample.x_out");
-        }
-        if ((rc = c->step_elite.ensure(sizeof(mpcd_best) * MPCD_MAX_ELITES))) return rc;
-    }
-    if constexpr (WARM || ELITE) {
-        if ((rc = sample_impl(c, &sa, stream, by_value ? &ctx_row : nullptr, 0, warm))) return rc;
-    } else {
-        if ((rc = sample_impl(c, &sa, stream, by_value ? &ctx_row : nullptr))) return rc;
-    }
-
-    // LimitsNormalizer's global clip flag over the chain (the reference's unnormalize_states of run_CFG's
-    // whole chain), over the final samples, or proven 0; max-reduced over ranks (see mpcd_clip_flag)
-    int *flags = c->flag.as<int>();
-    const int *flag = flags + 1;  // flag[1] is never written: a constant 0
-    // single rank, a small clip input: the selecting rollout launch computes the clip code itself (each
-    // workgroup over the whole input, <= kFuseClipMax floats) - one launch fewer per control step
-    const float *clip_src = a->clip_rule == MPCD_CLIP_CHAIN ? sa.chain_absmax : sa.x_out;
-    const int64_t clip_n = a->clip_rule == MPCD_CLIP_CHAIN ? B : B * row;
-    const bool fuse_clip = !c->comm && a->clip_rule != MPCD_CLIP_NONE && clip_n <= kFuseClipMax;
-    if (a->clip_rule != MPCD_CLIP_NONE && !fuse_clip) {
-        if (a->clip_rule == MPCD_CLIP_CHAIN)
-            HIP_TRY(launch_clip_flag(sa.chain_absmax, B, flags, c->sync_ws(), st));
-        else
-            HIP_TRY(launch_clip_flag(sa.x_out, B * row, flags, c->sync_ws(), st));
-        if ((rc = comm_reduce(c, flags, 1, COMM_MAX_I32, st))) return rc;
-        flag = flags;
-    }
-    mpcd_best *best_dev = c->step_out.as<mpcd_best>();
-    float *u_dev = reinterpret_cast<float *>(best_dev + 1);
-    double *part_cost = c->step_part.as<double>();
-    int64_t *part_idx = reinterpret_cast<int64_t *>(part_cost + n_part);
-    int32_t *code_dev = reinterpret_cast<int32_t *>(u_dev + row);
-    void *host_out = static_cast<char *>(c->step_host) + 64;
-    volatile uint32_t *host_flag =
-        reinterpret_cast<volatile uint32_t *>(static_cast<char *>(c->step_host) + (ELITE ? elite_flag_off : flag_off));
-    uint32_t seq = 0;
-    if (!c->comm) {  // rollout + cost + argmin + the winner's unnormalised row + the clip code in one launch
-        seq = ++c->step_seq;
-        if (seq == 0) seq = ++c->step_seq;
-        char *hdev = static_cast<char *>(c->step_host_dev);
-        RolloutSelect sel{best_dev, u_dev,    part_cost, part_idx, c->sync_ws() + 8, n_part, sa.global_offset, code_dev,
-                          fuse_clip ? clip_src : nullptr, fuse_clip ? clip_n : 0, hdev + 64,
-                          reinterpret_cast<uint32_t *>(hdev + flag_off), seq};
-        HIP_TRY(launch_rollout_cost(sys, a->x0, nullptr, B, sa.x_out, a->act_min, a->act_max, flag, B, H,
-                                    a->cost_local, st, &sel));
-    } else {
-        HIP_TRY(launch_rollout_cost(sys, a->x0, nullptr, B, sa.x_out, a->act_min, a->act_max, flag, B, H,
-                                    a->cost_local, st));
-        float *row_norm = reinterpret_cast<float *>(part_idx + n_part);
-        if ((rc = comm_gather(c, a->cost_local, a->costs_all, (size_t)B, 8, st))) return rc;
-        HIP_TRY(launch_argmin(a->costs_all, B * c->nranks, 0, best_dev, st));
-        HIP_TRY(launch_winner_row(best_dev, (int64_t)c->rank * B, B, sa.x_out, row, row_norm, st));
-        if ((rc = comm_reduce(c, row_norm, (size_t)row, COMM_SUM_F32, st))) return rc;
-        HIP_TRY(launch_unnormalize(row_norm, row, d.state_dim, flag, a->act_min, a->act_max, u_dev, st));
-        HIP_TRY(hipMemcpyAsync(code_dev, flag, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    }
-    if constexpr (WARM) {
-        // the next step's prior: the winner's normalised plan moved one horizon point ahead. One rank: the row of
-        // x_out that the device-resident best.index names; ranks: the all-reduced winner row (the same on each)
-        if (next_init_out) {
-            if (!c->comm)
-                HIP_TRY(launch_shift_plans(sa.x_out, B, H, d.state_dim, &best_dev->index, sa.global_offset, 1,
-                                           next_init_out, st));
-            else
-                HIP_TRY(launch_shift_plans(reinterpret_cast<float *>(part_idx + n_part), 1, H, d.state_dim, nullptr, 0, 1,
-                                           next_init_out, st));
-        }
-    }
-    if constexpr (ELITE) {
-        // the k best of cost_local, ranked (entry 0 = the selection above), mirrored to mapped host memory with a
-        // completion word of their own, which the wait below takes instead of the rollout launch's: it follows that
-        // launch on the stream, so the result block is complete too. Then every candidate's next prior.
-        char *hdev = static_cast<char *>(c->step_host_dev);
-        const TopkMirror mir{reinterpret_cast<mpcd_best *>(hdev + elite_off),
-                             reinterpret_cast<uint32_t *>(hdev + elite_flag_off), seq};
-        HIP_TRY(launch_topk(a->cost_local, 1, B, elite->k, sa.global_offset, c->step_elite.as<mpcd_best>(), st, &mir));
-        if (next_init_out)
-            HIP_TRY(launch_elite_priors(sa.x_out, 1, B, H, d.state_dim, c->step_elite.as<mpcd_best>(), elite->k,
-                                        sa.global_offset, 1, next_init_out, st));
-    }
-    if (c->comm) {
-        HIP_TRY(hipMemcpyAsync(host_out, c->step_out.p, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    } else {
-        // the selecting workgroup wrote the block to mapped host memory and then the completion word: spin on it
-        // (no copy launch, no stream synchronisation wake-up); the stream is queried now and then so that a failed
-        // launch cannot leave this loop waiting
-        for (uint32_t n = 1; *host_flag != seq; ++n) {
-            if ((n & 4095) == 0) {
-                const hipError_t q = hipStreamQuery(st);
-                if (q == hipSuccess && *host_flag != seq)
-                    return fail(MPCD_EHIP, "mpcd_mpc_step: the stream finished without the result block");
-                if (q != hipSuccess && q != hipErrorNotReady) HIP_TRY(q);
-            }
-#if defined(__x86_64__) || defined(__i386__)
-            __builtin_ia32_pause();  // spin-wait hint (host CPU)
-#else
-            std::this_thread::yield();
-#endif
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-    }
-    memcpy(best_host, host_out, sizeof(mpcd_best));
-    memcpy(u_best_host, static_cast<char *>(host_out) + sizeof(mpcd_best), sizeof(float) * (size_t)row);
-    int32_t code = 0;
-    memcpy(&code, static_cast<char *>(host_out) + sizeof(mpcd_best) + sizeof(float) * (size_t)row, sizeof code);
-    if constexpr (ELITE) {
-        if (elite->elites_host)
-            memcpy(elite->elites_host, static_cast<char *>(c->step_host) + elite_off, sizeof(mpcd_best) * elite->k);
-    }
-    c->step_flags = (code == 1 ? MPCD_STEP_CLIPPED : 0) | (code == 2 ? MPCD_STEP_NAN_SAMPLES : 0);
-    if (!std::isfinite(best_host->cost)) {
-        c->step_flags |= MPCD_STEP_NONFINITE_WINNER;
-        return fail(MPCD_ENONFINITE, "mpcd_mpc_step: no candidate has a finite cost (best %g, index %lld)%s",
-                    best_host->cost, (long long)best_host->index,
-                    code == 2 ? "; NaN in the sampled trajectories" : "");
-    }
-    return MPCD_OK;
-}
-
-// mpcd_mpc_step_constr's one attempt: mpc_step_impl's sequence with the constraint set. A function of its own, so the
-// three instantiations above compile the code they had. The mapped host block is the one mpc_step_impl allocates; this
-// call's parts lie behind everything that function uses (its result block, the elites and both completion words), so
-// neither call ever finds the other's data where it waits for a completion word: [.. mpc_step_impl's parts | result
-// block {best, row, code, V, n_feasible} | completion word | k elites | their V | the ranking launch's completion word].
-static int mpc_step_constr_impl(mpcd_ctx *c, const mpcd_step_args *a, const WarmArgs *warm, const mpcd_step_constr_args *e,
-                                mpcd_best *best_host, float *u_best_host, void *stream)
-{
-    const char *fn = "mpcd_mpc_step_constr";
-    if (!c || !a || !a->sys || !a->x0 || !a->act_min || !a->act_max || !a->cost_local || !best_host || !u_best_host)
-        return fail(MPCD_EINVAL, "null argument");
-    if (!c->net_loaded) return fail(MPCD_ESTATE, "no net loaded");
-    const mpcd_net_desc &d = c->desc;
-    const mpcd_system_desc &sys = *a->sys;
-    const int64_t B = a->sample.batch;
-    const int H = d.horizon, row = H * d.state_dim, k = e->k;
-    if (B < 1 || !a->sample.x_out) return fail(MPCD_EINVAL, "sample.batch / sample.x_out");
-    if (sys.n_u != d.state_dim) return fail(MPCD_EINVAL, "system n_u %d != net state_dim %d", sys.n_u, d.state_dim);
-    int rc = check_system(&sys, H);
-    if (rc) return rc;
-    if ((rc = check_constraints(fn, e->con, sys.n_x, sys.n_u))) return rc;
-    if (d.context_dim > 0 && (!a->ctx_min || !a->ctx_max)) return fail(MPCD_EINVAL, "ctx_min / ctx_max");
-    if (d.context_dim > 0 && d.context_dim != sys.n_x) return fail(MPCD_EINVAL, "context_dim %d != n_x %d", d.context_dim, sys.n_x);
-    if (c->comm && !a->costs_all) return fail(MPCD_EINVAL, "costs_all is required with a communicator");
-    if (a->clip_rule < MPCD_CLIP_CHAIN || a->clip_rule > MPCD_CLIP_NONE) return fail(MPCD_EINVAL, "clip_rule %d", a->clip_rule);
-    float *next_out = e->next_priors_out;
-    if (next_out) {  // the prior launches read x_out and write next_priors_out
-        const float *x_end = a->sample.x_out + (size_t)B * row, *o_end = next_out + (size_t)(k ? B : 1) * row;
-        if (next_out < x_end && a->sample.x_out < o_end) return fail(MPCD_EINVAL, "%s: next_priors_out overlaps sample.x_out", fn);
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    DEVICE_GUARD(c->device);
-
-    const size_t base_out = sizeof(mpcd_best) + sizeof(float) * (size_t)row + sizeof(int32_t);  // mpc_step_impl's layout
-    const size_t base_end = 64 + ((base_out + 63) & ~(size_t)63) + 64 + sizeof(mpcd_best) * MPCD_MAX_ELITES + 64;
-    const size_t out_bytes = step_constr_out_bytes(row), viol_off = step_constr_viol_off(row);
-    const size_t blk_off = base_end, flag_off = blk_off + ((out_bytes + 63) & ~(size_t)63);
-    const size_t elite_off = flag_off + 64, eviol_off = elite_off + sizeof(mpcd_best) * MPCD_MAX_ELITES;
-    const size_t elite_flag_off = eviol_off + sizeof(double) * MPCD_MAX_ELITES, host_bytes = elite_flag_off + 64;
-    if (c->step_host_bytes < host_bytes) {
-        if (c->step_host) (void)hipHostFree(c->step_host);
-        c->step_host = nullptr;
-        c->step_host_dev = nullptr;
-        c->step_host_bytes = 0;
-        HIP_TRY(hipHostMalloc(&c->step_host, host_bytes, hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_TRY(hipHostGetDevicePointer(&c->step_host_dev, c->step_host, 0));
-        memset(c->step_host, 0, host_bytes);
-        c->step_seq = 0;
-        c->step_host_bytes = host_bytes;
-    }
-    if ((rc = c->step_ctx.ensure(64)) || (rc = c->step_out.ensure(out_bytes))) return rc;
-    const int64_t n_part = (B + kRolloutBlock - 1) / kRolloutBlock;
-    if ((rc = c->step_part.ensure(32 * (size_t)n_part + sizeof(float) * (size_t)row))) return rc;
-    if (k && (rc = c->step_elite.ensure((sizeof(mpcd_best) + sizeof(double)) * MPCD_MAX_ELITES))) return rc;
-
-    // normalize_condition (A12), fp64 then the net's .float()
-    mpcd_sample_args sa = a->sample;
-    CtxRowArg ctx_row{};
-    const bool by_value = d.context_dim > 0 && d.context_dim <= kCtxRowMax;
-    if (d.context_dim > 0) {
-        float *ch = by_value ? ctx_row.v : static_cast<float *>(c->step_host);
-        for (int i = 0; i < d.context_dim; ++i) {
-            const double den = (double)(a->ctx_max[i] - a->ctx_min[i]);
-            ch[i] = (float)(2.0 * ((a->x0[i] - (double)a->ctx_min[i]) / den) - 1.0);
-        }
-        if (!by_value)
-            HIP_TRY(hipMemcpyAsync(c->step_ctx.p, ch, sizeof(float) * d.context_dim, hipMemcpyHostToDevice, st));
-        sa.context = by_value ? nullptr : c->step_ctx.as<float>();
-        sa.context_shared = 1;
-    } else {
-        sa.context = nullptr;
-    }
-    sa.chain_absmax = nullptr;
-    if (a->clip_rule == MPCD_CLIP_CHAIN) {
-        if ((rc = c->step_amax.ensure(sizeof(float) * (size_t)B))) return rc;
-        sa.chain_absmax = c->step_amax.as<float>();
-    }
-    if (warm) {
-        if ((rc = sample_impl(c, &sa, stream, by_value ? &ctx_row : nullptr, 0, warm))) return rc;
-    } else {
-        if ((rc = sample_impl(c, &sa, stream, by_value ? &ctx_row : nullptr))) return rc;
-    }
-
-    // the global clip flag, as in mpc_step_impl
-    int *flags = c->flag.as<int>();
-    const int *flag = flags + 1;  // flag[1] is never written: a constant 0
-    const float *clip_src = a->clip_rule == MPCD_CLIP_CHAIN ? sa.chain_absmax : sa.x_out;
-    const int64_t clip_n = a->clip_rule == MPCD_CLIP_CHAIN ? B : B * row;
-    const bool fuse_clip = !c->comm && a->clip_rule != MPCD_CLIP_NONE && clip_n <= kFuseClipMax;
-    if (a->clip_rule != MPCD_CLIP_NONE && !fuse_clip) {
-        HIP_TRY(launch_clip_flag(clip_src, clip_n, flags, c->sync_ws(), st));
-        if ((rc = comm_reduce(c, flags, 1, COMM_MAX_I32, st))) return rc;
-        flag = flags;
-    }
-    char *blk_dev = c->step_out.as<char>();
-    mpcd_best *best_dev = reinterpret_cast<mpcd_best *>(blk_dev);
-    float *u_dev = reinterpret_cast<float *>(best_dev + 1);
-    int32_t *code_dev = reinterpret_cast<int32_t *>(u_dev + row);
-    double *viol_dev = reinterpret_cast<double *>(blk_dev + viol_off);
-    int64_t *nfeas_dev = reinterpret_cast<int64_t *>(viol_dev + 1);
-    double *part = c->step_part.as<double>();
-    float *row_norm = reinterpret_cast<float *>(part + 4 * n_part);
-    char *hblk = static_cast<char *>(c->step_host) + blk_off;
-    volatile uint32_t *host_flag =
-        reinterpret_cast<volatile uint32_t *>(static_cast<char *>(c->step_host) + (k ? elite_flag_off : flag_off));
-    uint32_t seq = 0;
-    if (!c->comm) {  // rollout + cost + V + the feasibility-first selection + the winner's row in one launch
-        seq = ++c->step_seq;
-        if (seq == 0) seq = ++c->step_seq;
-        char *hdev = static_cast<char *>(c->step_host_dev);
-        const RolloutConstrSelect sel{blk_dev, part, n_part, c->sync_ws() + 8, sa.global_offset,
-                                      fuse_clip ? clip_src : nullptr, fuse_clip ? clip_n : 0, hdev + blk_off,
-                                      reinterpret_cast<uint32_t *>(hdev + flag_off), seq};
-        HIP_TRY(launch_rollout_constr_select(sys, a->x0, sa.x_out, a->act_min, a->act_max, flag, B, H, *e->con, e->tol,
-                                             e->u_prev_host, a->cost_local, e->viol_local, st, &sel));
-    } else {
-        HIP_TRY(launch_rollout_constr_select(sys, a->x0, sa.x_out, a->act_min, a->act_max, flag, B, H, *e->con, e->tol,
-                                             e->u_prev_host, a->cost_local, e->viol_local, st, nullptr));
-        if ((rc = comm_gather(c, a->cost_local, a->costs_all, (size_t)B, 8, st))) return rc;
-        if ((rc = comm_gather(c, e->viol_local, e->viols_all, (size_t)B, 8, st))) return rc;
-        HIP_TRY(launch_topk_feasible(a->costs_all, e->viols_all, 1, B * c->nranks, 1, e->tol, 0, best_dev, viol_dev,
-                                     nfeas_dev, st));
-        HIP_TRY(launch_winner_row(best_dev, (int64_t)c->rank * B, B, sa.x_out, row, row_norm, st));
-        if ((rc = comm_reduce(c, row_norm, (size_t)row, COMM_SUM_F32, st))) return rc;
-        HIP_TRY(launch_unnormalize(row_norm, row, d.state_dim, flag, a->act_min, a->act_max, u_dev, st));
-        HIP_TRY(hipMemcpyAsync(code_dev, flag, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    }
-    if (k == 0 && next_out) {  // mpc_step_impl's STEP_WARM: the winner's normalised plan moved one horizon point ahead
-        if (!c->comm)
-            HIP_TRY(launch_shift_plans(sa.x_out, B, H, d.state_dim, &best_dev->index, sa.global_offset, 1, next_out, st));
-        else
-            HIP_TRY(launch_shift_plans(row_norm, 1, H, d.state_dim, nullptr, 0, 1, next_out, st));
-    }
-    if (k) {
-        // the k first of (cost_local, viol_local) in the feasibility-first order (entry 0 = the selection above), mirrored
-        // to mapped host memory with a completion word of their own, which the wait below takes: it follows the
-        // selecting launch on the stream, so the result block is complete too. Then every candidate's next prior.
-        char *hdev = static_cast<char *>(c->step_host_dev);
-        mpcd_best *el_dev = c->step_elite.as<mpcd_best>();
-        const TopkFeasMirror mir{reinterpret_cast<mpcd_best *>(hdev + elite_off), reinterpret_cast<double *>(hdev + eviol_off),
-                                 reinterpret_cast<uint32_t *>(hdev + elite_flag_off), seq};
-        HIP_TRY(launch_topk_feasible(a->cost_local, e->viol_local, 1, B, k, e->tol, sa.global_offset, el_dev,
-                                     reinterpret_cast<double *>(el_dev + MPCD_MAX_ELITES), nullptr, st, &mir));
-        if (next_out)
-            HIP_TRY(launch_elite_priors(sa.x_out, 1, B, H, d.state_dim, el_dev, k, sa.global_offset, 1, next_out, st));
-    }
-    if (c->comm) {
-        HIP_TRY(hipMemcpyAsync(hblk, c->step_out.p, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    } else {
-        // spin on the completion word, as mpc_step_impl does
-        for (uint32_t n = 1; *host_flag != seq; ++n) {
-            if ((n & 4095) == 0) {
-                const hipError_t q = hipStreamQuery(st);
-                if (q == hipSuccess && *host_flag != seq)
-                    return fail(MPCD_EHIP, "%s: the stream finished without the result block", fn);
-                if (q != hipSuccess && q != hipErrorNotReady) HIP_TRY(q);
-            }
-#if defined(__x86_64__) || defined(__i386__)
-            __builtin_ia32_pause();  // spin-wait hint (host CPU)
-#else
-            std::this_thread::yield();
-#endif
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-    }
-    memcpy(best_host, hblk, sizeof(mpcd_best));
-    memcpy(u_best_host, hblk + sizeof(mpcd_best), sizeof(float) * (size_t)row);
-    int32_t code = 0;
-    memcpy(&code, hblk + sizeof(mpcd_best) + sizeof(float) * (size_t)row, sizeof code);
-    memcpy(e->viol_host, hblk + viol_off, sizeof(double));
-    memcpy(e->n_feasible_host, hblk + viol_off + sizeof(double), sizeof(int64_t));
-    if (k && e->elites_host) memcpy(e->elites_host, static_cast<char *>(c->step_host) + elite_off, sizeof(mpcd_best) * k);
-    if (k && e->elite_viol_host) memcpy(e->elite_viol_host, static_cast<char *>(c->step_host) + eviol_off, sizeof(double) * k);
-    c->step_flags = (code == 1 ? MPCD_STEP_CLIPPED : 0) | (code == 2 ? MPCD_STEP_NAN_SAMPLES : 0) |
-                    (*e->n_feasible_host == 0 ? MPCD_STEP_INFEASIBLE : 0);
-    if (!std::isfinite(best_host->cost)) {
-        c->step_flags |= MPCD_STEP_NONFINITE_WINNER;
-        return fail(MPCD_ENONFINITE, "%s: the selected candidate's cost is not finite (best %g, index %lld)%s", fn,
-                    best_host->cost, (long long)best_host->index, code == 2 ? "; NaN in the sampled trajectories" : "");
-    }
-    return MPCD_OK;
-}
-}  // extern "C++"
 
 
 // ---- native training step: MLP noise-net, fp32, csrc/train.hip

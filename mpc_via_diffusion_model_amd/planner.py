@@ -1439,13 +1439,14 @@ class DiffusionMPC:
             raise ValueError("u_prev serves the rate bounds of constraints=")
         if state_box is not None:
             if native:
-                raise ValueError("state_box is not available with native=True: folding the constraint into the fused step "
-                                 "(mpcd_mpc_step) is the follow-up; leave native unset or False")
+                raise ValueError("state_box is not available with native=True: the fused step (mpcd_mpc_step) takes no box; "
+                                 "its follow-up mpc_step_constr does (Constraints(state_box=...)), or leave native unset")
             if warm_start is not None or prior is not None or elites is not None:
-                raise ValueError("state_box with warm_start / prior / elites needs the native step, which takes no box "
-                                 "yet (the follow-up); closed_loop(native=False) combines them")
+                raise ValueError("state_box with warm_start / prior / elites needs the native step, which takes no box: "
+                                 "use its follow-up mpc_step_constr, or closed_loop(native=False)")
             if comm is not None or size > 1:
-                raise ValueError("state_box is single-rank: the multi-rank feasibility-first selection is the follow-up")
+                raise ValueError("state_box is single-rank here: the multi-rank feasibility-first selection is the "
+                                 "follow-up mpc_step_constr's")
             box, tol, native = self._state_box(state_box, system.n_x), self._viol_tol(viol_tol), False
         if native is None:
             native = comm is not None or size == 1
@@ -1536,30 +1537,8 @@ class DiffusionMPC:
         if d != system.n_u:
             raise ValueError(f"system {system.name} has {system.n_u} inputs, samples have {d}")
         sampler = self._sampler_id(sample_fn)
-        warm = nxt = None
-        if warm_start is not None or prior is not None:
-            K = int(warm_start) if warm_start is not None else 0
-            if K < 1 or K > self.n_steps or sampler != N.MPCD_DDPM_CFG:
-                raise ValueError(f"warm_start={warm_start} needs 1 <= K <= {self.n_steps} and the CFG-DDPM sampler")
-            if elites is not None:
-                elites = self._check_elites(elites, B)
-            if prior is None:
-                prior = getattr(self, "_prior", None)
-                if elites is not None and prior is not None and prior.shape[0] not in (1, B):
-                    raise ValueError(f"the stored priors have {prior.shape[0]} rows, neither 1 nor n_samples={B}: call "
-                                     "reset_warm_start() after changing n_samples")
-            warm, prior = self._warm(prior, K if prior is not None else 0, B)  # no prior yet: a cold step that fills it
-            if elites is None and prior is not None and prior.shape[0] != 1:
-                raise ValueError(f"prior must be one plan [{H}, {d}], got {tuple(prior.shape)}")
-            rows = 1 if elites is None else B  # the next priors: the winner's plan, or one per candidate
-            nxt = getattr(self, "_prior_spare", None)
-            if nxt is None or nxt.shape[0] != rows or (prior is not None and nxt.data_ptr() == prior.data_ptr()):
-                nxt = torch.empty((rows, H, d), dtype=torch.float32, device=self.device)
-        if noise is not None:
-            steps = self.n_denoise_steps(sample_fn, n_wo_noise, ddim_steps, warm.t_start or None if warm else None)
-            noise = noise.to(self.device, torch.float32).contiguous()
-            if tuple(noise.shape) != (steps + 1, B, H, d):
-                raise ValueError(f"noise must be [{steps + 1}, {B}, {H}, {d}], got {tuple(noise.shape)}")
+        warm, prior, nxt, elites = self._step_warm(sampler, B, warm_start, prior, elites)
+        noise = self._step_noise(noise, sample_fn, n_wo_noise, ddim_steps, warm, B)
         u_norm = torch.empty((B, H, d), dtype=torch.float32, device=self.device)
         cost = torch.empty(B, dtype=torch.float64, device=self.device)
         viol = torch.empty(B, dtype=torch.float64, device=self.device)
@@ -1567,15 +1546,7 @@ class DiffusionMPC:
         viols = torch.empty(size * B, dtype=torch.float64, device=self.device) if size > 1 else viol
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
         desc = self._system_desc(system)
-        a = N.StepArgs()
-        a.sys = ctypes.pointer(desc)
-        a.ctx_min, a.ctx_max = self.ctx_min.ctypes.data, self.ctx_max.ctypes.data
-        a.act_min, a.act_max = self.act_min.ctypes.data, self.act_max.ctypes.data
-        a.sample = self._args(sampler, B, _STEP_CONTEXT, w, n_wo_noise, ddim_steps, clamp_x0, seed, rank * B, noise, u_norm,
-                              None)
-        a.clip_rule = _CLIP_RULES[clip_rule]
-        if clip_rule == "final" and sampler == N.MPCD_DDPM_CFG and self.ddpm_final_in_range:
-            a.clip_rule = N.MPCD_CLIP_NONE
+        a = self._step_args(desc, sampler, B, w, n_wo_noise, ddim_steps, clamp_x0, seed, rank * B, noise, u_norm, clip_rule)
         a.x0 = x0.__array_interface__["data"][0]
         a.cost_local, a.costs_all = cost.data_ptr(), costs.data_ptr()
         e = N.StepConstrArgs()
@@ -1596,8 +1567,7 @@ class DiffusionMPC:
         N.check(self._lib.mpcd_mpc_step_constr(self._ctx, ctypes.byref(a), ctypes.byref(warm) if warm is not None else None,
                                                ctypes.byref(e), ctypes.byref(best), u_best.__array_interface__["data"][0],
                                                self._stream()), "mpcd_mpc_step_constr")
-        if nxt is not None:  # the refreshed prior becomes the next call's; this call's buffer is the next one's output
-            self._prior, self._prior_spare = nxt, getattr(self, "_prior", None)
+        self._swap_prior(nxt)
         N.check(self._lib.mpcd_last_step_flags(self._ctx, ctypes.byref(fl)), "mpcd_last_step_flags")
         return MPCResult(u0=u_best[0].copy(), u_best=u_best, best_cost=best.cost, best_index=best.index, costs=costs,
                          u_norm=u_norm, flags=fl.value, elite_index=None if el is None else el["index"].copy(),
@@ -1615,9 +1585,66 @@ class DiffusionMPC:
         p = getattr(self, "_prior", None)
         return None if p is None else p[0]
 
+    def _step_warm(self, sampler, B, warm_start, prior, elites):
+        """The warm start of a native single-state step (mpc_step, mpc_step_constr): (warm, prior, nxt, elites) - the
+        WarmStart block (None without warm_start / prior: the cold call), the prior it reads, the buffer the call
+        writes the next priors into and the checked elite count."""
+        if warm_start is None and prior is None:
+            return None, None, None, elites
+        H, d = self.spec.horizon, self.spec.state_dim
+        K = int(warm_start) if warm_start is not None else 0
+        if K < 1 or K > self.n_steps or sampler != N.MPCD_DDPM_CFG:
+            raise ValueError(f"warm_start={warm_start} needs 1 <= K <= {self.n_steps} and the CFG-DDPM sampler")
+        if elites is not None:
+            elites = self._check_elites(elites, B)
+        if prior is None:
+            prior = getattr(self, "_prior", None)
+            if elites is not None and prior is not None and prior.shape[0] not in (1, B):
+                raise ValueError(f"the stored priors have {prior.shape[0]} rows, neither 1 nor n_samples={B}: call "
+                                 "reset_warm_start() after changing n_samples")
+        # no prior yet: a cold step (t_start 0) that fills it
+        warm, prior = self._warm(prior, K if prior is not None else 0, B)
+        if elites is None and prior is not None and prior.shape[0] != 1:
+            raise ValueError(f"prior must be one plan [{H}, {d}], got {tuple(prior.shape)}")
+        rows = 1 if elites is None else B  # the next priors: the winner's plan, or one per candidate
+        nxt = getattr(self, "_prior_spare", None)
+        if nxt is None or nxt.shape[0] != rows or (prior is not None and nxt.data_ptr() == prior.data_ptr()):
+            nxt = torch.empty((rows, H, d), dtype=torch.float32, device=self.device)
+        return warm, prior, nxt, elites
+
+    def _step_noise(self, noise, sample_fn, n_wo_noise, ddim_steps, warm, B):
+        """Injected noise on the device, one slice per denoise step of this call (fewer after a warm start) and one more."""
+        if noise is None:
+            return None
+        H, d = self.spec.horizon, self.spec.state_dim
+        steps = self.n_denoise_steps(sample_fn, n_wo_noise, ddim_steps, warm.t_start or None if warm else None)
+        noise = noise.to(self.device, torch.float32).contiguous()
+        if tuple(noise.shape) != (steps + 1, B, H, d):
+            raise ValueError(f"noise must be [{steps + 1}, {B}, {H}, {d}], got {tuple(noise.shape)}")
+        return noise
+
+    def _step_args(self, desc, sampler, B, w, n_wo_noise, ddim_steps, clamp_x0, seed, offset, noise, u_norm, clip_rule):
+        """The StepArgs block of a native single-state step, all but x0 and the cost pointers."""
+        a = N.StepArgs()
+        a.sys = ctypes.pointer(desc)
+        a.ctx_min, a.ctx_max = self.ctx_min.ctypes.data, self.ctx_max.ctypes.data
+        a.act_min, a.act_max = self.act_min.ctypes.data, self.act_max.ctypes.data
+        a.sample = self._args(sampler, B, _STEP_CONTEXT, w, n_wo_noise, ddim_steps, clamp_x0, seed, offset, noise, u_norm,
+                              None)
+        a.clip_rule = _CLIP_RULES[clip_rule]
+        if clip_rule == "final" and sampler == N.MPCD_DDPM_CFG and self.ddpm_final_in_range:
+            a.clip_rule = N.MPCD_CLIP_NONE
+        return a
+
+    def _swap_prior(self, nxt):
+        """After a step that wrote the next priors into nxt: they become the next call's prior, and this call's prior
+        buffer the next call's output."""
+        if nxt is not None:
+            self._prior, self._prior_spare = nxt, getattr(self, "_prior", None)
+
     def _mpc_step_native(self, x0, system, n_samples, w, sample_fn, n_wo_noise, ddim_steps, clamp_x0, seed, noise,
                          comm, clip_rule="chain", warm_start=None, prior=None, elites=None):
-        """mpc_step as one libmpcd call (mpcd_mpc_step): one H2D copy of the context row, the kernels,
+        """mpc_step as one libmpcd call (mpcd_mpc_step): the context row by value in the sampler launch, the kernels,
         the result block {best, u_best} written to pinned host memory by the selecting workgroup (one rank) or one
         D2H copy + stream synchronisation (with a communicator)."""
         size, rank = (comm.size, comm.rank) if comm is not None else (1, 0)
@@ -1625,31 +1652,8 @@ class DiffusionMPC:
         if d != system.n_u:
             raise ValueError(f"system {system.name} has {system.n_u} inputs, samples have {d}")
         sampler = self._sampler_id(sample_fn)
-        warm = None
-        if warm_start is not None or prior is not None:
-            K = int(warm_start) if warm_start is not None else 0
-            if K < 1 or K > self.n_steps or sampler != N.MPCD_DDPM_CFG:
-                raise ValueError(f"warm_start={warm_start} needs 1 <= K <= {self.n_steps} and the CFG-DDPM sampler")
-            if elites is not None:
-                elites = self._check_elites(elites, B)
-            if prior is None:
-                prior = getattr(self, "_prior", None)
-                if elites is not None and prior is not None and prior.shape[0] not in (1, B):
-                    raise ValueError(f"the stored priors have {prior.shape[0]} rows, neither 1 nor n_samples={B}: call "
-                                     "reset_warm_start() after changing n_samples")
-            # no prior yet: a cold step (t_start 0) that fills it
-            warm, prior = self._warm(prior, K if prior is not None else 0, B)
-            if elites is None and prior is not None and prior.shape[0] != 1:
-                raise ValueError(f"prior must be one plan [{H}, {d}], got {tuple(prior.shape)}")
-            rows = 1 if elites is None else B  # the next priors: the winner's plan, or one per candidate
-            nxt = getattr(self, "_prior_spare", None)
-            if nxt is None or nxt.shape[0] != rows or (prior is not None and nxt.data_ptr() == prior.data_ptr()):
-                nxt = torch.empty((rows, H, d), dtype=torch.float32, device=self.device)
-        if noise is not None:
-            steps = self.n_denoise_steps(sample_fn, n_wo_noise, ddim_steps, warm.t_start or None if warm else None)
-            noise = noise.to(self.device, torch.float32).contiguous()
-            if tuple(noise.shape) != (steps + 1, B, H, d):
-                raise ValueError(f"noise must be [{steps + 1}, {B}, {H}, {d}], got {tuple(noise.shape)}")
+        warm, prior, nxt, elites = self._step_warm(sampler, B, warm_start, prior, elites)
+        noise = self._step_noise(noise, sample_fn, n_wo_noise, ddim_steps, warm, B)
         u_norm = torch.empty((B, H, d), dtype=torch.float32, device=self.device)
         cost = torch.empty(B, dtype=torch.float64, device=self.device)
         costs = torch.empty(size * B, dtype=torch.float64, device=self.device) if size > 1 else cost
@@ -1661,15 +1665,8 @@ class DiffusionMPC:
                noise is None)
         cache = getattr(self, "_step_args_cache", None)
         if cache is None or cache[0] != key:
-            a = N.StepArgs()
-            a.sys = ctypes.pointer(desc)
-            a.ctx_min, a.ctx_max = self.ctx_min.ctypes.data, self.ctx_max.ctypes.data
-            a.act_min, a.act_max = self.act_min.ctypes.data, self.act_max.ctypes.data
-            a.sample = self._args(sampler, B, _STEP_CONTEXT, w, n_wo_noise, ddim_steps, clamp_x0, seed, rank * B,
-                                  noise, u_norm, None)
-            a.clip_rule = _CLIP_RULES[clip_rule]
-            if clip_rule == "final" and sampler == N.MPCD_DDPM_CFG and self.ddpm_final_in_range:
-                a.clip_rule = N.MPCD_CLIP_NONE
+            a = self._step_args(desc, sampler, B, w, n_wo_noise, ddim_steps, clamp_x0, seed, rank * B, noise, u_norm,
+                                clip_rule)
             # (+ the DDIM time list a.sample points into, kept alive with the block)
             cache = self._step_args_cache = (key, a, ctypes.byref(a), desc, N.Best(), ctypes.c_int32(),
                                              getattr(self, "_times", None))
@@ -1693,13 +1690,11 @@ class DiffusionMPC:
                                                   ctypes.c_void_p(nxt.data_ptr()), el.ctypes.data, ctypes.byref(best),
                                                   u_best.__array_interface__["data"][0], self._stream()),
                     "mpcd_mpc_step_elite")
-            self._prior, self._prior_spare = nxt, getattr(self, "_prior", None)
         else:
             N.check(self._lib.mpcd_mpc_step_warm(self._ctx, a_ref, ctypes.byref(warm), ctypes.c_void_p(nxt.data_ptr()),
                                                  ctypes.byref(best), u_best.__array_interface__["data"][0],
                                                  self._stream()), "mpcd_mpc_step_warm")
-            # the refreshed prior becomes the next call's; this call's buffer is the next one's output
-            self._prior, self._prior_spare = nxt, getattr(self, "_prior", None)
+        self._swap_prior(nxt)
         N.check(self._lib.mpcd_last_step_flags(self._ctx, ctypes.byref(fl)), "mpcd_last_step_flags")
         return MPCResult(u0=u_best[0].copy(), u_best=u_best, best_cost=best.cost, best_index=best.index, costs=costs,
                          u_norm=u_norm, flags=fl.value, elite_index=None if el is None else el["index"].copy(),

@@ -719,3 +719,48 @@ def test_the_three_steps_alternate_on_one_context():
     for rnd in range(2):
         for i, f in enumerate(steps(plan)):
             assert key(f()) == want[i], f"round {rnd}, step {i}"
+
+
+# ------------------------------------------------------------------------ 11. the first call on a fresh context
+FORMS = ["cold", "warm", "elites", "constr", "constr_elites"]
+
+
+def _form(plan, form, sysm, seed, con, clip_rule):
+    """One of the five single-state calls at B = 70 (two workgroups, the second ragged). A function of its arguments
+    alone: the warm forms take their prior from the call, not from what an earlier call left in the planner."""
+    kw = dict(seed=seed, clip_rule=clip_rule)
+    if form not in ("cold", "constr"):
+        kw.update(warm_start=LOOP_K, prior=torch.linspace(-0.9, 0.9, 32).reshape(16, 2))
+    if form.endswith("elites"):
+        kw.update(elites=4)
+    if form.startswith("constr"):
+        return plan.mpc_step_constr(X0, sysm, 70, con, u_prev=U_PREV, **kw)
+    return plan.mpc_step(X0, sysm, 70, **kw)
+
+
+def _result_bits(r):
+    extra = (r.violation, r.n_feasible, r.elite_index, r.elite_cost, r.elite_violation)
+    return (r.best_index, r.flags, np.float64(r.best_cost).tobytes(), r.u_best.tobytes()) + \
+        tuple(None if v is None else np.asarray(v).tobytes() for v in extra)
+
+
+@pytest.fixture(scope="module")
+def first_calls():
+    """{(form, clip_rule): the result bits of that call made first on a fresh planner}, with the system, seed and set"""
+    sysm = systems.double_int2d()
+    seed, con = _live_set(_loop_plan(), sysm, 70)
+    res = {(f, c): _form(_loop_plan(), f, sysm, seed, con, c) for f in FORMS for c in ("chain", "final")}
+    assert res["constr", "final"].n_feasible not in (0, 70), "the set must be live"
+    return sysm, seed, con, {key: _result_bits(r) for key, r in res.items()}
+
+
+@pytest.mark.parametrize("clip_rule", ["chain", "final"])
+@pytest.mark.parametrize("first", FORMS)
+def test_the_first_entry_point_on_a_context_does_not_matter(first_calls, first, clip_rule):
+    """The mapped host block is sized and laid out once for every entry point: whichever form a fresh context meets
+    first, that call and each other form after it return the bits of the same call made first on a fresh planner."""
+    sysm, seed, con, want = first_calls
+    plan = _loop_plan()
+    for form in [first] + [f for f in FORMS if f != first]:
+        got = _result_bits(_form(plan, form, sysm, seed, con, clip_rule))
+        assert got == want[form, clip_rule], f"{form} after {first} first"

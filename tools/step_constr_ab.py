@@ -3,9 +3,10 @@
 H = 32, an f32x3 MLP at the cfg2 net shape (d = 2, C = 4, N = 100), one GPU, one state x 4,096 candidates.
 
 Both builds (this one and, with --parent-lib, a libmpcd.so of the parent commit loaded through MPCD_LIB) run, in the same
-sequence, what this change leaves alone: the native unconstrained mpc_step, cold and warm (K = 10), and the composed
-constrained step mpc_step(constraints=) (cold: it takes no warm start). A digest of every output must be the same for
-both builds. This build's process then goes on to mpc_step_constr:
+sequence, what this change leaves alone: the native unconstrained mpc_step, cold, warm (K = 10) and warm with elites = 8,
+and the composed constrained step mpc_step(constraints=) (cold: it takes no warm start). A digest of every output must be
+the same for both builds. This build's process, and the parent's if its library has the entry point (then a second
+digest, of these outputs, must be the same too), goes on to mpc_step_constr:
 
   constr box               the box alone, cold
   constr full              the box, 2 rows, the rate bounds and u_prev, cold
@@ -37,9 +38,13 @@ def worker(a):
     import torch
 
     from mpc_via_diffusion_model_amd import _native as N
-    if a.worker == "parent":  # the parent's library has no such entry point to bind
-        for name in NEW:
-            N.EXPORTS.pop(name, None)
+    this = a.worker == "this"
+    if not this:  # a parent from before mpc_step_constr has no such entry point to bind; a later one runs those paths too
+        import ctypes
+        this = all(hasattr(ctypes.CDLL(os.environ["MPCD_LIB"]), name) for name in NEW)
+        if not this:
+            for name in NEW:
+                N.EXPORTS.pop(name, None)
     from mpc_via_diffusion_model_amd import Constraints, DiffusionMPC, NetSpec, systems
     from oracle import nets
 
@@ -54,9 +59,15 @@ def worker(a):
     rows = [([0.1 * (r + 1), -0.2, 0.3, 0.05 * r], [0.25, -0.125], 1e6) for r in range(2)]
     box, full, tol = Constraints(box_py), Constraints(box_py, rows, [1.9, 1.95]), 0.0
     xs = np.random.default_rng(0).uniform(-1.0, 1.0, (T + 1, 4))
-    this = a.worker == "this"
-    digest = hashlib.sha256()
+    digest, digest_constr = hashlib.sha256(), hashlib.sha256()
     res, live = {}, {}
+
+    def add(dg, r):
+        fields = [r.u_best, np.float64(r.best_cost), np.int64(r.best_index), r.costs.cpu().numpy(), r.u_norm.cpu().numpy()]
+        fields += [np.asarray(f) for f in (r.violation, r.n_feasible, r.elite_index, r.elite_cost, r.elite_violation)
+                   if f is not None]
+        for f in fields:
+            dg.update(np.ascontiguousarray(f).tobytes())
 
     def run(kind):
         """T + 1 control steps (the first one untimed): (results, ms per step by the host clock, by HIP events)"""
@@ -72,6 +83,8 @@ def worker(a):
                 r = plan.mpc_step(xs[it], sysm, B, **kw)
             elif kind == "step warm":
                 r = plan.mpc_step(xs[it], sysm, B, warm_start=K, **kw)
+            elif kind == "step warm elites":
+                r = plan.mpc_step(xs[it], sysm, B, warm_start=K, elites=k, **kw)
             elif kind == "composed full":
                 r = plan.mpc_step(xs[it], sysm, B, constraints=full, u_prev=prev[0], viol_tol=tol, **kw)
             elif kind == "constr box":
@@ -92,14 +105,11 @@ def worker(a):
                 evs.append(e0.elapsed_time(e1))
         return out, statistics.mean(host), statistics.mean(evs)
 
-    common = ["step", "step warm", "composed full"]
+    common = ["step", "step warm", "step warm elites", "composed full"]
     flip = (lambda seq: list(seq)[::-1]) if a.reverse else list
     for kind in common:  # the outputs first (this also warms every variant)
         for r in run(kind)[0]:
-            fields = (r.u_best, np.float64(r.best_cost), np.int64(r.best_index), r.costs.cpu().numpy(), r.u_norm.cpu().numpy())
-            fields += (np.float64(r.violation), np.int64(r.n_feasible)) if kind == "composed full" else ()
-            for f in fields:
-                digest.update(np.ascontiguousarray(f).tobytes())
+            add(digest, r)
     for kind in flip(common):
         _, res[f"host|{kind}"], res[f"event|{kind}"] = run(kind)
     if this:
@@ -110,11 +120,15 @@ def worker(a):
                 (r.best_index, r.best_cost, r.violation, r.n_feasible), f"step {it}: the one call is not the composed step"
             np.testing.assert_array_equal(g.u_best, r.u_best)
         for kind in own:
-            live[kind] = float(np.mean([r.n_feasible for r in run(kind)[0][1:]]))
+            out = run(kind)[0]
+            live[kind] = float(np.mean([r.n_feasible for r in out[1:]]))
+            for r in out:
+                add(digest_constr, r)
         for kind in flip(own + ["composed full"]):
             name = kind if kind != "composed full" else "composed full (again)"
             _, res[f"host|{name}"], res[f"event|{name}"] = run(kind)
-    print(TAG + json.dumps({"res": res, "live": live, "digest": digest.hexdigest(), "device": torch.cuda.get_device_name(0)}))
+    print(TAG + json.dumps({"res": res, "live": live, "digest": digest.hexdigest(), "device": torch.cuda.get_device_name(0),
+                            "digest_constr": digest_constr.hexdigest() if this else None}))
     return 0
 
 
@@ -148,26 +162,33 @@ def main():
         return json.loads(lines[-1][len(TAG):])
 
     builds = ["this"] + (["parent"] if a.parent_lib else [])
-    times, digests, device, live = {}, {}, None, {}
+    times, digests, device, live, constr, constr_builds = {}, {}, None, {}, set(), set()
     for rnd in range(a.rounds):
         flip = (rnd % 2 == 1) != a.reverse
         for which in (builds[::-1] if flip else builds):
             r = child(which, flip)
             device = r["device"]
             digests.setdefault(which, set()).add(r["digest"])
+            if r.get("digest_constr"):
+                constr.add(r["digest_constr"])
+                constr_builds.add(which)
             live.update(r["live"])
             for key, v in r["res"].items():
                 clock, name = key.split("|")
                 times.setdefault(clock, {}).setdefault(f"{which}: {name}", []).append(v)
     if any(len(dg) != 1 for dg in digests.values()) or len(set.union(*digests.values())) != 1:
         raise RuntimeError(f"the unchanged paths' outputs differ between runs or builds: {digests}")
+    if len(constr) != 1:
+        raise RuntimeError(f"mpc_step_constr's outputs differ between runs or builds: {constr}")
     print(f"device {device}; {a.rounds} rounds, one fresh process per build and round; ms per control step over {a.steps} "
           "steps of one state x 4,096 candidates; host: the host clock around the call; event: between two HIP events "
           "recorded around it")
-    print("mpc_step (cold, warm K = 10) and the composed mpc_step(constraints=) outputs "
+    print("mpc_step (cold, warm K = 10, with elites = 8) and the composed mpc_step(constraints=) outputs "
           + ("byte-identical on both builds" if a.parent_lib else "identical in every round")
           + f" (sha256 {next(iter(digests['this']))[:16]}...); mpc_step_constr == the composed step (index, cost, V, "
-          "n_feasible, plan) at every step in every round")
+          "n_feasible, plan) at every step in every round; its four forms' outputs "
+          + ("byte-identical on both builds" if len(constr_builds) == 2 else "identical in every round")
+          + f" (sha256 {next(iter(constr))[:16]}...)")
     for kind, n in live.items():
         print(f"{kind}: {n:.0f} of 4096 candidates feasible on average over the timed steps")
     out = {}
