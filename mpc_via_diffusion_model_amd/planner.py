@@ -24,12 +24,82 @@ import torch
 from . import _native as N
 from . import distributed as D
 from . import schedule as S
+from .constraints import Constraints  # noqa: F401 (re-exported)
+from .constraints import NEEDS_ARGMIN, _p, _viol_tol, feasibility, state_box_of
 from .systems import System
 
 _STEP_CONTEXT = object()  # _args placeholder: mpcd_mpc_step normalises x0 into the context itself
 _CLIP_RULES = {"chain": N.MPCD_CLIP_CHAIN, "final": N.MPCD_CLIP_FINAL}
 _SAMPLERS = {"ddpm_cfg": N.MPCD_DDPM_CFG, "ddpm_cart_pole_sample_fn": N.MPCD_DDPM_CFG,
              "ddim_cfg": N.MPCD_DDIM_CFG, "ddim": N.MPCD_DDIM, "ddim_sample": N.MPCD_DDIM}
+_ELITES_NEED_WARM = "elites needs warm_start=K: the elite set seeds the warm-start priors"
+_BAD_CLIP_RULE = f"clip_rule must be one of {sorted(_CLIP_RULES)}"
+# closed_loop(native=True) and the native mpc_step take neither producer of V: their refusals, by producer
+_NO_NATIVE_LOOP = {
+    "state_box": "state_box is not available with native=True: folding the constraint into mpcd_closed_loop's fused "
+                 "tail is the follow-up; use native=False",
+    "constraints": "constraints are not available with native=True: mpcd_closed_loop's fused tail takes no constraint "
+                   "set; use native=False"}
+_NO_NATIVE_STEP = {
+    "state_box": "state_box is not available with native=True: the fused step (mpcd_mpc_step) takes no box; its "
+                 "follow-up mpc_step_constr does (Constraints(state_box=...)), or leave native unset",
+    "constraints": "constraints are not available with native=True: the fused step (mpcd_mpc_step) takes no constraint "
+                   "set; leave native unset or False"}
+_NO_WARM_STEP = {
+    "state_box": "state_box with warm_start / prior / elites needs the native step, which takes no box: use its "
+                 "follow-up mpc_step_constr, or closed_loop(native=False)",
+    "constraints": "constraints with warm_start / prior / elites need the native step, which takes no constraint set; "
+                   "closed_loop(native=False) combines them"}
+_SINGLE_RANK_STEP = {
+    "state_box": "state_box is single-rank here: the multi-rank feasibility-first selection is the follow-up "
+                 "mpc_step_constr's",
+    "constraints": "constraints are single-rank: there is no multi-rank feasibility-first selection"}
+
+
+def _rows_dev(rows, device, name, M, cols):
+    """rows [M, cols] (or [cols] for one state; host values or a device tensor) as a contiguous device float64 tensor,
+    checked (M None: any number of rows); None stays None"""
+    if rows is None:
+        return None
+    if torch.is_tensor(rows):
+        t = rows.to(device, torch.float64)
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.float64)).to(device)
+    t = (t[None] if t.dim() == 1 else t).contiguous()
+    if t.dim() != 2 or t.shape[1] != cols or (M is not None and t.shape[0] != M):
+        raise ValueError(f"{name} must be [{'M' if M is None else M}, {cols}], got {tuple(t.shape)}")
+    return t
+
+
+def _check_clip_flags(clip_flags, M, device):
+    if clip_flags.dtype != torch.int32 or clip_flags.device != device or clip_flags.numel() != M:
+        raise ValueError(f"clip_flags must be {M} int32 codes on {device}")
+
+
+def _group_split(B, M, group, noun):
+    """the candidates per state of B rows over M states (default B // M), checked"""
+    group = B // M if group is None else int(group)
+    if group < 1 or M * group != B:
+        raise ValueError(f"u_norm has {B} {noun}: not {M} states x group={group}")
+    return group
+
+
+def _check_inputs(system, d):
+    if d != system.n_u:
+        raise ValueError(f"system {system.name} has {system.n_u} inputs, samples have {d}")
+
+
+def _history(T, M, nx, d, dev):
+    """closed_loop's device history: states [T + 1, M, n_x], actions [T, M, d], costs and indices [T, M]"""
+    f64 = dict(dtype=torch.float64, device=dev)
+    return (torch.empty((T + 1, M, nx), **f64), torch.empty((T, M, d), **f64), torch.empty((T, M), **f64),
+            torch.empty((T, M), dtype=torch.int64, device=dev))
+
+
+def _loop_result(xs, us, cs, ix, **more):
+    """the history on the host, state-major (the copies wait for the stream)"""
+    return ClosedLoopResult(x=xs.transpose(0, 1).cpu().numpy(), u=us.transpose(0, 1).cpu().numpy(),
+                            cost=cs.t().cpu().numpy(), index=ix.t().cpu().numpy(), **more)
 
 
 def philox_noise(n_cand, n_slices, flat, seed=0, global_offset=0, device=None):
@@ -39,8 +109,8 @@ def philox_noise(n_cand, n_slices, flat, seed=0, global_offset=0, device=None):
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
     out = torch.empty((int(n_slices), int(n_cand), int(flat)), dtype=torch.float32, device=dev)
     N.check(N.lib().mpcd_philox_noise(int(seed) & 0xFFFFFFFFFFFFFFFF, int(global_offset), int(n_cand), int(n_slices),
-                                      int(flat), ctypes.c_void_p(out.data_ptr()),
-                                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mpcd_philox_noise")
+                                      int(flat), _p(out), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+            "mpcd_philox_noise")
     return out
 
 
@@ -146,56 +216,6 @@ class BatchStepResult:
     elite_violation: np.ndarray = None  # [M, k] mpc_step_batch_box / _constr with elites: V of each ranked candidate
 
 
-class Constraints:
-    """A constraint set (mpcd.h "Constraint set"): a state box, up to 8 linear rows and per-input rate bounds.
-
-    state_box: (lo, hi) as everywhere (None = unbounded: the whole box, a side, or single entries).
-    rows: a sequence of (a, c, b) meaning sum_i a[i] x[i] + sum_j c[j] u[j] <= b on every visited pair (x_{k+1}, u_k):
-    a has n_x entries, c has n_u entries or is None (zeros), b is a float (+inf switches the row off).
-    du_max: n_u entries bounding |u_k[j] - u_{k-1}[j]| (None, or None entries = unbounded).
-    The set is checked against a system when a call takes it; a ValueError names the entry."""
-
-    def __init__(self, state_box=None, rows=(), du_max=None):
-        self.state_box, self.rows, self.du_max = state_box, tuple(rows), du_max
-
-    def native(self, n_x, n_u):
-        """the mpcd_constraints of a system with n_x states and n_u inputs (checked)"""
-        con = N.ConstraintSet()
-        con.box = DiffusionMPC._state_box((None, None) if self.state_box is None else self.state_box, n_x)
-        if len(self.rows) > N.MPCD_MAX_CON_ROWS:
-            raise ValueError(f"constraints: {len(self.rows)} rows, at most {N.MPCD_MAX_CON_ROWS}")
-        con.n_rows = len(self.rows)
-        for r in range(N.MPCD_MAX_CON_ROWS):
-            con.b[r] = np.inf
-        for r, row in enumerate(self.rows):
-            try:
-                a, c, b = row
-                a = [float(v) for v in a]
-                c = [0.0] * n_u if c is None else [float(v) for v in c]
-                b = float(b)
-            except (TypeError, ValueError):
-                raise ValueError(f"constraints row {r}: must be (a [n_x], c [n_u] or None, b)") from None
-            if len(a) != n_x or len(c) != n_u:
-                raise ValueError(f"constraints row {r}: a has {len(a)} entries (n_x = {n_x}), c has {len(c)} (n_u = {n_u})")
-            for what, vals, dst in (("a", a, con.A[r]), ("c", c, con.C[r])):
-                for i, v in enumerate(vals):
-                    if not np.isfinite(v):
-                        raise ValueError(f"constraints row {r}: {what}[{i}] = {v} is not finite")
-                    dst[i] = v
-            if np.isnan(b) or b == -np.inf:
-                raise ValueError(f"constraints row {r}: b = {b} (use +inf to switch a row off)")
-            con.b[r] = b
-        du = [None] * n_u if self.du_max is None else list(self.du_max)
-        if len(du) != n_u:
-            raise ValueError(f"constraints du_max must have n_u = {n_u} entries, got {len(du)}")
-        for j in range(4):
-            v = np.inf if j >= n_u or du[j] is None else float(du[j])
-            if not v >= 0.0:
-                raise ValueError(f"constraints du_max[{j}] = {v} must be >= 0 (None = unbounded)")
-            con.du_max[j] = v
-        return con
-
-
 _STATE_RESULT = np.dtype([("cost", "<f8"), ("index", "<i8"), ("flags", "<i4"), ("reserved", "<i4")])
 _BEST = np.dtype([("cost", "<f8"), ("index", "<i8")])  # mpcd_best
 
@@ -230,12 +250,10 @@ class DiffusionMPC:
             if tuple(params[n].shape) != shp:
                 raise ValueError(f"{n}: shape {tuple(params[n].shape)} != {shp}")
         blob = blob.contiguous()
-        N.check(self._lib.mpcd_load_net(self._ctx, ctypes.byref(self._desc), ctypes.c_void_p(blob.data_ptr()),
-                                        blob.numel()), "mpcd_load_net")
+        N.check(self._lib.mpcd_load_net(self._ctx, ctypes.byref(self._desc), _p(blob), blob.numel()), "mpcd_load_net")
         tab = S.pack(self.tables)
         std = S.posterior_std(self.tables).contiguous()
-        N.check(self._lib.mpcd_set_schedule(self._ctx, ctypes.c_void_p(tab.data_ptr()), self.n_steps,
-                                            ctypes.c_void_p(std.data_ptr())), "mpcd_set_schedule")
+        N.check(self._lib.mpcd_set_schedule(self._ctx, _p(tab), self.n_steps, _p(std)), "mpcd_set_schedule")
         # DDPM with clip_denoised ends with x = coef1[0]*clamp(x0) + coef2[0]*x: if coef2[0] == 0 and
         # |coef1[0]| <= 1 + 1e-4 the clip flag over the FINAL samples is provably 0 (clip_rule="final";
         # the reference's chain-wide rule still sees x_T and is computed).
@@ -280,10 +298,9 @@ class DiffusionMPC:
         x = x.contiguous()
         out = torch.empty_like(x)
         d = x.shape[-1]
-        flag_ptr = ctypes.c_void_p(clip_flag.data_ptr()) if clip_flag is not None else None
-        N.check(self._lib.mpcd_unnormalize(self._ctx, ctypes.c_void_p(x.data_ptr()), x.numel() // d, d,
-                                           self.act_min.ctypes.data, self.act_max.ctypes.data, flag_ptr,
-                                           ctypes.c_void_p(out.data_ptr()), self._stream()), "mpcd_unnormalize")
+        N.check(self._lib.mpcd_unnormalize(self._ctx, _p(x), x.numel() // d, d, self.act_min.ctypes.data,
+                                           self.act_max.ctypes.data, _p(clip_flag), _p(out), self._stream()),
+                "mpcd_unnormalize")
         return out
 
     # ------------------------------------------------------------------ sampling (A2-A11)
@@ -311,6 +328,31 @@ class DiffusionMPC:
             raise ValueError(f"unsupported sample_fn {name!r}; use one of {sorted(_SAMPLERS)}")
         return _SAMPLERS[name]
 
+    def _ddim_times(self, a):
+        """the reference's DDIM time list of a SampleArgs (a DDIM sampler's) with ddim_steps set; self._times keeps it alive"""
+        times = S.ddim_times(self.n_steps, a.ddim_steps or None)
+        self._times = (ctypes.c_int32 * len(times))(*times)
+        a.ddim_times = ctypes.cast(self._times, ctypes.POINTER(ctypes.c_int32))
+        a.n_ddim_times = len(times)
+
+    def _plant_block(self, a, desc):
+        """sys and the normaliser limits: the head of the step, closed-loop and batched-step argument blocks"""
+        a.sys = ctypes.pointer(desc)
+        a.ctx_min, a.ctx_max = self.ctx_min.ctypes.data, self.ctx_max.ctypes.data
+        a.act_min, a.act_max = self.act_min.ctypes.data, self.act_max.ctypes.data
+        return a
+
+    def _noise(self, noise, B, steps):
+        """Injected noise on the device, checked to be [steps + 1, B, H, d]: one slice per denoise step of the call
+        (fewer after a warm start) and one more. steps: the count, or n_denoise_steps' arguments."""
+        H, d = self.spec.horizon, self.spec.state_dim
+        if not isinstance(steps, int):
+            steps = self.n_denoise_steps(*steps)
+        noise = noise.to(self.device, torch.float32).contiguous()
+        if tuple(noise.shape) != (steps + 1, B, H, d):
+            raise ValueError(f"noise must be [{steps + 1}, {B}, {H}, {d}], got {tuple(noise.shape)}")
+        return noise
+
     def _args(self, sampler, batch, context, w, n_wo_noise, ddim_steps, clamp_x0, seed, global_offset, noise,
               x_out, chain, absmax=None, group=None):
         a = N.SampleArgs()
@@ -337,10 +379,7 @@ class DiffusionMPC:
         a.ddim_steps = int(ddim_steps or 0)
         a.clamp_x0 = 1 if clamp_x0 else 0
         if sampler != N.MPCD_DDPM_CFG:
-            times = S.ddim_times(self.n_steps, ddim_steps or None)
-            self._times = (ctypes.c_int32 * len(times))(*times)
-            a.ddim_times = ctypes.cast(self._times, ctypes.POINTER(ctypes.c_int32))
-            a.n_ddim_times = len(times)
+            self._ddim_times(a)
         a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         a.global_offset = int(global_offset)
         a.noise = noise.data_ptr() if noise is not None else None
@@ -385,10 +424,8 @@ class DiffusionMPC:
             raise ValueError(f"index must be a contiguous int64 tensor on {self.device}")
         if out is None:
             out = torch.empty((M, H, d), dtype=torch.float32, device=self.device)
-        N.check(self._lib.mpcd_shift_plans(self._ctx, ctypes.c_void_p(u_norm.data_ptr()), B, H,
-                                           ctypes.c_void_p(index.data_ptr()) if index is not None else None,
-                                           int(index_offset), M, ctypes.c_void_p(out.data_ptr()), self._stream()),
-                "mpcd_shift_plans")
+        N.check(self._lib.mpcd_shift_plans(self._ctx, _p(u_norm), B, H, _p(index), int(index_offset), M, _p(out),
+                                           self._stream()), "mpcd_shift_plans")
         return out
 
     def n_denoise_steps(self, sample_fn="ddpm_cfg", n_wo_noise=0, ddim_steps=None, t_start=None):
@@ -398,10 +435,7 @@ class DiffusionMPC:
         a.n_wo_noise = n_wo_noise
         a.ddim_steps = int(ddim_steps or 0)
         if a.sampler != N.MPCD_DDPM_CFG:
-            times = S.ddim_times(self.n_steps, ddim_steps or None)
-            self._times = (ctypes.c_int32 * len(times))(*times)
-            a.ddim_times = ctypes.cast(self._times, ctypes.POINTER(ctypes.c_int32))
-            a.n_ddim_times = len(times)
+            self._ddim_times(a)
         n = ctypes.c_int32()
         if t_start is None:
             N.check(self._lib.mpcd_sample_steps(self._ctx, ctypes.byref(a), ctypes.byref(n)), "mpcd_sample_steps")
@@ -446,9 +480,7 @@ class DiffusionMPC:
             context = context.to(self.device).contiguous()
         steps = self.n_denoise_steps(sample_fn, n_wo_noise, ddim_steps, t_start if t_start else None)
         if noise is not None:
-            noise = noise.to(self.device, torch.float32).contiguous()
-            if tuple(noise.shape) != (steps + 1, B, H, d):
-                raise ValueError(f"noise must be [{steps + 1}, {B}, {H}, {d}], got {tuple(noise.shape)}")
+            noise = self._noise(noise, B, steps)
         x = out if out is not None else torch.empty((B, H, d), dtype=torch.float32, device=self.device)
         chain = torch.empty((steps + 1, B, H, d), dtype=torch.float32, device=self.device) if return_chain else None
         if absmax_out is not None and (absmax_out.dtype != torch.float32 or absmax_out.numel() != B
@@ -505,10 +537,8 @@ class DiffusionMPC:
                 context = context[None]
         ec = torch.empty_like(x)
         eu = torch.empty_like(x) if self.spec.cfg else None
-        N.check(self._lib.mpcd_eps(self._ctx, ctypes.c_void_p(x.data_ptr()), int(t),
-                                   ctypes.c_void_p(context.data_ptr()) if context is not None else None,
-                                   1 if context is not None and context.shape[0] == 1 else 0, B,
-                                   ctypes.c_void_p(ec.data_ptr()), ctypes.c_void_p(eu.data_ptr()) if eu is not None else None,
+        N.check(self._lib.mpcd_eps(self._ctx, _p(x), int(t), _p(context),
+                                   1 if context is not None and context.shape[0] == 1 else 0, B, _p(ec), _p(eu),
                                    self._stream()), "mpcd_eps")
         return ec, eu
 
@@ -579,28 +609,24 @@ class DiffusionMPC:
     def rollout_cost(self, system: System, x0, u_norm, clip_flag=None):
         """fp64 cost per candidate [B] on device."""
         B, H, d = u_norm.shape
-        if d != system.n_u:
-            raise ValueError(f"system {system.name} has {system.n_u} inputs, samples have {d}")
+        _check_inputs(system, d)
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
         cost = torch.empty(B, dtype=torch.float64, device=self.device)
         desc = system.desc()
-        flag_ptr = ctypes.c_void_p(clip_flag.data_ptr()) if clip_flag is not None else None
-        N.check(self._lib.mpcd_rollout_cost(self._ctx, ctypes.byref(desc), x0.ctypes.data,
-                                            ctypes.c_void_p(u_norm.contiguous().data_ptr()), self.act_min.ctypes.data,
-                                            self.act_max.ctypes.data, B, H, flag_ptr, ctypes.c_void_p(cost.data_ptr()),
-                                            self._stream()), "mpcd_rollout_cost")
+        N.check(self._lib.mpcd_rollout_cost(self._ctx, ctypes.byref(desc), x0.ctypes.data, _p(u_norm.contiguous()),
+                                            self.act_min.ctypes.data, self.act_max.ctypes.data, B, H, _p(clip_flag),
+                                            _p(cost), self._stream()), "mpcd_rollout_cost")
         return cost
 
     def clip_flag(self, x):
         flag = torch.empty(1, dtype=torch.int32, device=self.device)
-        N.check(self._lib.mpcd_clip_flag(self._ctx, ctypes.c_void_p(x.data_ptr()), x.numel(),
-                                         ctypes.c_void_p(flag.data_ptr()), self._stream()), "mpcd_clip_flag")
+        N.check(self._lib.mpcd_clip_flag(self._ctx, _p(x), x.numel(), _p(flag), self._stream()), "mpcd_clip_flag")
         return flag
 
     def argmin(self, cost, index_offset=0):
         """Device argmin (NaN = +inf, lowest index on ties) -> (index, cost); syncs the stream."""
-        N.check(self._lib.mpcd_argmin(self._ctx, ctypes.c_void_p(cost.data_ptr()), cost.numel(), index_offset,
-                                      ctypes.c_void_p(self._best.data_ptr()), self._stream()), "mpcd_argmin")
+        N.check(self._lib.mpcd_argmin(self._ctx, _p(cost), cost.numel(), index_offset, _p(self._best), self._stream()),
+                "mpcd_argmin")
         host = self._best.cpu()
         return int(host.view(torch.int64)[1]), float(host[0])
 
@@ -620,8 +646,8 @@ class DiffusionMPC:
         group = cost.numel() // M
         k = self._check_elites(k, group)
         raw = torch.empty((M, k, 2), dtype=torch.int64, device=self.device)
-        N.check(self._lib.mpcd_topk(self._ctx, ctypes.c_void_p(cost.data_ptr()), M, group, k, int(index_offset),
-                                    ctypes.c_void_p(raw.data_ptr()), self._stream()), "mpcd_topk")
+        N.check(self._lib.mpcd_topk(self._ctx, _p(cost), M, group, k, int(index_offset), _p(raw), self._stream()),
+                "mpcd_topk")
         return raw
 
     def topk(self, cost, k, n_groups=1, index_offset=0):
@@ -647,8 +673,7 @@ class DiffusionMPC:
         if elite_index.dtype != torch.int64 or elite_index.device != self.device or elite_index.dim() != 2:
             raise ValueError(f"elite_index must be an int64 [M, k] tensor on {self.device}")
         M, k = elite_index.shape
-        if group < 1 or M * group != B:
-            raise ValueError(f"u_norm has {B} rows: not {M} states x group={group}")
+        group = _group_split(B, M, group, "rows")
         self._check_elites(k, group)
         raw = torch.zeros((M, k, 2), dtype=torch.int64, device=self.device)
         raw[..., 1] = elite_index
@@ -661,46 +686,39 @@ class DiffusionMPC:
         elif (tuple(out.shape) != (B, H, d) or out.dtype != torch.float32 or out.device != self.device
               or not out.is_contiguous()):
             raise ValueError(f"out must be a contiguous fp32 [{B}, {H}, {d}] tensor on {self.device}")
-        N.check(self._lib.mpcd_elite_priors(self._ctx, ctypes.c_void_p(u_norm.data_ptr()), raw.shape[0], group, H,
-                                            ctypes.c_void_p(raw.data_ptr()), raw.shape[1], int(index_offset),
-                                            1 if shift else 0, ctypes.c_void_p(out.data_ptr()), self._stream()),
+        N.check(self._lib.mpcd_elite_priors(self._ctx, _p(u_norm), raw.shape[0], group, H, _p(raw), raw.shape[1],
+                                            int(index_offset), 1 if shift else 0, _p(out), self._stream()),
                 "mpcd_elite_priors")
         return out
 
     # ------------------------------------------------------------------ state constraints
-    @staticmethod
-    def _state_box(state_box, n_x):
-        """(lo, hi) with None = unbounded (the whole side, or single entries) -> the mpcd_state_box of an n_x system"""
-        try:
-            lo, hi = state_box
-        except (TypeError, ValueError):
-            raise ValueError("state_box must be a pair (lo, hi) of per-component bounds, None = unbounded") from None
-        box = N.StateBox()
-        for side, fill, dst in ((lo, -np.inf, box.lo), (hi, np.inf, box.hi)):
-            vals = [None] * n_x if side is None else list(side)
-            if len(vals) != n_x:
-                raise ValueError(f"state_box bounds must have n_x = {n_x} entries each, got {len(vals)}")
-            for i in range(12):
-                dst[i] = fill if i >= n_x or vals[i] is None else float(vals[i])
-        for i in range(n_x):
-            if np.isnan(box.lo[i]) or np.isnan(box.hi[i]) or box.lo[i] > box.hi[i]:
-                raise ValueError(f"state_box component {i}: [{box.lo[i]}, {box.hi[i]}] is not an interval")
-        return box
+    _state_box = staticmethod(state_box_of)
 
-    @staticmethod
-    def _viol_tol(viol_tol):
-        tol = float(viol_tol)
-        if not tol >= 0.0:
-            raise ValueError(f"viol_tol = {viol_tol} must be >= 0")
-        return tol
+    def _clip_flags(self, src, M, per_state, flags):
+        """mpcd_clip_flags: flags[m] <- LimitsNormalizer's clip code over state m's per_state consecutive values of src"""
+        N.check(self._lib.mpcd_clip_flags(self._ctx, _p(src), M, per_state, _p(flags), self._stream()), "mpcd_clip_flags")
 
-    def _rollout_cost_box_raw(self, desc, x_dev, group, u_norm, flags, box, cost, viol):
-        B, H, _ = u_norm.shape
-        N.check(self._lib.mpcd_rollout_cost_box(self._ctx, ctypes.byref(desc), ctypes.c_void_p(x_dev.data_ptr()), group,
-                                                ctypes.c_void_p(u_norm.data_ptr()), self.act_min.ctypes.data,
-                                                self.act_max.ctypes.data, B, H, ctypes.c_void_p(flags.data_ptr()),
-                                                ctypes.byref(box), ctypes.c_void_p(cost.data_ptr()),
-                                                ctypes.c_void_p(viol.data_ptr()), self._stream()), "mpcd_rollout_cost_box")
+    def _rollout_feasible(self, system, x0_states, u_norm, group, clip_flags, feas=None, **spec):
+        """rollout_cost_box / rollout_cost_constr: one body. feas: the call's Feasibility, or None to build it from
+        **spec (feasibility()'s arguments) once the shapes are checked."""
+        B, H, d = u_norm.shape
+        _check_inputs(system, d)
+        x = _rows_dev(x0_states, self.device, "x0_states", None, system.n_x)
+        M = x.shape[0]
+        group = _group_split(B, M, group, "candidates")
+        if feas is None:
+            feas = feasibility(system, **spec)
+        up = _rows_dev(feas.u_prev, self.device, "u_prev", M, d)
+        u_norm = u_norm.contiguous()
+        if clip_flags is None:
+            clip_flags = torch.empty(M, dtype=torch.int32, device=self.device)
+            self._clip_flags(u_norm, M, group * H * d, clip_flags)
+        else:
+            _check_clip_flags(clip_flags, M, self.device)
+        cost = torch.empty(B, dtype=torch.float64, device=self.device)
+        viol = torch.empty(B, dtype=torch.float64, device=self.device)
+        feas.rollout(self, system.desc(), x, group, u_norm, clip_flags, cost, viol, up)
+        return cost, viol
 
     def rollout_cost_box(self, system: System, x0_states, u_norm, state_box, group=None, clip_flags=None):
         """rollout_cost for M start states with a state box (mpcd_rollout_cost_box): (cost [B], violation [B]) device
@@ -710,59 +728,7 @@ class DiffusionMPC:
         cost evaluation visits over state_box = (lo, hi)), None entries = unbounded; the start state is not tested; +inf
         where an excess is NaN. clip_flags: device int32 [M] clip codes (one per state); default: LimitsNormalizer's
         rule over each state's own candidates of u_norm."""
-        B, H, d = u_norm.shape
-        if d != system.n_u:
-            raise ValueError(f"system {system.name} has {system.n_u} inputs, samples have {d}")
-        if torch.is_tensor(x0_states):
-            x = x0_states.to(self.device, torch.float64)
-        else:
-            x = torch.from_numpy(np.ascontiguousarray(x0_states, dtype=np.float64)).to(self.device)
-        x = (x[None] if x.dim() == 1 else x).contiguous()
-        M = x.shape[0]
-        if x.dim() != 2 or x.shape[1] != system.n_x:
-            raise ValueError(f"x0_states must be [M, {system.n_x}], got {tuple(x.shape)}")
-        group = B // M if group is None else int(group)
-        if group < 1 or M * group != B:
-            raise ValueError(f"u_norm has {B} candidates: not {M} states x group={group}")
-        box = self._state_box(state_box, system.n_x)
-        u_norm = u_norm.contiguous()
-        if clip_flags is None:
-            clip_flags = torch.empty(M, dtype=torch.int32, device=self.device)
-            N.check(self._lib.mpcd_clip_flags(self._ctx, ctypes.c_void_p(u_norm.data_ptr()), M, group * H * d,
-                                              ctypes.c_void_p(clip_flags.data_ptr()), self._stream()), "mpcd_clip_flags")
-        elif clip_flags.dtype != torch.int32 or clip_flags.device != self.device or clip_flags.numel() != M:
-            raise ValueError(f"clip_flags must be {M} int32 codes on {self.device}")
-        cost = torch.empty(B, dtype=torch.float64, device=self.device)
-        viol = torch.empty(B, dtype=torch.float64, device=self.device)
-        self._rollout_cost_box_raw(system.desc(), x, group, u_norm, clip_flags, box, cost, viol)
-        return cost, viol
-
-    @staticmethod
-    def _constraints(constraints, system):
-        if not isinstance(constraints, Constraints):
-            raise ValueError("constraints must be a Constraints(state_box=, rows=, du_max=)")
-        return constraints.native(system.n_x, system.n_u)
-
-    def _u_prev(self, u_prev, M, n_u):
-        """u_prev [M, n_u] (or [n_u] for one state; a NaN row: none) as a device float64 tensor, or None"""
-        if u_prev is None:
-            return None
-        if torch.is_tensor(u_prev):
-            up = u_prev.to(self.device, torch.float64)
-        else:
-            up = torch.from_numpy(np.ascontiguousarray(u_prev, dtype=np.float64)).to(self.device)
-        up = (up[None] if up.dim() == 1 else up).contiguous()
-        if tuple(up.shape) != (M, n_u):
-            raise ValueError(f"u_prev must be [{M}, {n_u}], got {tuple(up.shape)}")
-        return up
-
-    def _rollout_cost_constr_raw(self, desc, x_dev, group, u_norm, flags, con, u_prev, cost, viol):
-        B, H, _ = u_norm.shape
-        N.check(self._lib.mpcd_rollout_cost_constr(
-            self._ctx, ctypes.byref(desc), ctypes.c_void_p(x_dev.data_ptr()), group, ctypes.c_void_p(u_norm.data_ptr()),
-            self.act_min.ctypes.data, self.act_max.ctypes.data, B, H, ctypes.c_void_p(flags.data_ptr()), ctypes.byref(con),
-            None if u_prev is None else ctypes.c_void_p(u_prev.data_ptr()), ctypes.c_void_p(cost.data_ptr()),
-            ctypes.c_void_p(viol.data_ptr()), self._stream()), "mpcd_rollout_cost_constr")
+        return self._rollout_feasible(system, x0_states, u_norm, group, clip_flags, kind="state_box", state_box=state_box)
 
     def rollout_cost_constr(self, system: System, x0_states, u_norm, constraints, group=None, clip_flags=None, u_prev=None):
         """rollout_cost_box with a constraint set (mpcd_rollout_cost_constr): (cost [B], violation [B]) device float64
@@ -771,33 +737,8 @@ class DiffusionMPC:
         [M, n_u] (host values or a device float64 tensor; [n_u] for one state): each state's previous applied action,
         the predecessor of u_0 in the rate test; None, or a row with a NaN: that state's rate test starts at u_1.
         x0_states, group, clip_flags: rollout_cost_box's. cost is bit for bit the unconstrained rollout's."""
-        B, H, d = u_norm.shape
-        if d != system.n_u:
-            raise ValueError(f"system {system.name} has {system.n_u} inputs, samples have {d}")
-        if torch.is_tensor(x0_states):
-            x = x0_states.to(self.device, torch.float64)
-        else:
-            x = torch.from_numpy(np.ascontiguousarray(x0_states, dtype=np.float64)).to(self.device)
-        x = (x[None] if x.dim() == 1 else x).contiguous()
-        M = x.shape[0]
-        if x.dim() != 2 or x.shape[1] != system.n_x:
-            raise ValueError(f"x0_states must be [M, {system.n_x}], got {tuple(x.shape)}")
-        group = B // M if group is None else int(group)
-        if group < 1 or M * group != B:
-            raise ValueError(f"u_norm has {B} candidates: not {M} states x group={group}")
-        con = self._constraints(constraints, system)
-        up = self._u_prev(u_prev, M, d)
-        u_norm = u_norm.contiguous()
-        if clip_flags is None:
-            clip_flags = torch.empty(M, dtype=torch.int32, device=self.device)
-            N.check(self._lib.mpcd_clip_flags(self._ctx, ctypes.c_void_p(u_norm.data_ptr()), M, group * H * d,
-                                              ctypes.c_void_p(clip_flags.data_ptr()), self._stream()), "mpcd_clip_flags")
-        elif clip_flags.dtype != torch.int32 or clip_flags.device != self.device or clip_flags.numel() != M:
-            raise ValueError(f"clip_flags must be {M} int32 codes on {self.device}")
-        cost = torch.empty(B, dtype=torch.float64, device=self.device)
-        viol = torch.empty(B, dtype=torch.float64, device=self.device)
-        self._rollout_cost_constr_raw(system.desc(), x, group, u_norm, clip_flags, con, up, cost, viol)
-        return cost, viol
+        return self._rollout_feasible(system, x0_states, u_norm, group, clip_flags, kind="constraints",
+                                      constraints=constraints, u_prev=u_prev)
 
     def _topk_feasible_raw(self, cost, viol, k, n_groups, tol, index_offset=0):
         """mpcd_topk_feasible: (mpcd_best records as int64 [M, k, 2] (cost bits, index), violation [M, k], n_feasible [M])"""
@@ -813,10 +754,8 @@ class DiffusionMPC:
         raw = torch.empty((M, k, 2), dtype=torch.int64, device=self.device)
         vk = torch.empty((M, k), dtype=torch.float64, device=self.device)
         nf = torch.empty(M, dtype=torch.int64, device=self.device)
-        N.check(self._lib.mpcd_topk_feasible(self._ctx, ctypes.c_void_p(cost.data_ptr()), ctypes.c_void_p(viol.data_ptr()),
-                                             M, group, k, self._viol_tol(tol), int(index_offset),
-                                             ctypes.c_void_p(raw.data_ptr()), ctypes.c_void_p(vk.data_ptr()),
-                                             ctypes.c_void_p(nf.data_ptr()), self._stream()), "mpcd_topk_feasible")
+        N.check(self._lib.mpcd_topk_feasible(self._ctx, _p(cost), _p(viol), M, group, k, _viol_tol(tol), int(index_offset),
+                                             _p(raw), _p(vk), _p(nf), self._stream()), "mpcd_topk_feasible")
         return raw, vk, nf
 
     def topk_feasible(self, cost, violation, k, n_groups=1, tol=0.0, index_offset=0):
@@ -831,11 +770,9 @@ class DiffusionMPC:
     def _control_step_picked_raw(self, desc, x, u_norm, raw, index_offset, flags, decimals, u_out, i_out, c_out):
         B, H, _ = u_norm.shape
         N.check(self._lib.mpcd_control_step_picked(
-            self._ctx, ctypes.byref(desc), ctypes.c_void_p(x.data_ptr()), raw.shape[0], ctypes.c_void_p(u_norm.data_ptr()),
-            B, H, ctypes.c_void_p(raw.data_ptr()), raw.shape[1], int(index_offset), self.act_min.ctypes.data,
-            self.act_max.ctypes.data, ctypes.c_void_p(flags.data_ptr()), -1 if decimals is None else int(decimals),
-            ctypes.c_void_p(u_out.data_ptr()), ctypes.c_void_p(i_out.data_ptr()), ctypes.c_void_p(c_out.data_ptr()),
-            self._stream()), "mpcd_control_step_picked")
+            self._ctx, ctypes.byref(desc), _p(x), raw.shape[0], _p(u_norm), B, H, _p(raw), raw.shape[1], int(index_offset),
+            self.act_min.ctypes.data, self.act_max.ctypes.data, _p(flags), -1 if decimals is None else int(decimals),
+            _p(u_out), _p(i_out), _p(c_out), self._stream()), "mpcd_control_step_picked")
 
     def control_step_picked(self, system: System, x_states, u_norm, index, cost, clip_flags, decimals=4, index_offset=0):
         """One control step with the selection supplied (mpcd_control_step_picked): state m applies candidate index[m] -
@@ -849,14 +786,12 @@ class DiffusionMPC:
                 or x_states.dim() != 2 or x_states.shape[1] != system.n_x or not x_states.is_contiguous()):
             raise ValueError(f"x_states must be a contiguous float64 [M, {system.n_x}] tensor on {self.device}")
         M = x_states.shape[0]
-        if d != system.n_u:
-            raise ValueError(f"system {system.name} has {system.n_u} inputs, samples have {d}")
+        _check_inputs(system, d)
         if index.dtype != torch.int64 or index.device != self.device or index.numel() != M:
             raise ValueError(f"index must be {M} int64 entries on {self.device}")
         if cost.dtype != torch.float64 or cost.device != self.device or cost.numel() != M:
             raise ValueError(f"cost must be {M} float64 entries on {self.device}")
-        if clip_flags.dtype != torch.int32 or clip_flags.device != self.device or clip_flags.numel() != M:
-            raise ValueError(f"clip_flags must be {M} int32 codes on {self.device}")
+        _check_clip_flags(clip_flags, M, self.device)
         raw = torch.empty((M, 1, 2), dtype=torch.int64, device=self.device)
         raw[:, 0, 0] = cost.reshape(M).view(torch.int64)
         raw[:, 0, 1] = index.reshape(M)
@@ -866,6 +801,36 @@ class DiffusionMPC:
         self._control_step_picked_raw(system.desc(), x_states, u_norm.contiguous(), raw, index_offset, clip_flags, decimals,
                                       u_out, i_out, c_out)
         return u_out, i_out, c_out
+
+    def _check_modes(self, K, sample_fn, select, clip_rule, elites, n, native=False):
+        """closed_loop's and the batched step's refusals over warm_start=K, select, clip_rule and elites; n: the
+        candidates per state the elite count is checked against (None: not yet). Returns the checked elite count."""
+        if elites is not None:
+            if K is None:
+                raise ValueError(_ELITES_NEED_WARM)
+            if native:
+                raise ValueError("elites is not available with native=True: mpcd_closed_loop's fused tail writes one "
+                                 "prior per state; use native=False")
+            if select != "argmin":
+                raise ValueError("elites ranks candidates by cost: it needs select='argmin'")
+            if n is not None:
+                elites = self._check_elites(elites, n)
+        if K is not None and (K < 1 or K > self.n_steps or self._sampler_id(sample_fn) != N.MPCD_DDPM_CFG):
+            raise ValueError(f"warm_start={K} needs 1 <= K <= {self.n_steps} and the CFG-DDPM sampler")
+        if select not in ("argmin", "first"):
+            raise ValueError("select must be 'argmin' or 'first'")
+        if clip_rule not in _CLIP_RULES:
+            raise ValueError(_BAD_CLIP_RULE)
+        return elites
+
+    def _check_plant(self, system, nx, what):
+        """a call that conditions on the plant state (`what`, for the text): states of nx columns against the planning
+        model and the net"""
+        if nx != system.n_x or system.n_u != self.spec.state_dim:
+            raise ValueError(f"system {system.name}: n_x={system.n_x}, n_u={system.n_u}; states have {nx} columns, "
+                             f"the net samples {self.spec.state_dim} actions")
+        if self.spec.context_dim != nx:
+            raise ValueError(f"{what} conditions on the plant state: context_dim {self.spec.context_dim} != n_x {nx}")
 
     def closed_loop(self, x0_states, system: System, iterations, n_samples=1, w=0.01, sample_fn="ddpm_cfg",
                     n_wo_noise=0, ddim_steps=None, clamp_x0=False, select="argmin", decimals=4, seed=0, noise=None,
@@ -919,48 +884,12 @@ class DiffusionMPC:
         u_prev [M, n_u] or None is each state's previous applied action for iteration 0 (a NaN row: none); every later
         iteration's is the previous iteration's applied (rounded) action, read on the device. Same refusals."""
         K = None if warm_start is None else int(warm_start)
-        box = con = None
-        if constraints is not None:
-            if state_box is not None:
-                raise ValueError("state_box together with constraints: put the box into the set, "
-                                 "Constraints(state_box=...)")
-            if native:
-                raise ValueError("constraints are not available with native=True: mpcd_closed_loop's fused tail takes no "
-                                 "constraint set; use native=False")
-            if select != "argmin":
-                raise ValueError("constraints rank candidates feasibility-first: they need select='argmin'")
-            con, tol = self._constraints(constraints, system), self._viol_tol(viol_tol)
-        elif u_prev is not None:
-            raise ValueError("u_prev serves the rate bounds of constraints=")
-        if state_box is not None:
-            if native:
-                raise ValueError("state_box is not available with native=True: folding the constraint into "
-                                 "mpcd_closed_loop's fused tail is the follow-up; use native=False")
-            if select != "argmin":
-                raise ValueError("state_box ranks candidates feasibility-first: it needs select='argmin'")
-            box, tol = self._state_box(state_box, system.n_x), self._viol_tol(viol_tol)
-        if elites is not None:
-            if K is None:
-                raise ValueError("elites needs warm_start=K: the elite set seeds the warm-start priors")
-            if native:
-                raise ValueError("elites is not available with native=True: mpcd_closed_loop's fused tail writes one "
-                                 "prior per state; use native=False")
-            if select != "argmin":
-                raise ValueError("elites ranks candidates by cost: it needs select='argmin'")
-            elites = self._check_elites(elites, int(n_samples))
-        if K is not None and (K < 1 or K > self.n_steps or self._sampler_id(sample_fn) != N.MPCD_DDPM_CFG):
-            raise ValueError(f"warm_start={K} needs 1 <= K <= {self.n_steps} and the CFG-DDPM sampler")
-        if select not in ("argmin", "first"):
-            raise ValueError("select must be 'argmin' or 'first'")
-        if clip_rule not in _CLIP_RULES:
-            raise ValueError(f"clip_rule must be one of {sorted(_CLIP_RULES)}")
+        feas = feasibility(system, state_box, constraints, viol_tol, u_prev,
+                           refuse=((native, _NO_NATIVE_LOOP), (select != "argmin", NEEDS_ARGMIN)))
+        elites = self._check_modes(K, sample_fn, select, clip_rule, elites, int(n_samples), native)
         x0 = np.ascontiguousarray(np.atleast_2d(np.asarray(x0_states, dtype=np.float64)))
         M, nx = x0.shape
-        if nx != system.n_x or system.n_u != self.spec.state_dim:
-            raise ValueError(f"system {system.name}: n_x={system.n_x}, n_u={system.n_u}; states have {nx} columns, "
-                             f"the net samples {self.spec.state_dim} actions")
-        if self.spec.context_dim != nx:
-            raise ValueError(f"closed loop conditions on the plant state: context_dim {self.spec.context_dim} != n_x {nx}")
+        self._check_plant(system, nx, "closed loop")
         T, n, H, d = int(iterations), int(n_samples), self.spec.horizon, self.spec.state_dim
         B, dev, st = M * n, self.device, self._stream()
         if native:
@@ -968,74 +897,58 @@ class DiffusionMPC:
                                             decimals, seed, noise, clip_rule, grouped, K)
         desc = system.desc()
         x = torch.from_numpy(x0).to(dev)
-        xs = torch.empty((T + 1, M, nx), dtype=torch.float64, device=dev)
-        us = torch.empty((T, M, d), dtype=torch.float64, device=dev)
-        cs = torch.empty((T, M), dtype=torch.float64, device=dev)
-        ix = torch.empty((T, M), dtype=torch.int64, device=dev)
+        xs, us, cs, ix = _history(T, M, nx, d, dev)
         ctx = torch.empty((M, nx), dtype=torch.float32, device=dev)
         flags = torch.empty(M, dtype=torch.int32, device=dev)
         cost = torch.empty(B, dtype=torch.float64, device=dev)
         u_norm = torch.empty((B, H, d), dtype=torch.float32, device=dev)
         absmax = torch.empty(B, dtype=torch.float32, device=dev) if clip_rule == "chain" else None
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         grouped = bool(grouped) and self.grouped_pays(M, n, sample_fn)
         priors = None
         if K is not None:  # one prior per state, or (elites) one per candidate
             priors = torch.empty((M if elites is None else B, H, d), dtype=torch.float32, device=dev)
-        if box is not None or con is not None:
+        if feas is not None:
             viol = torch.empty(B, dtype=torch.float64, device=dev)
             vs = torch.empty((T, M), dtype=torch.float64, device=dev)
             nfs = torch.empty((T, M), dtype=torch.int64, device=dev)
-        if con is not None:
-            up = self._u_prev(u_prev, M, d)
+            up = _rows_dev(feas.u_prev, dev, "u_prev", M, d)
         xs[0] = x
         for it in range(T):
             warm = {}
             if K is not None and it > 0:
-                if elites is not None:
-                    warm = dict(x_init=priors, t_start=K)
-                else:
-                    warm = dict(x_init=priors if grouped else priors.repeat_interleave(n, dim=0), t_start=K)
-            N.check(self._lib.mpcd_normalize_states(self._ctx, ptr(x), M, nx, self.ctx_min.ctypes.data,
-                                                    self.ctx_max.ctypes.data, ptr(ctx), st), "mpcd_normalize_states")
+                per_row = elites is not None or grouped  # the sampler takes the priors as they are
+                warm = dict(x_init=priors if per_row else priors.repeat_interleave(n, dim=0), t_start=K)
+            N.check(self._lib.mpcd_normalize_states(self._ctx, _p(x), M, nx, self.ctx_min.ctypes.data,
+                                                    self.ctx_max.ctypes.data, _p(ctx), st), "mpcd_normalize_states")
             self.sample_trajectories(ctx if grouped else ctx.repeat_interleave(n, dim=0), B, H, w, sample_fn, n_wo_noise,
                                      ddim_steps, clamp_x0, seed + it, 0, None if noise is None else noise(it), False,
                                      out=u_norm, absmax_out=absmax, context_group=n if grouped else None, **warm)
             if absmax is not None:  # each state's flag over its candidates' chains
-                N.check(self._lib.mpcd_clip_flags(self._ctx, ptr(absmax), M, n, ptr(flags), st), "mpcd_clip_flags")
+                self._clip_flags(absmax, M, n, flags)
             else:
-                N.check(self._lib.mpcd_clip_flags(self._ctx, ptr(u_norm), M, n * H * d, ptr(flags), st), "mpcd_clip_flags")
-            if box is not None or con is not None:  # feasibility-first: one ranked list serves the selection and the next priors
-                if con is not None:  # the predecessor of u_0: the action the plant received last
-                    self._rollout_cost_constr_raw(desc, x, n, u_norm, flags, con, up if it == 0 else us[it - 1], cost, viol)
-                else:
-                    self._rollout_cost_box_raw(desc, x, n, u_norm, flags, box, cost, viol)
-                raw, vk, nf = self._topk_feasible_raw(cost, viol, elites or 1, M, tol)
+                self._clip_flags(u_norm, M, n * H * d, flags)
+            if feas is None:
+                N.check(self._lib.mpcd_rollout_cost_grouped(self._ctx, ctypes.byref(desc), _p(x), n, _p(u_norm),
+                                                            self.act_min.ctypes.data, self.act_max.ctypes.data, B, H,
+                                                            _p(flags), _p(cost), st), "mpcd_rollout_cost_grouped")
+                N.check(self._lib.mpcd_control_step(self._ctx, ctypes.byref(desc), _p(x), M, n, _p(u_norm), H, _p(cost),
+                                                    self.act_min.ctypes.data, self.act_max.ctypes.data, _p(flags),
+                                                    1 if select == "first" else 0, -1 if decimals is None else int(decimals),
+                                                    _p(us[it]), _p(ix[it]), _p(cs[it]), st), "mpcd_control_step")
+                raw = None if elites is None else self._topk_raw(cost, elites, M)
+            else:  # feasibility-first: one ranked list serves the selection and the next priors
+                # the predecessor of u_0 in a set's rate test: the action the plant received last
+                feas.rollout(self, desc, x, n, u_norm, flags, cost, viol, up if it == 0 else us[it - 1])
+                raw, vk, nf = self._topk_feasible_raw(cost, viol, elites or 1, M, feas.tol)
                 self._control_step_picked_raw(desc, x, u_norm, raw, 0, flags, decimals, us[it], ix[it], cs[it])
-                if elites is not None:
-                    self._elite_priors_raw(u_norm, raw, n, True, 0, priors)
-                elif K is not None:
-                    self.shift_plans(u_norm, ix[it], 0, out=priors)
                 vs[it], nfs[it] = vk[:, 0], nf
-                xs[it + 1] = x
-                continue
-            N.check(self._lib.mpcd_rollout_cost_grouped(self._ctx, ctypes.byref(desc), ptr(x), n, ptr(u_norm),
-                                                        self.act_min.ctypes.data, self.act_max.ctypes.data, B, H,
-                                                        ptr(flags), ptr(cost), st), "mpcd_rollout_cost_grouped")
-            N.check(self._lib.mpcd_control_step(self._ctx, ctypes.byref(desc), ptr(x), M, n, ptr(u_norm), H, ptr(cost),
-                                                self.act_min.ctypes.data, self.act_max.ctypes.data, ptr(flags),
-                                                1 if select == "first" else 0, -1 if decimals is None else int(decimals),
-                                                ptr(us[it]), ptr(ix[it]), ptr(cs[it]), st), "mpcd_control_step")
             if elites is not None:
-                self._elite_priors_raw(u_norm, self._topk_raw(cost, elites, M), n, True, 0, priors)
+                self._elite_priors_raw(u_norm, raw, n, True, 0, priors)
             elif K is not None:
                 self.shift_plans(u_norm, ix[it], 0, out=priors)
             xs[it + 1] = x
-        res = ClosedLoopResult(x=xs.transpose(0, 1).cpu().numpy(), u=us.transpose(0, 1).cpu().numpy(),
-                               cost=cs.t().cpu().numpy(), index=ix.t().cpu().numpy())
-        if box is not None or con is not None:
-            res.violation, res.n_feasible = vs.t().cpu().numpy(), nfs.t().cpu().numpy()
-        return res
+        more = {} if feas is None else dict(violation=vs.t().cpu().numpy(), n_feasible=nfs.t().cpu().numpy())
+        return _loop_result(xs, us, cs, ix, **more)
 
     def _closed_loop_native(self, x0, system, T, n, w, sample_fn, n_wo_noise, ddim_steps, clamp_x0, select, decimals,
                             seed, noise, clip_rule, grouped, K):
@@ -1049,24 +962,12 @@ class DiffusionMPC:
         if noise is not None:  # evaluated up front and kept alive until the results are on the host
             cold = self.n_denoise_steps(sample_fn, n_wo_noise, ddim_steps)
             later = cold if K is None else self.n_denoise_steps(sample_fn, n_wo_noise, ddim_steps, K)
-            noises = []
-            for it in range(T):
-                z = noise(it).to(dev, torch.float32).contiguous()
-                steps = cold if it == 0 else later
-                if tuple(z.shape) != (steps + 1, B, H, d):
-                    raise ValueError(f"noise must be [{steps + 1}, {B}, {H}, {d}], got {tuple(z.shape)}")
-                noises.append(z)
+            noises = [self._noise(noise(it), B, cold if it == 0 else later) for it in range(T)]
         grouped = bool(grouped) and self.grouped_pays(M, n, sample_fn)
         x = torch.from_numpy(x0).to(dev)
-        xs = torch.empty((T + 1, M, nx), dtype=torch.float64, device=dev)
-        us = torch.empty((T, M, d), dtype=torch.float64, device=dev)
-        cs = torch.empty((T, M), dtype=torch.float64, device=dev)
-        ix = torch.empty((T, M), dtype=torch.int64, device=dev)
+        xs, us, cs, ix = _history(T, M, nx, d, dev)
         desc = system.desc()
-        a = N.ClosedLoopArgs()
-        a.sys = ctypes.pointer(desc)
-        a.ctx_min, a.ctx_max = self.ctx_min.ctypes.data, self.ctx_max.ctypes.data
-        a.act_min, a.act_max = self.act_min.ctypes.data, self.act_max.ctypes.data
+        a = self._plant_block(N.ClosedLoopArgs(), desc)
         u_norm = torch.empty((B, H, d), dtype=torch.float32, device=dev)
         a.sample = self._args(self._sampler_id(sample_fn), B, _STEP_CONTEXT, w, n_wo_noise, ddim_steps, clamp_x0, seed, 0,
                               None, u_norm, None)
@@ -1084,8 +985,7 @@ class DiffusionMPC:
         a.x_dev, a.x_hist, a.u_hist = x.data_ptr(), xs.data_ptr(), us.data_ptr()
         a.cost_hist, a.index_hist = cs.data_ptr(), ix.data_ptr()
         N.check(self._lib.mpcd_closed_loop(self._ctx, ctypes.byref(a), self._stream()), "mpcd_closed_loop")
-        res = ClosedLoopResult(x=xs.transpose(0, 1).cpu().numpy(), u=us.transpose(0, 1).cpu().numpy(),
-                               cost=cs.t().cpu().numpy(), index=ix.t().cpu().numpy(), u_norm=u_norm)
+        res = _loop_result(xs, us, cs, ix, u_norm=u_norm)
         del noises  # the copies above waited for the loop: its inputs may go now
         return res
 
@@ -1149,10 +1049,9 @@ class DiffusionMPC:
         0 no candidate stayed in the box: the least violating plan is returned and the state's flags carry
         MPCD_STEP_INFEASIBLE - not an error; the caller decides whether to apply it. An all-infinite box with
         viol_tol=0 returns mpc_step_batch's results bit for bit."""
-        if kw.get("select", "argmin") != "argmin":
-            raise ValueError("state_box ranks candidates feasibility-first: it needs select='argmin'")
-        box, tol = self._state_box(state_box, system.n_x), self._viol_tol(viol_tol)
-        return self._mpc_step_batch(x_states, system, n_samples, box=(box, tol), **kw)
+        feas = feasibility(system, state_box, viol_tol=viol_tol, kind="state_box",
+                           refuse=((kw.get("select", "argmin") != "argmin", NEEDS_ARGMIN),))
+        return self._mpc_step_batch(x_states, system, n_samples, feas=feas, **kw)
 
     def mpc_step_batch_constr(self, x_states, system: System, n_samples, constraints, viol_tol=0.0, u_prev=None, **kw):
         """mpc_step_batch_box with a constraint set in place of the box: still ONE library call
@@ -1162,37 +1061,19 @@ class DiffusionMPC:
         applied action (the predecessor of u_0 in the rate test; a NaN row: none), uploaded with the states in the one
         copy. A state named by `reset` whose row the caller left out (u_prev=None) has none. **kw, the kept prior set,
         the `reset` split and the result fields: mpc_step_batch_box's."""
-        if kw.get("select", "argmin") != "argmin":
-            raise ValueError("constraints rank candidates feasibility-first: they need select='argmin'")
-        con, tol = self._constraints(constraints, system), self._viol_tol(viol_tol)
         x = np.asarray(x_states, dtype=np.float64)
-        M = 1 if x.ndim == 1 else x.shape[0]
-        up = None
-        if u_prev is not None:
-            up = np.ascontiguousarray(np.atleast_2d(np.asarray(u_prev, dtype=np.float64)))
-            if up.shape != (M, system.n_u):
-                raise ValueError(f"u_prev must be [{M}, {system.n_u}], got {up.shape}")
-        return self._mpc_step_batch(x_states, system, n_samples, box=(con, tol, up), **kw)
+        feas = feasibility(system, None, constraints, viol_tol, u_prev, kind="constraints",
+                           refuse=((kw.get("select", "argmin") != "argmin", NEEDS_ARGMIN),),
+                           u_prev_shape=(1 if x.ndim == 1 else x.shape[0], system.n_u))
+        return self._mpc_step_batch(x_states, system, n_samples, feas=feas, **kw)
 
     def _mpc_step_batch(self, x_states, system, n_samples, w=0.01, sample_fn="ddpm_cfg", n_wo_noise=0, ddim_steps=None,
                         clamp_x0=False, seed=0, noise=None, select="argmin", decimals=4, clip_rule="chain", grouped=False,
-                        warm_start=None, reset=None, return_samples=False, allow_nonfinite=False, elites=None, box=None):
-        """mpc_step_batch, mpc_step_batch_box (box = (mpcd_state_box, tol), checked) and mpc_step_batch_constr (box =
-        (mpcd_constraints, tol, u_prev [M, n_u] or None), checked): one body, one kept prior set"""
-        K = None if warm_start is None else int(warm_start)
-        if elites is not None:
-            if K is None:
-                raise ValueError("elites needs warm_start=K: the elite set seeds the warm-start priors")
-            if select != "argmin":
-                raise ValueError("elites ranks candidates by cost: it needs select='argmin'")
-            if int(n_samples) >= 1:
-                elites = self._check_elites(elites, int(n_samples))
-        if K is not None and (K < 1 or K > self.n_steps or self._sampler_id(sample_fn) != N.MPCD_DDPM_CFG):
-            raise ValueError(f"warm_start={K} needs 1 <= K <= {self.n_steps} and the CFG-DDPM sampler")
-        if select not in ("argmin", "first"):
-            raise ValueError("select must be 'argmin' or 'first'")
-        if clip_rule not in _CLIP_RULES:
-            raise ValueError(f"clip_rule must be one of {sorted(_CLIP_RULES)}")
+                        warm_start=None, reset=None, return_samples=False, allow_nonfinite=False, elites=None, feas=None):
+        """mpc_step_batch, mpc_step_batch_box and mpc_step_batch_constr (feas: their Feasibility, with host u_prev rows):
+        one body, one kept prior set"""
+        K, n = None if warm_start is None else int(warm_start), int(n_samples)
+        elites = self._check_modes(K, sample_fn, select, clip_rule, elites, n if n >= 1 else None)  # (n < 1: refused below)
         if self.spec.dtype == "f16x2":
             raise ValueError("mpc_step_batch does not take an f16x2 spec: its range guard reads the chain maxima on "
                              "the host and re-runs the sampler, a second round trip inside the step")
@@ -1203,12 +1084,7 @@ class DiffusionMPC:
             raise ValueError(f"x_states must be [M, n_x], got {x.shape}")
         x = np.ascontiguousarray(x)
         M, nx = x.shape
-        if nx != system.n_x or system.n_u != self.spec.state_dim:
-            raise ValueError(f"system {system.name}: n_x={system.n_x}, n_u={system.n_u}; states have {nx} columns, "
-                             f"the net samples {self.spec.state_dim} actions")
-        if self.spec.context_dim != nx:
-            raise ValueError(f"the step conditions on the plant state: context_dim {self.spec.context_dim} != n_x {nx}")
-        n = int(n_samples)
+        self._check_plant(system, nx, "the step")
         if n < 1:
             raise ValueError(f"n_samples={n} must be >= 1")
         mask = None
@@ -1219,7 +1095,7 @@ class DiffusionMPC:
         H, d = self.spec.horizon, self.spec.state_dim
         kw = dict(system=system, n=n, w=w, sample_fn=sample_fn, n_wo_noise=n_wo_noise, ddim_steps=ddim_steps,
                   clamp_x0=clamp_x0, seed=seed, select=select, decimals=decimals, clip_rule=clip_rule, grouped=grouped,
-                  return_samples=return_samples, elites=elites, box=box)
+                  return_samples=return_samples, elites=elites)
         priors = getattr(self, "_batch_priors", None) if K is not None else None
         if priors is not None and priors.shape[0] != M:
             priors = None  # the fleet changed size: a cold start
@@ -1239,41 +1115,30 @@ class DiffusionMPC:
             warm = K is not None and priors is not None and not (mask is not None and mask.all())
             if K is not None and not warm:
                 priors = torch.empty((M,) + pshape, dtype=torch.float32, device=self.device)
-            res, bad = self._batch_step_call(x, K if warm else 0, priors, noise, **kw)
+            res, bad = self._batch_step_call(x, K if warm else 0, priors, noise, feas=feas, **kw)
         else:
             ic, iw = np.flatnonzero(mask), np.flatnonzero(~mask)
             tc, tw = torch.from_numpy(ic).to(self.device), torch.from_numpy(iw).to(self.device)
             pc = torch.empty((len(ic),) + pshape, dtype=torch.float32, device=self.device)
             pw = priors.index_select(0, tw)
-            kc = kwm = kw
-            if box is not None and len(box) == 3 and box[2] is not None:  # each sub-call takes its states' u_prev rows
-                kc, kwm = dict(kw, box=(box[0], box[1], box[2][ic])), dict(kw, box=(box[0], box[1], box[2][iw]))
-            rc_, bad_c = self._batch_step_call(x[ic], 0, pc, noise[0], **kc)
-            rw_, bad_w = self._batch_step_call(x[iw], K, pw, noise[1], **kwm)
+            fc, fw = (None, None) if feas is None else (feas.restrict(ic), feas.restrict(iw))  # their u_prev rows
+            rc_, bad_c = self._batch_step_call(x[ic], 0, pc, noise[0], feas=fc, **kw)
+            rw_, bad_w = self._batch_step_call(x[iw], K, pw, noise[1], feas=fw, **kw)
             priors.index_copy_(0, tc, pc)
             priors.index_copy_(0, tw, pw)
             bad = bad_c or bad_w
-            res = BatchStepResult(u=np.empty((M, d)), plan=np.empty((M, H, d), dtype=np.float32), cost=np.empty(M),
-                                  index=np.empty(M, dtype=np.int64), flags=np.empty(M, dtype=np.int32))
+            # every host field a sub-call returned, scattered to its states' rows (index and elite_index renumbered
+            # from the sub-call's batch to the whole one's)
+            res = BatchStepResult(**{f: np.empty((M,) + v.shape[1:], dtype=v.dtype) for f, v in vars(rc_).items()
+                                     if isinstance(v, np.ndarray)})
             if return_samples:
                 res.u_norm = torch.empty((M * n, H, d), dtype=torch.float32, device=self.device)
-            if elites is not None:
-                res.elite_index = np.empty((M, elites), dtype=np.int64)
-                res.elite_cost = np.empty((M, elites))
-            if box is not None:
-                res.violation, res.n_feasible = np.empty(M), np.empty(M, dtype=np.int64)
-                if elites is not None:
-                    res.elite_violation = np.empty((M, elites))
             for idx, tidx, sub in ((ic, tc, rc_), (iw, tw, rw_)):
-                res.u[idx], res.plan[idx], res.cost[idx], res.flags[idx] = sub.u, sub.plan, sub.cost, sub.flags
-                res.index[idx] = idx * n + (sub.index - np.arange(len(idx)) * n)
-                if elites is not None:
-                    res.elite_cost[idx] = sub.elite_cost
-                    res.elite_index[idx] = (idx * n)[:, None] + (sub.elite_index - (np.arange(len(idx)) * n)[:, None])
-                    if box is not None:
-                        res.elite_violation[idx] = sub.elite_violation
-                if box is not None:
-                    res.violation[idx], res.n_feasible[idx] = sub.violation, sub.n_feasible
+                first = (idx - np.arange(len(idx))) * n
+                for f, v in vars(sub).items():
+                    if isinstance(v, np.ndarray):
+                        renumber = f in ("index", "elite_index")
+                        getattr(res, f)[idx] = v + first.reshape((-1,) + (1,) * (v.ndim - 1)) if renumber else v
                 if return_samples:
                     res.u_norm.view(M, n, H, d).index_copy_(0, tidx, sub.u_norm.view(len(idx), n, H, d))
         if K is not None:
@@ -1299,25 +1164,18 @@ class DiffusionMPC:
         self._batch_priors = priors
 
     def _batch_step_call(self, x, t_start, priors, noise, system, n, w, sample_fn, n_wo_noise, ddim_steps, clamp_x0,
-                         seed, select, decimals, clip_rule, grouped, return_samples, elites=None, box=None):
+                         seed, select, decimals, clip_rule, grouped, return_samples, elites=None, feas=None):
         """One mpcd_mpc_step_batch call on the states x [M, n_x] (checked by mpc_step_batch): (BatchStepResult, whether
         the call returned MPCD_ENONFINITE). priors: device [M, H, d] read when t_start > 0 and refreshed, or None.
-        elites=k: mpcd_mpc_step_batch_elite, priors [M, n, H, d]. box = (mpcd_state_box, tol): mpcd_mpc_step_batch_box,
-        with or without elites; box = (mpcd_constraints, tol, u_prev [M, n_u] or None): mpcd_mpc_step_batch_constr."""
+        elites=k: mpcd_mpc_step_batch_elite, priors [M, n, H, d]. feas: a Feasibility for these states, with or without
+        elites - mpcd_mpc_step_batch_box or mpcd_mpc_step_batch_constr, as it says."""
         x = np.ascontiguousarray(x)
         M = x.shape[0]
         H, d, B, dev = self.spec.horizon, self.spec.state_dim, M * n, self.device
         sampler = self._sampler_id(sample_fn)
         if noise is not None:
-            steps = self.n_denoise_steps(sample_fn, n_wo_noise, ddim_steps, t_start or None)
-            noise = noise.to(dev, torch.float32).contiguous()
-            if tuple(noise.shape) != (steps + 1, B, H, d):
-                raise ValueError(f"noise must be [{steps + 1}, {B}, {H}, {d}], got {tuple(noise.shape)}")
-        desc = self._system_desc(system)
-        a = N.BatchStepArgs()
-        a.sys = ctypes.pointer(desc)
-        a.ctx_min, a.ctx_max = self.ctx_min.ctypes.data, self.ctx_max.ctypes.data
-        a.act_min, a.act_max = self.act_min.ctypes.data, self.act_max.ctypes.data
+            noise = self._noise(noise, B, (sample_fn, n_wo_noise, ddim_steps, t_start or None))
+        a = self._plant_block(N.BatchStepArgs(), self._system_desc(system))
         u_norm = torch.empty((B, H, d), dtype=torch.float32, device=dev) if return_samples else None
         a.sample = self._args(sampler, B, _STEP_CONTEXT, w, n_wo_noise, ddim_steps, clamp_x0, seed, 0, noise,
                               self._flag, None)
@@ -1343,23 +1201,10 @@ class DiffusionMPC:
             e.priors = priors.data_ptr() if priors is not None else None
             best = np.empty((M, elites), dtype=_BEST)
             e.elites_host = best.ctypes.data
-        if box is not None:
-            if len(box) == 3:
-                bx = N.BatchConstrArgs()
-                bx.con, bx.tol = ctypes.pointer(box[0]), box[1]
-                up = None if box[2] is None else np.ascontiguousarray(box[2], dtype=np.float64)
-                bx.u_prev_host = None if up is None else up.ctypes.data
-                call = self._lib.mpcd_mpc_step_batch_constr
-            else:
-                bx = N.BatchBoxArgs()
-                bx.box, bx.tol = ctypes.pointer(box[0]), box[1]
-                call = self._lib.mpcd_mpc_step_batch_box
-            viol, nfeas = np.empty(M, dtype=np.float64), np.empty(M, dtype=np.int64)
-            bx.viol_host, bx.n_feasible_host = viol.ctypes.data, nfeas.ctypes.data
-            if elites is not None:
-                eviol = np.empty((M, elites), dtype=np.float64)
-                bx.elite_viol_host = eviol.ctypes.data
-            rc = call(self._ctx, ctypes.byref(a), None if e is None else ctypes.byref(e), ctypes.byref(bx), self._stream())
+        if feas is not None:
+            name, bx, viol, nfeas, eviol = feas.batch_block(M, elites)
+            rc = getattr(self._lib, name)(self._ctx, ctypes.byref(a), None if e is None else ctypes.byref(e),
+                                          ctypes.byref(bx), self._stream())
         elif e is None:
             rc = self._lib.mpcd_mpc_step_batch(self._ctx, ctypes.byref(a), self._stream())
         else:
@@ -1370,10 +1215,8 @@ class DiffusionMPC:
                               flags=rec["flags"].copy(), u_norm=u_norm)
         if elites is not None:
             res.elite_index, res.elite_cost = best["index"].copy(), best["cost"].copy()
-        if box is not None:
-            res.violation, res.n_feasible = viol, nfeas
-            if elites is not None:
-                res.elite_violation = eviol
+        if feas is not None:
+            res.violation, res.n_feasible, res.elite_violation = viol, nfeas, eviol
         return res, rc == N.MPCD_ENONFINITE
 
     def mpc_step(self, x0, system: System, n_samples, w=0.01, sample_fn="ddpm_cfg", n_wo_noise=0, ddim_steps=None,
@@ -1416,43 +1259,23 @@ class DiffusionMPC:
         producer of V (the box goes into the set: state_box= together with constraints= raises ValueError); u_prev is the
         previous applied action, the predecessor of u_0 in the rate test. Same result fields, same refusals."""
         if clip_rule not in _CLIP_RULES:
-            raise ValueError(f"clip_rule must be one of {sorted(_CLIP_RULES)}")
+            raise ValueError(_BAD_CLIP_RULE)
         if comm is not None:
             rank, size = comm.rank, comm.size
         else:
             rank, size = D.world(group)
-        box = con = None
-        if constraints is not None:
-            if state_box is not None:
-                raise ValueError("state_box together with constraints: put the box into the set, "
-                                 "Constraints(state_box=...)")
-            if native:
-                raise ValueError("constraints are not available with native=True: the fused step (mpcd_mpc_step) takes "
-                                 "no constraint set; leave native unset or False")
-            if warm_start is not None or prior is not None or elites is not None:
-                raise ValueError("constraints with warm_start / prior / elites need the native step, which takes no "
-                                 "constraint set; closed_loop(native=False) combines them")
-            if comm is not None or size > 1:
-                raise ValueError("constraints are single-rank: there is no multi-rank feasibility-first selection")
-            con, tol, native = self._constraints(constraints, system), self._viol_tol(viol_tol), False
-        elif u_prev is not None:
-            raise ValueError("u_prev serves the rate bounds of constraints=")
-        if state_box is not None:
-            if native:
-                raise ValueError("state_box is not available with native=True: the fused step (mpcd_mpc_step) takes no box; "
-                                 "its follow-up mpc_step_constr does (Constraints(state_box=...)), or leave native unset")
-            if warm_start is not None or prior is not None or elites is not None:
-                raise ValueError("state_box with warm_start / prior / elites needs the native step, which takes no box: "
-                                 "use its follow-up mpc_step_constr, or closed_loop(native=False)")
-            if comm is not None or size > 1:
-                raise ValueError("state_box is single-rank here: the multi-rank feasibility-first selection is the "
-                                 "follow-up mpc_step_constr's")
-            box, tol, native = self._state_box(state_box, system.n_x), self._viol_tol(viol_tol), False
+        feas = None
+        if state_box is not None or constraints is not None or u_prev is not None:  # (the plain step pays one test)
+            feas = feasibility(system, state_box, constraints, viol_tol, u_prev, refuse=(
+                (native, _NO_NATIVE_STEP),
+                (warm_start is not None or prior is not None or elites is not None, _NO_WARM_STEP),
+                (comm is not None or size > 1, _SINGLE_RANK_STEP)))
+            native = False
         if native is None:
             native = comm is not None or size == 1
         if elites is not None:
             if warm_start is None:
-                raise ValueError("elites needs warm_start=K: the elite set seeds the warm-start priors")
+                raise ValueError(_ELITES_NEED_WARM)
             if not native:
                 raise ValueError("elites needs the native step (native=True)")
             if comm is not None or size > 1:
@@ -1479,12 +1302,9 @@ class DiffusionMPC:
             flag = self.clip_flag(absmax if absmax is not None else u_norm)
             if size > 1:
                 flag = comm.any_flag(flag) if comm else D.any_flag(flag, group)
-        if box is not None or con is not None:
-            if con is not None:
-                cost_local, viol = self.rollout_cost_constr(system, x0, u_norm, constraints, clip_flags=flag, u_prev=u_prev)
-            else:
-                cost_local, viol = self.rollout_cost_box(system, x0, u_norm, state_box, clip_flags=flag)
-            raw, vk, nf = self._topk_feasible_raw(cost_local, viol, 1, 1, tol)
+        if feas is not None:
+            cost_local, viol = self._rollout_feasible(system, x0, u_norm, None, flag, feas)
+            raw, vk, nf = self._topk_feasible_raw(cost_local, viol, 1, 1, feas.tol)
             idx, best = int(raw[0, 0, 1]), float(raw[0, 0, 0:1].view(torch.float64))
             u_host = self.unnormalize_states(u_norm[idx][None], flag)[0].cpu().numpy()
             return MPCResult(u0=u_host[0].copy(), u_best=u_host, best_cost=best, best_index=idx, costs=cost_local,
@@ -1514,65 +1334,17 @@ class DiffusionMPC:
         ValueError: constraints that is no Constraints, a bad viol_tol, a u_prev that is not [n_u], elites without
         warm_start or with a comm, several torch.distributed ranks without a NativeComm."""
         if clip_rule not in _CLIP_RULES:
-            raise ValueError(f"clip_rule must be one of {sorted(_CLIP_RULES)}")
-        con = self._constraints(constraints, system)
-        tol = self._viol_tol(viol_tol)
-        up = None
-        if u_prev is not None:
-            up = np.ascontiguousarray(u_prev.detach().cpu().numpy() if torch.is_tensor(u_prev) else u_prev, dtype=np.float64)
-            if up.shape != (system.n_u,):
-                raise ValueError(f"u_prev must be [{system.n_u}], got {tuple(up.shape)}")
+            raise ValueError(_BAD_CLIP_RULE)
+        feas = feasibility(system, None, constraints, viol_tol, u_prev, kind="constraints", u_prev_shape=(system.n_u,))
         if elites is not None:
             if warm_start is None:
-                raise ValueError("elites needs warm_start=K: the elite set seeds the warm-start priors")
+                raise ValueError(_ELITES_NEED_WARM)
             if comm is not None:
                 raise ValueError("elites is single-rank: the elite rows live on other ranks (no comm)")
-        if comm is not None:
-            rank, size = comm.rank, comm.size
-        else:
-            rank, size = D.world(None)
-            if size > 1:
-                raise ValueError("mpc_step_constr on several ranks needs a NativeComm")
-        B, H, d = int(n_samples), self.spec.horizon, self.spec.state_dim
-        if d != system.n_u:
-            raise ValueError(f"system {system.name} has {system.n_u} inputs, samples have {d}")
-        sampler = self._sampler_id(sample_fn)
-        warm, prior, nxt, elites = self._step_warm(sampler, B, warm_start, prior, elites)
-        noise = self._step_noise(noise, sample_fn, n_wo_noise, ddim_steps, warm, B)
-        u_norm = torch.empty((B, H, d), dtype=torch.float32, device=self.device)
-        cost = torch.empty(B, dtype=torch.float64, device=self.device)
-        viol = torch.empty(B, dtype=torch.float64, device=self.device)
-        costs = torch.empty(size * B, dtype=torch.float64, device=self.device) if size > 1 else cost
-        viols = torch.empty(size * B, dtype=torch.float64, device=self.device) if size > 1 else viol
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        desc = self._system_desc(system)
-        a = self._step_args(desc, sampler, B, w, n_wo_noise, ddim_steps, clamp_x0, seed, rank * B, noise, u_norm, clip_rule)
-        a.x0 = x0.__array_interface__["data"][0]
-        a.cost_local, a.costs_all = cost.data_ptr(), costs.data_ptr()
-        e = N.StepConstrArgs()
-        e.con, e.tol = ctypes.pointer(con), tol
-        e.u_prev_host = up.ctypes.data if up is not None else None
-        e.viol_local, e.viols_all = viol.data_ptr(), viols.data_ptr()
-        e.k = elites or 0
-        e.next_priors_out = nxt.data_ptr() if nxt is not None else None
-        el = ev = None
-        if elites is not None:
-            el, ev = np.empty(elites, dtype=_BEST), np.empty(elites, dtype=np.float64)
-            e.elites_host, e.elite_viol_host = el.ctypes.data, ev.ctypes.data
-        v_host, nf_host = ctypes.c_double(), ctypes.c_int64()
-        e.viol_host, e.n_feasible_host = ctypes.pointer(v_host), ctypes.pointer(nf_host)
-        best, fl = N.Best(), ctypes.c_int32()
-        u_best = np.empty((H, d), dtype=np.float32)
-        # MPCD_ENONFINITE (the selected cost is not finite: NaN / Inf samples) raises MpcdError here
-        N.check(self._lib.mpcd_mpc_step_constr(self._ctx, ctypes.byref(a), ctypes.byref(warm) if warm is not None else None,
-                                               ctypes.byref(e), ctypes.byref(best), u_best.__array_interface__["data"][0],
-                                               self._stream()), "mpcd_mpc_step_constr")
-        self._swap_prior(nxt)
-        N.check(self._lib.mpcd_last_step_flags(self._ctx, ctypes.byref(fl)), "mpcd_last_step_flags")
-        return MPCResult(u0=u_best[0].copy(), u_best=u_best, best_cost=best.cost, best_index=best.index, costs=costs,
-                         u_norm=u_norm, flags=fl.value, elite_index=None if el is None else el["index"].copy(),
-                         elite_cost=None if el is None else el["cost"].copy(), violation=v_host.value,
-                         n_feasible=nf_host.value, elite_violation=ev)
+        if comm is None and D.world(None)[1] > 1:
+            raise ValueError("mpc_step_constr on several ranks needs a NativeComm")
+        return self._mpc_step_native(x0, system, n_samples, w, sample_fn, n_wo_noise, ddim_steps, clamp_x0, seed, noise,
+                                     comm, clip_rule, warm_start, prior, elites, feas)
 
     def reset_warm_start(self):
         """Drop the prior plan mpc_step(warm_start=K) keeps and the prior set mpc_step_batch(warm_start=K) keeps: the
@@ -1612,23 +1384,9 @@ class DiffusionMPC:
             nxt = torch.empty((rows, H, d), dtype=torch.float32, device=self.device)
         return warm, prior, nxt, elites
 
-    def _step_noise(self, noise, sample_fn, n_wo_noise, ddim_steps, warm, B):
-        """Injected noise on the device, one slice per denoise step of this call (fewer after a warm start) and one more."""
-        if noise is None:
-            return None
-        H, d = self.spec.horizon, self.spec.state_dim
-        steps = self.n_denoise_steps(sample_fn, n_wo_noise, ddim_steps, warm.t_start or None if warm else None)
-        noise = noise.to(self.device, torch.float32).contiguous()
-        if tuple(noise.shape) != (steps + 1, B, H, d):
-            raise ValueError(f"noise must be [{steps + 1}, {B}, {H}, {d}], got {tuple(noise.shape)}")
-        return noise
-
     def _step_args(self, desc, sampler, B, w, n_wo_noise, ddim_steps, clamp_x0, seed, offset, noise, u_norm, clip_rule):
         """The StepArgs block of a native single-state step, all but x0 and the cost pointers."""
-        a = N.StepArgs()
-        a.sys = ctypes.pointer(desc)
-        a.ctx_min, a.ctx_max = self.ctx_min.ctypes.data, self.ctx_max.ctypes.data
-        a.act_min, a.act_max = self.act_min.ctypes.data, self.act_max.ctypes.data
+        a = self._plant_block(N.StepArgs(), desc)
         a.sample = self._args(sampler, B, _STEP_CONTEXT, w, n_wo_noise, ddim_steps, clamp_x0, seed, offset, noise, u_norm,
                               None)
         a.clip_rule = _CLIP_RULES[clip_rule]
@@ -1643,24 +1401,26 @@ class DiffusionMPC:
             self._prior, self._prior_spare = nxt, getattr(self, "_prior", None)
 
     def _mpc_step_native(self, x0, system, n_samples, w, sample_fn, n_wo_noise, ddim_steps, clamp_x0, seed, noise,
-                         comm, clip_rule="chain", warm_start=None, prior=None, elites=None):
-        """mpc_step as one libmpcd call (mpcd_mpc_step): the context row by value in the sampler launch, the kernels,
-        the result block {best, u_best} written to pinned host memory by the selecting workgroup (one rank) or one
-        D2H copy + stream synchronisation (with a communicator)."""
+                         comm, clip_rule="chain", warm_start=None, prior=None, elites=None, feas=None):
+        """mpc_step and mpc_step_constr (feas: its Feasibility, u_prev a host [n_u] row) as one libmpcd call
+        (mpcd_mpc_step, _warm, _elite or _constr): the context row by value in the sampler launch, the kernels, the
+        result block {best, u_best} written to pinned host memory by the selecting workgroup (one rank) or one D2H copy +
+        stream synchronisation (with a communicator)."""
         size, rank = (comm.size, comm.rank) if comm is not None else (1, 0)
-        B, H, d = int(n_samples), self.spec.horizon, self.spec.state_dim
-        if d != system.n_u:
-            raise ValueError(f"system {system.name} has {system.n_u} inputs, samples have {d}")
+        B, H, d, dev = int(n_samples), self.spec.horizon, self.spec.state_dim, self.device
+        _check_inputs(system, d)
         sampler = self._sampler_id(sample_fn)
         warm, prior, nxt, elites = self._step_warm(sampler, B, warm_start, prior, elites)
-        noise = self._step_noise(noise, sample_fn, n_wo_noise, ddim_steps, warm, B)
-        u_norm = torch.empty((B, H, d), dtype=torch.float32, device=self.device)
-        cost = torch.empty(B, dtype=torch.float64, device=self.device)
-        costs = torch.empty(size * B, dtype=torch.float64, device=self.device) if size > 1 else cost
+        if noise is not None:
+            noise = self._noise(noise, B, (sample_fn, n_wo_noise, ddim_steps, warm.t_start or None if warm else None))
+        u_norm = torch.empty((B, H, d), dtype=torch.float32, device=dev)
+        cost = torch.empty(B, dtype=torch.float64, device=dev)
+        costs = torch.empty(size * B, dtype=torch.float64, device=dev) if size > 1 else cost
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
         desc = self._system_desc(system)
-        # the argument block of a control loop's repeated call is built once and patched per step (x0, seed, the
-        # output pointers): the host path between two sampler launches is part of every control step's latency
+        # the argument block of a control loop's repeated call is built once and patched per step (x0, seed, noise, the
+        # output pointers): the host path between two sampler launches is part of every control step's latency. The key
+        # is everything else the block holds: rank * B is its global_offset, clip_rule with the sampler its clip code
         key = (id(desc), B, sampler, float(w), int(n_wo_noise), ddim_steps, bool(clamp_x0), clip_rule, size, rank,
                noise is None)
         cache = getattr(self, "_step_args_cache", None)
@@ -1679,23 +1439,38 @@ class DiffusionMPC:
         a.cost_local = cost.data_ptr()
         a.costs_all = costs.data_ptr()
         u_best = np.empty((H, d), dtype=np.float32)
+        ub, st = u_best.__array_interface__["data"][0], self._stream()
+        el = None if elites is None else np.empty(elites, dtype=_BEST)
+        more = {}
         # MPCD_ENONFINITE (no candidate with a finite cost: NaN / Inf samples) raises MpcdError here
-        el = None
-        if warm is None:
-            N.check(self._lib.mpcd_mpc_step(self._ctx, a_ref, ctypes.byref(best), u_best.__array_interface__["data"][0],
-                                            self._stream()), "mpcd_mpc_step")
-        elif elites is not None:
-            el = np.empty(elites, dtype=_BEST)
-            N.check(self._lib.mpcd_mpc_step_elite(self._ctx, a_ref, ctypes.byref(warm), elites,
-                                                  ctypes.c_void_p(nxt.data_ptr()), el.ctypes.data, ctypes.byref(best),
-                                                  u_best.__array_interface__["data"][0], self._stream()),
-                    "mpcd_mpc_step_elite")
+        if feas is not None:  # the set, its outputs and the warm / elite outputs travel in one block, built per call
+            viol = torch.empty(B, dtype=torch.float64, device=dev)
+            viols = torch.empty(size * B, dtype=torch.float64, device=dev) if size > 1 else viol
+            e = N.StepConstrArgs()
+            e.con, e.tol = ctypes.pointer(feas.native), feas.tol
+            e.u_prev_host = feas.u_prev.ctypes.data if feas.u_prev is not None else None
+            e.viol_local, e.viols_all = viol.data_ptr(), viols.data_ptr()
+            e.k = elites or 0
+            e.next_priors_out = nxt.data_ptr() if nxt is not None else None
+            ev = None
+            if el is not None:
+                ev = np.empty(elites, dtype=np.float64)
+                e.elites_host, e.elite_viol_host = el.ctypes.data, ev.ctypes.data
+            v_host, nf_host = ctypes.c_double(), ctypes.c_int64()
+            e.viol_host, e.n_feasible_host = ctypes.pointer(v_host), ctypes.pointer(nf_host)
+            N.check(self._lib.mpcd_mpc_step_constr(self._ctx, a_ref, ctypes.byref(warm) if warm is not None else None,
+                                                   ctypes.byref(e), ctypes.byref(best), ub, st), "mpcd_mpc_step_constr")
+            more = dict(violation=v_host.value, n_feasible=nf_host.value, elite_violation=ev)
+        elif warm is None:
+            N.check(self._lib.mpcd_mpc_step(self._ctx, a_ref, ctypes.byref(best), ub, st), "mpcd_mpc_step")
+        elif el is not None:
+            N.check(self._lib.mpcd_mpc_step_elite(self._ctx, a_ref, ctypes.byref(warm), elites, _p(nxt), el.ctypes.data,
+                                                  ctypes.byref(best), ub, st), "mpcd_mpc_step_elite")
         else:
-            N.check(self._lib.mpcd_mpc_step_warm(self._ctx, a_ref, ctypes.byref(warm), ctypes.c_void_p(nxt.data_ptr()),
-                                                 ctypes.byref(best), u_best.__array_interface__["data"][0],
-                                                 self._stream()), "mpcd_mpc_step_warm")
+            N.check(self._lib.mpcd_mpc_step_warm(self._ctx, a_ref, ctypes.byref(warm), _p(nxt), ctypes.byref(best), ub, st),
+                    "mpcd_mpc_step_warm")
         self._swap_prior(nxt)
         N.check(self._lib.mpcd_last_step_flags(self._ctx, ctypes.byref(fl)), "mpcd_last_step_flags")
         return MPCResult(u0=u_best[0].copy(), u_best=u_best, best_cost=best.cost, best_index=best.index, costs=costs,
                          u_norm=u_norm, flags=fl.value, elite_index=None if el is None else el["index"].copy(),
-                         elite_cost=None if el is None else el["cost"].copy())
+                         elite_cost=None if el is None else el["cost"].copy(), **more)

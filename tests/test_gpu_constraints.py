@@ -16,6 +16,7 @@ import torch
 from mpc_via_diffusion_model_amd import Constraints, systems
 from mpc_via_diffusion_model_amd import _native as nat
 from mpc_via_diffusion_model_amd import distributed as D
+from mpc_via_diffusion_model_amd.constraints import Feasibility
 
 from ._util import unnormalize_np
 from .test_gpu_comm import _key
@@ -401,18 +402,18 @@ def test_closed_loop_constraints(warm, first):
     inplan = np.abs(np.diff(np.clip(u0, -1, 1).astype(np.float64), axis=1)).max(axis=1)
     du, tol = [float(_median(inplan[:, j])) for j in range(d)], 0.01
     con = Constraints(du_max=du)
-    passed, raw = [], plan._rollout_cost_constr_raw  # what the loop hands the rollout as u_prev, iteration by iteration
+    passed, raw = [], Feasibility.rollout  # what the loop hands the rollout as u_prev, iteration by iteration
 
-    def spy(desc, x_dev, group, u_norm, flags, cset, up, cost, viol):
+    def spy(feas, pl, desc, x_dev, group, u_norm, flags, cost, viol, up=None):
         passed.append(None if up is None else up.cpu().numpy().copy())
-        return raw(desc, x_dev, group, u_norm, flags, cset, up, cost, viol)
+        return raw(feas, pl, desc, x_dev, group, u_norm, flags, cost, viol, up)
 
-    plan._rollout_cost_constr_raw = spy
+    Feasibility.rollout = spy
     try:
         got = plan.closed_loop(x0, sysm, T, n_samples=n, w=0.01, noise=lambda it: draws[it], warm_start=K, elites=k,
                                constraints=con, u_prev=u_prev, viol_tol=tol)
     finally:
-        del plan._rollout_cost_constr_raw
+        Feasibility.rollout = raw
     assert len(passed) == T and (passed[0] is None if u_prev is None else np.array_equal(passed[0], u_prev, equal_nan=True))
     for it in range(1, T):
         np.testing.assert_array_equal(passed[it], got.u[:, it - 1], err_msg="u_prev is not the action applied last")

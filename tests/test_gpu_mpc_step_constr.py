@@ -764,3 +764,38 @@ def test_the_first_entry_point_on_a_context_does_not_matter(first_calls, first, 
     for form in [first] + [f for f in FORMS if f != first]:
         got = _result_bits(_form(plan, form, sysm, seed, con, clip_rule))
         assert got == want[form, clip_rule], f"{form} after {first} first"
+
+
+# ------------------------------------------------------------------------ 12. the cached argument block
+def _keyed_step(plan, sysm, con, a):
+    """mpc_step / mpc_step_constr at double_int2d with the arguments a; injected noise is a function of a alone"""
+    z = None
+    if a["noise"]:
+        z = torch.randn(LOOP_N + a["n_wo_noise"] + 1, a["n"], 16, 2, generator=torch.Generator().manual_seed(5))
+    kw = dict(seed=a["seed"], w=a["w"], clip_rule=a["clip_rule"], noise=z, n_wo_noise=a["n_wo_noise"])
+    if a["constr"]:
+        return plan.mpc_step_constr(X0, sysm, a["n"], con, u_prev=U_PREV, **kw)
+    return plan.mpc_step(X0, sysm, a["n"], **kw)
+
+
+def test_the_cached_argument_block_follows_every_argument():
+    """mpc_step and mpc_step_constr share one cached argument block, rebuilt when its key changes and patched per call.
+    One planner runs a sequence of calls in which consecutive calls differ in exactly one argument - seed, w, n_samples
+    (70 -> 134 -> 70: two and three workgroups, the last one ragged), clip_rule, injected noise against Philox,
+    n_wo_noise, constrained against not - and every result is, bit for bit, that of the same call made first on a fresh
+    planner: an argument missing from the key, or patched too late, shows as the previous call's value."""
+    sysm = systems.double_int2d()
+    seed, con = _live_set(_loop_plan(), sysm, 70)
+    a = dict(constr=False, n=70, seed=seed, w=0.01, clip_rule="chain", noise=False, n_wo_noise=0)
+    changes = [{}, dict(seed=seed + 1), dict(w=0.05), dict(n=134), dict(constr=True), dict(n=70), dict(clip_rule="final"),
+               dict(noise=True), dict(n_wo_noise=2), dict(constr=False), dict(noise=False), dict(n_wo_noise=0), dict(w=0.01),
+               dict(constr=True), dict(seed=seed), dict(clip_rule="chain"), dict(n=134), dict(constr=False)]
+    plan, distinct = _loop_plan(), set()
+    for i, change in enumerate(changes):
+        assert len(change) <= 1 and all(a[k] != v for k, v in change.items())
+        a.update(change)
+        got = _result_bits(_keyed_step(plan, sysm, con, a))
+        assert got == _result_bits(_keyed_step(_loop_plan(), sysm, con, a)), f"call {i}, after changing {change}: {a}"
+        distinct.add(got)
+    print(f"\n{len(distinct)} distinct results in {len(changes)} calls")
+    assert len(distinct) == len(changes), "every change must show in the result, or a stale value could hide behind it"

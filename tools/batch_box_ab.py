@@ -51,6 +51,7 @@ def worker(a):
     if a.worker == "parent":  # the parent's library has no such entry point to bind
         N.EXPORTS.pop("mpcd_mpc_step_batch_box", None)
     from mpc_via_diffusion_model_amd import DiffusionMPC, NetSpec, systems
+    from mpc_via_diffusion_model_amd.constraints import Feasibility
     from oracle import nets
 
     assert torch.cuda.is_available(), "a timing needs the GPU"
@@ -64,7 +65,8 @@ def worker(a):
     dev, L, ctx = plan.device, plan._lib, plan._ctx
     ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
     box_py = ([None, None, -a.bound, -a.bound], [None, None, a.bound, a.bound])
-    box_c, tol = plan._state_box(box_py, 4), 0.0
+    tol = 0.0
+    box_f = Feasibility("state_box", plan._state_box(box_py, 4), tol)
 
     def states(M):
         return np.random.default_rng(0).uniform(-1.0, 1.0, (T + 1, M, 4))
@@ -122,7 +124,7 @@ def worker(a):
                                      False, 1 + it, 0, None, False, out=u_norm, absmax_out=absmax,
                                      context_group=n if grouped else None, **warm)
             N.check(L.mpcd_clip_flags(ctx, ptr(absmax), M, n, ptr(flags), st), "mpcd_clip_flags")
-            plan._rollout_cost_box_raw(desc, x, n, u_norm, flags, box_c, cost, viol)
+            box_f.rollout(plan, desc, x, n, u_norm, flags, cost, viol)
             raw, vk, nf = plan._topk_feasible_raw(cost, viol, kk, M, tol)
             # x is this step's own upload: the plant step lands in a buffer nobody reads again
             plan._control_step_picked_raw(desc, x, u_norm, raw, 0, flags, 4, us, ix, cs)
